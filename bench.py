@@ -9,6 +9,11 @@ frames, LP + TCN loss, encoder backward (+ RCCL gradient all-reduce overlapped w
 Trainer.update (BASELINE config 2: "ResNet-50 encoder fwd+bwd bs=256 fp32, TCN loss only, synthetic frames").
 "bs=256" is 256 clips per GPU = 1280 frames per GPU (the reference's batch_size counts clips).
 Prints ONE JSON line on rank 0.
+
+A plain run times the one workload its arguments name and nothing else. --full also measures, after that workload's timed steps, what
+the line reports besides it: the other BASELINE configs and the inference points under "secondary" (headline workload only) and the
+CPU baseline. --dump-outputs DIR writes what the last timed step computed (metrics and the model state it leaves) as .npy files; the
+timed steps start from the same state and random draws in every run, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -96,7 +101,13 @@ def parse_args(argv=None):
                          "idle period with 2 warm-up steps and 348 ms with 12; 119.8 vs 105.6 ms in bf16). 0 disables.")
     ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket the conv GEMM launches with HIP events (diagnostic: "
                                                                      "measures what the live roofline timing costs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the 'secondary' BASELINE configs and inference points "
+                         "(headline workload only) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's metrics and the model state it leaves to DIR/<name>.npy "
+                         "(float64 / float32, at most 64 MB: larger tensors as a fixed sample, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-clips", type=int, default=8)
     ap.add_argument("--launch-csv", default="", help="write one row per conv GEMM launch of the timed steps (layer report)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -109,7 +120,7 @@ def parse_args(argv=None):
     ap.add_argument("--no-bind", action="store_true",
                     help="N > 1: do not pin each rank to cores of its GPU's NUMA node (r3m_amd/utils/affinity.py)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short measurements of the other BASELINE configs that the default (headline) run appends under "
+                    help="skip the short measurements of the other BASELINE configs that --full appends to the headline under "
                          "'secondary' AFTER the headline's timed region")
     ap.add_argument("--secondary-steps", type=int, default=10)
     ap.add_argument("--secondary-warmup", type=int, default=5)
@@ -117,7 +128,7 @@ def parse_args(argv=None):
 
 
 def is_headline(args):
-    """The default workload = BASELINE configs[1]; only that run appends the 'secondary' measurements."""
+    """The default workload = BASELINE configs[1]; only that run appends the 'secondary' measurements (with --full)."""
     return (args.size == 50 and args.precision == "fp32" and args.langweight == 0 and args.doaug == "none"
             and args.encoder_only_frames == 0 and args.clips_per_gpu == 256)
 
@@ -194,9 +205,52 @@ def workload_label(w, world):
     return lab
 
 
-def measure(w, steps, warmup, prewarm_seconds, ctx, kernel_timing=True, launch_csv=""):
+def reset_state(core, initial):
+    """Put R3M `core` back, in place, to `initial` (its state_dict before any step) with the optimizer at no step taken: zero Adam
+    moments and step counts are exactly what a fresh FusedAdam starts from."""
+    core.load_state_dict(initial)
+    opt = core.encoder_opt
+    opt._steps = [0] * len(opt._steps)
+    for m, v in zip(opt._m, opt._v):
+        if m is not None:
+            m.zero_()
+            v.zero_()
+
+
+DUMP_BUDGET_BYTES = 48 << 20     # state tensors; with the metrics well under the 64 MB that --dump-outputs promises
+
+
+def dump_outputs(out_dir, metrics, core, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what a caller of Trainer.update holds after the last timed step. `metric_<key>.npy` (float64 scalar) for every
+    metric the step returned, `<state_dict key>.npy` (float32, logical shape; integer counters as float64) for every parameter and
+    buffer of the model it updated. A tensor above the per-tensor cap is written as `<key>.sample.npy`: its flattened (logical order)
+    elements at the sorted indices numpy.random.default_rng(0).choice(numel, cap, replace=False); the cap is the largest power of two
+    that keeps all state files within `budget` bytes."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in metrics.items():
+        np.save(os.path.join(out_dir, f"metric_{k}.npy"), np.asarray(v, dtype=np.float64))
+    sd = core.state_dict()
+    sizes = [(t.numel(), 4 if t.is_floating_point() else 8) for t in sd.values()]
+    cap = 1 << 24
+    while sum(min(n, cap) * b for n, b in sizes) > budget:
+        cap //= 2
+    for k, t in sd.items():
+        t = t.detach()
+        dt = torch.float32 if t.is_floating_point() else torch.float64
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=cap, replace=False))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].to(dt).cpu().numpy()
+            np.save(os.path.join(out_dir, f"{k}.sample.npy"), a)
+        else:
+            np.save(os.path.join(out_dir, f"{k}.npy"), t.to(dt).cpu().numpy())
+
+
+def measure(w, steps, warmup, prewarm_seconds, ctx, kernel_timing=True, launch_csv="", dump_dir=""):
     """One workload `w` (dict: size, clips, precision, langweight, doaug, unfused_crop, encoder_only_frames): build the model,
-    W warm-up steps, then EXACTLY K timed steps between barrier + synchronize; returns the JSON object (rank 0) or None."""
+    W warm-up steps, then EXACTLY K timed steps between barrier + synchronize; returns the JSON object (rank 0) or None.
+    The timed steps start from the model's initial state and the same random draws whatever ran before them; with `dump_dir`,
+    rank 0 writes what the last of them computed there (dump_outputs)."""
     import gc
     from r3m_amd import R3M, _lib
     from r3m_amd.parallel import make_network_wrapper
@@ -211,6 +265,7 @@ def measure(w, steps, warmup, prewarm_seconds, ctx, kernel_timing=True, launch_c
     model = model.to(dev)
     net = make_network_wrapper(model, force=use_dist)
     g = torch.Generator(device=dev).manual_seed(1234 + rank)
+    box_gen = None
     if w["doaug"] == "none":
         frames = torch.randint(0, 256, (B, 5, 3, 224, 224), generator=g, device=dev, dtype=torch.int32).float()
         get_frames = lambda: frames
@@ -253,6 +308,10 @@ def measure(w, steps, warmup, prewarm_seconds, ctx, kernel_timing=True, launch_c
         trainer = _EncTrainer()
         get_frames = lambda: xe
 
+    # the pre-warm runs for a fixed wall time, so a varying number of steps (weight updates, random draws) precedes the timed ones:
+    # the state they start from is the initial one again (reset after the warm-up, outside the timed region)
+    core = net.module
+    initial = {k: v.detach().clone() for k, v in core.state_dict().items()}
     prewarm_steps = 0
     if prewarm_seconds > 0:                             # device warm-up (clock ramp), outside both the W warm-up and the timed K steps
         t_pw = time.perf_counter()
@@ -286,6 +345,11 @@ def measure(w, steps, warmup, prewarm_seconds, ctx, kernel_timing=True, launch_c
             warm_bytes = (C.c_double * 4)()
             _lib.check(L.r3m_profile_collect_bytes(warm_bytes), "profile_collect_bytes")
             L.r3m_profile_enable(0)
+    reset_state(core, initial)
+    del initial
+    torch.manual_seed(1)                               # Trainer.update's torch.randperm draws
+    if box_gen is not None:
+        box_gen.manual_seed(99 + rank)
     timed_classes = 0xF
     if warm_ms is not None and max(warm_ms) > 0:
         timed_classes = 1 << max(range(4), key=lambda k: warm_ms[k])
@@ -321,6 +385,8 @@ def measure(w, steps, warmup, prewarm_seconds, ctx, kernel_timing=True, launch_c
         dt_max, dt_min = max(b[0] for b in by_rank), min(b[0] for b in by_rank)
         comm_exposed_ms = max(b[1] for b in by_rank)
         dt = dt_max
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, metrics, core)
     collectives = ((f"rccl all_reduce(AVG)" if dist.is_initialized() and dist.get_backend() == "nccl" else "gloo all_reduce(SUM)/N")
                    + f", {net.sync.launched / max(1, total_steps):.1f} per step"
                    + (" (one-rank group: identity, issued to exercise the path)" if world == 1 else "")) if use_dist \
@@ -404,7 +470,7 @@ def measure(w, steps, warmup, prewarm_seconds, ctx, kernel_timing=True, launch_c
                                          f"{w['encoder_only_frames']} frames of 224x224x3 per GPU, {'bf16 activations' if bf16 else 'fp32'}")
             out["config"]["frames_per_gpu"] = w["encoder_only_frames"]
     # release the activation arena (the dominant HBM allocation) before the next workload is built
-    del trainer, net, model, get_frames
+    del trainer, net, model, core, get_frames
     gc.collect()
     torch.cuda.empty_cache()
     return out
@@ -563,8 +629,8 @@ def main():
     w = dict(size=args.size, clips=args.clips_per_gpu, precision=args.precision, langweight=args.langweight, doaug=args.doaug,
              unfused_crop=args.unfused_crop, encoder_only_frames=args.encoder_only_frames)
     out = measure(w, args.steps, args.warmup, args.prewarm_seconds, ctx, kernel_timing=not args.no_kernel_timing,
-                  launch_csv=args.launch_csv)
-    if is_headline(args) and not args.no_secondary and args.secondary_steps > 0:
+                  launch_csv=args.launch_csv, dump_dir=args.dump_outputs)
+    if args.full and is_headline(args) and not args.no_secondary and args.secondary_steps > 0:
         sec = {}
         for name, sw in SECONDARY:
             sw = dict({"encoder_only_frames": 0}, **sw, unfused_crop=False)
@@ -600,7 +666,7 @@ def main():
             out["kernel_timing_note"] = ("timed steps bracket the dominant kernel class only (fence-free HIP events, 99 launches): "
                                          "0.3 ms per step in the interleaved same-box A/B profiles/r05_event_fence_ab.txt")
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if affinity0 is not None:
                 os.sched_setaffinity(0, affinity0)       # the CPU baseline uses the host's cores, not the rank's NUMA slice
             out["cpu_baseline"] = cpu_baseline(args.size, args.cpu_clips)

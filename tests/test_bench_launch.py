@@ -145,3 +145,59 @@ def test_bind_rank_never_raises_and_keeps_a_nonempty_mask():
     # a slice smaller than what the caller needs (launcher + loader workers) leaves the mask alone and says so
     info = affinity.bind_rank(0, 2, device_indices=[0, 1], set_threads=False, min_cpus=10 ** 6)
     assert ("skipped" in info or "error" in info) and os.sched_getaffinity(0) == before
+
+
+def test_plain_run_measures_the_named_workload_only():
+    a = _args("--gpus", "1", "--steps", "3", "--warmup", "1")
+    assert not a.full and a.dump_outputs == "" and a.steps == 3 and a.warmup == 1
+    a = _args("--full", "--dump-outputs", "outdir")
+    assert a.full and a.dump_outputs == "outdir"
+
+
+def test_dump_outputs_files_and_sample(tmp_path):
+    """--dump-outputs: one float64 file per metric, one float32 file per state tensor in its logical shape (integer counters as
+    float64), tensors above the cap as a fixed sample that keeps the state files within the budget."""
+    import numpy as np
+    import torch
+    import torch.nn as nn
+    torch.manual_seed(0)
+    core = nn.Sequential(nn.Conv2d(3, 64, 3), nn.BatchNorm2d(64), nn.Linear(512, 256))
+    budget = 64 * 1024
+    out = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in out:
+        bench.dump_outputs(d, {"full_loss": 0.25, "tcnloss": 1.5}, core, budget=budget)
+    names = sorted(os.listdir(out[0]))
+    assert names == sorted(os.listdir(out[1]))
+    assert "metric_full_loss.npy" in names and "metric_tcnloss.npy" in names
+    assert np.load(os.path.join(out[0], "metric_tcnloss.npy")).dtype == np.float64
+    assert float(np.load(os.path.join(out[0], "metric_tcnloss.npy"))) == 1.5
+    w = np.load(os.path.join(out[0], "0.weight.npy"))                      # 1728 elements: under the cap, whole and shaped
+    assert w.dtype == np.float32 and w.shape == (64, 3, 3, 3) and np.array_equal(w, core[0].weight.detach().numpy())
+    assert np.load(os.path.join(out[0], "1.num_batches_tracked.npy")).dtype == np.float64
+    assert "2.weight.sample.npy" in names and "2.weight.npy" not in names   # 131072 elements: sampled
+    s = [np.load(os.path.join(d, "2.weight.sample.npy")) for d in out]
+    assert np.array_equal(s[0], s[1]) and set(s[0].tolist()) <= set(core[2].weight.detach().reshape(-1).tolist())
+    state_bytes = sum(os.path.getsize(os.path.join(out[0], n)) - 128 for n in names if not n.startswith("metric_"))
+    assert state_bytes <= budget
+
+
+def test_reset_state_restores_model_and_optimizer():
+    """The timed steps start from the initial state whatever the time-based pre-warm ran: parameters, BatchNorm buffers and
+    counters come back in place (views of the flat buffers stay views), the optimizer to zero moments and no step taken."""
+    import torch
+    from r3m_amd import R3M
+    torch.manual_seed(1)
+    m = R3M("cuda", 1e-4, 1024, size=18, l2weight=1e-5, l1weight=1e-5, langweight=0.0, tcnweight=1.0)
+    initial = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    flat = m.convnet.flat_params()
+    with torch.no_grad():
+        m.convnet.conv1.weight.add_(1.0)
+        m.convnet.bn1.running_mean.add_(2.0)
+        m.convnet.bn1.num_batches_tracked += 5
+    opt = m.encoder_opt
+    opt._steps = [7]
+    opt._m, opt._v = [torch.ones(4)], [torch.ones(4)]
+    bench.reset_state(m, initial)
+    assert all(torch.equal(v, initial[k]) for k, v in m.state_dict().items())
+    assert m.convnet.flat_params() is flat and m.convnet._is_flat()
+    assert opt._steps == [0] and not opt._m[0].any() and not opt._v[0].any()

@@ -476,6 +476,27 @@ def test_bench_spawns_its_own_ranks(hip):
     assert plain["n_gpus"] == 1 and "rccl_ranks" not in plain and plain["config"]["collectives"] == "none (single process)"
 
 
+def test_bench_dump_outputs_do_not_depend_on_the_prewarm(hip, tmp_path):
+    """`--dump-outputs DIR`: what the last timed step computed (metrics, model state) is the same in two runs whose time-based
+    pre-warms ran different numbers of steps — the timed steps start from the initial state and the same random draws — so
+    that two builds can be compared output for output."""
+    runs = []
+    for name, prewarm in (("a", "0"), ("b", "1.5")):
+        d = tmp_path / name
+        out = _run_bench(["--gpus", "1", "--prewarm-seconds", prewarm, "--dump-outputs", str(d)])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        runs.append((out, d))
+    assert runs[0][0]["prewarm_steps"] == 0 and runs[1][0]["prewarm_steps"] > 0
+    names = sorted(p.name for p in runs[0][1].iterdir())
+    assert names == sorted(p.name for p in runs[1][1].iterdir())
+    assert "metric_full_loss.npy" in names and "convnet.conv1.weight.npy" in names
+    assert sum((runs[0][1] / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(runs[0][1] / n), np.load(runs[1][1] / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=n)
+
+
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_ranks_on_one_gpu_over_gloo(hip, world):
     """The N > 1 code of bench.py itself — self-spawned ranks, process group, barriers, all-reduced timing (max over ranks, per-rank

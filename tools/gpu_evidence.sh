@@ -1,5 +1,5 @@
 #!/bin/bash
-# Evidence run (one box, back to back; kernel traces cover 20 steps = 2 warm-up + 18 timed, no pre-warm, no secondary workloads): the driver's default bench line (headline + secondary configs + CPU baseline), every
+# Evidence run (one box, back to back; kernel traces cover 20 steps = 2 warm-up + 18 timed, no pre-warm, no secondary workloads): the --full bench line (headline + secondary configs + CPU baseline), every
 # BASELINE config as its own bench line, the launcher forms (torchrun 1 rank, self-spawn), kernel traces (fp32 / bf16 / configs[4])
 # and PMC passes (fp32 / bf16). Outputs under gpurun_out/; tools/collect_profiles.py <tag> copies the summaries into profiles/<tag>_*.
 # usage: gpu_evidence.sh [tests]     ("tests": also the whole GPU suite + smoke first)
@@ -12,7 +12,7 @@ if [ "$1" = "tests" ]; then
   echo "pytest rc=$?"; grep -E "passed|failed|error" gpurun_out/pytest_all.log | tail -2; grep -E "^(FAILED|ERROR)" gpurun_out/pytest_all.log | head
   python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 gpurun_out/smoke.log
 fi
-B="timeout 1200 python bench.py"
+B="timeout 1200 python bench.py --full"   # --full: the headline line below with its secondary configs and CPU baseline
 $B --launch-csv gpurun_out/launches_fp32.csv > gpurun_out/bench_fp32.json 2> gpurun_out/bench_fp32.err; echo "bench default (fp32 headline + secondary + cpu) rc=$?"
 $B --precision bf16 --steps 20 --warmup 5 --no-cpu-baseline --launch-csv gpurun_out/launches_bf16.csv > gpurun_out/bench_bf16.json 2> gpurun_out/bench_bf16.err; echo "bench bf16 rc=$?"
 $B --precision bf16 --langweight 1 --steps 15 --warmup 5 --no-cpu-baseline > gpurun_out/cfg_c2_r50_lang_bf16.json 2>/dev/null
