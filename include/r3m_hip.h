@@ -110,6 +110,16 @@ int r3m_resnet_set_fused_bn_reduce(r3m_resnet_t h, int on);
 int r3m_resnet_set_bn_pair(r3m_resnet_t h, int on);
 int r3m_resnet_backward(r3m_resnet_t h, const float* dh, const float* params, float* grads, void* arena, int stage_begin,
                         int stage_end, int accumulate, r3m_stream_t stream);
+/* r3m_resnet_backward with two optional outputs (r3m_resnet_backward(...) == r3m_resnet_backward_ex(..., grads, ..., NULL, 0, stream)):
+ *   grads == NULL : no parameter gradient is written and no weight-gradient launch is enqueued (frozen encoder); the BatchNorm
+ *                   backward sums that dz still needs go to plan scratch (reserved in the arena at create time)
+ *   dx != NULL    : (only in the call that runs stage 3) d/d(frames) [frames,3,224,224] fp32 NCHW of the frames given to
+ *                   r3m_resnet_forward, written (dx_accumulate = 0) or added to dx. Not available after r3m_resnet_forward_crop or an
+ *                   inference-mode (training = 2) forward: returns non-zero.
+ * What autograd computes for obs.grad through the reference's R3M.forward (models_r3m.py:84-100): the encoder as a frozen,
+ * differentiable reward or perceptual loss. */
+int r3m_resnet_backward_ex(r3m_resnet_t h, const float* dh, const float* params, float* grads, void* arena, int stage_begin,
+                           int stage_end, int accumulate, float* dx, int dx_accumulate, r3m_stream_t stream);
 
 /* ---------------- single operators (parity-tested one by one) -------------------------------------------------
  * conv2d fwd / dgrad / wgrad: ATen conv2d + autograd under torchvision ResNet.forward (call site models_r3m.py:99). */
@@ -132,6 +142,11 @@ int r3m_stem_conv_fwd(const float* xn, const float* w_ohwi, float* y, float* sta
 size_t r3m_stem_conv_wgrad_workspace_bytes(void);
 int r3m_stem_conv_wgrad(const float* xn, const float* dy, float* dw_ohwi, void* workspace, size_t workspace_bytes, int frames,
                         int accumulate, r3m_stream_t stream);
+/* input gradient of the stem (x/255 -> Normalize -> conv1): dz [frames,112,112,64] NHWC, fp32 (dz_dtype R3M_DT_F32) or bf16
+ * (R3M_DT_BF16), w_ohwi [64,7,7,3] fp32 -> dx_nchw [frames,3,224,224] fp32 = d/d(frames in 0..255); accumulate: 0 writes, 1 adds.
+ * fp32 accumulation; the bf16 rounding of the normalised frames in bf16 plans is taken as identity (as autocast does). */
+int r3m_stem_input_grad(const void* dz, int dz_dtype, const float* w_ohwi, float* dx_nchw, int frames, int accumulate,
+                        r3m_stream_t stream);
 
 /* BatchNorm2d(eps, momentum) train/eval + ReLU + residual add (torchvision BasicBlock/Bottleneck).
  * coef: [4][C] = mean, invstd, scale = gamma*invstd, shift = beta - mean*scale. */
@@ -243,6 +258,11 @@ int r3m_crop_resize(const void* frames, int frames_are_u8, const int* boxes, flo
  * 0..255. The caller derives resized_h/w and the window with torchvision's rounding (r3m_amd/augment.py). */
 int r3m_resize_crop(const void* frames, int frames_are_u8, float* out, long long N, int C, int Hi, int Wi, int resized_h,
                     int resized_w, int top, int left, int Ho, int Wo, r3m_stream_t stream);
+/* Adjoint of r3m_resize_crop for float frames: dout [N,C,Ho,Wo] -> din [N,C,Hi,Wi] (accumulate: 0 writes, 1 adds). A gather (each
+ * input pixel sums the <= 2 x 2 taps per window pixel that sampled it, same source-index arithmetic as the forward): no atomics,
+ * the same bits on every run. uint8 frames carry no gradient. */
+int r3m_resize_crop_backward(const float* dout, float* din, long long N, int C, int Hi, int Wi, int resized_h, int resized_w, int top,
+                             int left, int Ho, int Wo, int accumulate, r3m_stream_t stream);
 
 /* LanguageReward, all 15 evaluations of a step batched (r3m/trainer.py:72-92 calling r3m/models/models_r3m.py:78-81 and
  * r3m/models/models_language.py:43-55). alle [B,5,D]; feats [B,lang_dim] = frozen sentence features (LangEncoder output,

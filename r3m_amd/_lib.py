@@ -49,6 +49,7 @@ SIGNATURES = {
     "r3m_resnet_set_fused_bn_reduce": (c_i, [C.c_void_p, c_i]),
     "r3m_resnet_set_bn_pair": (c_i, [C.c_void_p, c_i]),
     "r3m_resnet_backward": (c_i, [C.c_void_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
+    "r3m_resnet_backward_ex": (c_i, [C.c_void_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f]),
     "r3m_conv2d_stats_rows": (c_i, [c_i] * 7),
     "r3m_conv2d_fwd": (c_i, [c_f, c_f, c_f, c_f] + [c_i] * 8 + [c_f]),
     "r3m_conv2d_dgrad_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
@@ -59,6 +60,7 @@ SIGNATURES = {
     "r3m_stem_conv_fwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_f]),
     "r3m_stem_conv_wgrad_workspace_bytes": (c_sz, []),
     "r3m_stem_conv_wgrad": (c_i, [c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_f]),
+    "r3m_stem_input_grad": (c_i, [c_f, c_i, c_f, c_f, c_i, c_i, c_f]),
     "r3m_bn_workspace_bytes": (c_sz, [c_ll, c_i]),
     "r3m_bn_train_coeffs": (c_i, [c_f, c_i, c_ll, c_f, c_f, c_f, c_f, c_fl, c_fl, c_f, c_f, c_sz, c_i, c_f]),
     "r3m_bn_eval_coeffs": (c_i, [c_f, c_f, c_f, c_f, c_fl, c_f, c_i, c_f]),
@@ -96,6 +98,7 @@ SIGNATURES = {
     "r3m_linear_fwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "r3m_crop_resize": (c_i, [c_f, c_i, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_resize_crop": (c_i, [c_f, c_i, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_resize_crop_backward": (c_i, [c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_langrew_num_params": (c_ll, [c_i, c_i, c_i]),
     "r3m_langrew_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "r3m_langrew_forward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_f]),

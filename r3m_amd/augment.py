@@ -203,9 +203,39 @@ def resize_center_crop_geometry(h, w, size=256, crop=224):
     return nh, nw, int(round((nh - crop) / 2.0)), int(round((nw - crop) / 2.0))
 
 
+def _resize_crop_fwd(frames, nh, nw, top, left, crop):
+    N, C, H, W = frames.shape
+    out = torch.empty((N, C, crop, crop), dtype=torch.float32, device=frames.device)
+    with _lib.on(frames):
+        _lib.check(_lib.lib().r3m_resize_crop(frames.data_ptr(), 1 if frames.dtype == torch.uint8 else 0, out.data_ptr(), N, C, H, W,
+                                              nh, nw, top, left, crop, crop, _lib.stream_ptr(frames.device)), "resize_crop")
+    return out
+
+
+class _ResizeCropFn(torch.autograd.Function):
+    """resize_center_crop of float frames that require grad: the backward is the adjoint gather of csrc/augment.hip
+    (r3m_resize_crop_backward), deterministic."""
+
+    @staticmethod
+    def forward(ctx, frames, nh, nw, top, left, crop):
+        ctx.geom = (tuple(frames.shape), nh, nw, top, left, crop)
+        return _resize_crop_fwd(frames, nh, nw, top, left, crop)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (N, C, H, W), nh, nw, top, left, crop = ctx.geom
+        dout = dout.float().contiguous()
+        din = torch.empty((N, C, H, W), dtype=torch.float32, device=dout.device)
+        with _lib.on(dout):
+            _lib.check(_lib.lib().r3m_resize_crop_backward(dout.data_ptr(), din.data_ptr(), N, C, H, W, nh, nw, top, left, crop, crop, 0,
+                                                           _lib.stream_ptr(dout.device)), "resize_crop_backward")
+        return din, None, None, None, None, None
+
+
 def resize_center_crop(frames, size=256, crop=224):
     """frames [N,C,H,W] uint8 or float (0..255) on the GPU -> [N,C,crop,crop] float32 0..255: Resize(size) + CenterCrop(crop) of
-    R3M.forward (/root/reference/r3m/models/models_r3m.py:85-90) as ONE HIP gather pass (csrc/augment.hip)."""
+    R3M.forward (/root/reference/r3m/models/models_r3m.py:85-90) as ONE HIP gather pass (csrc/augment.hip). Differentiable for float
+    frames that require grad (the adjoint is a HIP gather as well); uint8 frames carry no gradient."""
     if not frames.is_cuda:
         raise RuntimeError("r3m_amd.augment: HIP kernel needs a CUDA/HIP tensor (no CPU fallback)")
     if frames.dtype not in (torch.uint8, torch.float32):
@@ -215,8 +245,6 @@ def resize_center_crop(frames, size=256, crop=224):
     nh, nw, top, left = resize_center_crop_geometry(H, W, size, crop)
     if nh < crop or nw < crop:
         raise ValueError(f"resize_center_crop: {H}x{W} resizes to {nh}x{nw}, smaller than the {crop}x{crop} crop")
-    out = torch.empty((N, C, crop, crop), dtype=torch.float32, device=frames.device)
-    with _lib.on(frames):
-        _lib.check(_lib.lib().r3m_resize_crop(frames.data_ptr(), 1 if frames.dtype == torch.uint8 else 0, out.data_ptr(), N, C, H, W,
-                                              nh, nw, top, left, crop, crop, _lib.stream_ptr(frames.device)), "resize_crop")
-    return out
+    if torch.is_grad_enabled() and frames.requires_grad:
+        return _ResizeCropFn.apply(frames, nh, nw, top, left, crop)
+    return _resize_crop_fwd(frames, nh, nw, top, left, crop)

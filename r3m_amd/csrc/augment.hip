@@ -59,4 +59,69 @@ int launch_resize_crop(const void* in, int in_is_u8, float* out, long long N, in
   return launch_resample(in, in_is_u8, nullptr, out, N, C, Hi, Wi, Ho, Wo, 1, top, left, full_Ho, full_Wo, s);
 }
 
+// Adjoint of launch_resize_crop (float frames only): din[n,c,iy,ix] (= or +=) sum over the window pixels (y, x) whose bilinear taps
+// include (iy, ix) of the tap weight times dout[n,c,y,x]. A GATHER — each input pixel visits the few window rows / columns whose
+// source index lands next to it and re-derives their taps with bilinear_sample's own arithmetic — so there are no atomics and the
+// result is the same bits on every run. The 1/255 and x255 of the forward cancel and are not applied.
+struct ResizeAxis {
+  int lo, hi;          // window indices [lo, hi) that may tap source index i
+};
+__device__ __forceinline__ ResizeAxis resize_axis_range(int i, float scale, int dst_off, int n_out) {
+  // src = (dst + 0.5) scale - 0.5 in [i - 1, i + 1) <=> dst in [(i - 0.5) / scale - 0.5, (i + 1.5) / scale - 0.5): one index of
+  // slack on each side, the exact test is made per candidate
+  const int lo = (int)floorf(((float)i - 0.5f) / scale - 0.5f) - 1 - dst_off;
+  const int hi = (int)ceilf(((float)i + 1.5f) / scale - 0.5f) + 2 - dst_off;
+  return ResizeAxis{lo < 0 ? 0 : lo, hi > n_out ? n_out : hi};
+}
+// weight of source index i in the bilinear taps of window index d (bilinear_sample's arithmetic, contraction off)
+__device__ __forceinline__ float resize_tap_weight(int d, int i, int dst_off, int in_len, int full_len) {
+#pragma clang fp contract(off)
+  const float sd = fmaxf(fmaf((float)(d + dst_off) + 0.5f, (float)in_len / (float)full_len, -0.5f), 0.f);
+  const int i0 = (int)sd;
+  const int i1 = i0 + (i0 < in_len - 1 ? 1 : 0);
+  const float l = sd - (float)i0;
+  float wgt = 0.f;
+  if (i0 == i) wgt += 1.f - l;
+  if (i1 == i) wgt += l;
+  return wgt;
+}
+
+__global__ __launch_bounds__(256) void resize_crop_bwd_kernel(const float* __restrict__ dout, float* __restrict__ din, long long total,
+                                                              int Hi, int Wi, int full_Ho, int full_Wo, int top, int left, int Ho,
+                                                              int Wo, int accumulate) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;   // one thread per input pixel (n, c, iy, ix)
+  if (idx >= total) return;
+  const int ix = (int)(idx % Wi);
+  const long long t = idx / Wi;
+  const int iy = (int)(t % Hi);
+  const long long nc = t / Hi;
+  const ResizeAxis ry = resize_axis_range(iy, (float)Hi / (float)full_Ho, top, Ho);
+  const ResizeAxis rx = resize_axis_range(ix, (float)Wi / (float)full_Wo, left, Wo);
+  const float* g = dout + nc * Ho * Wo;
+  float sum = 0.f;
+  for (int y = ry.lo; y < ry.hi; ++y) {
+    const float wy = resize_tap_weight(y, iy, top, Hi, full_Ho);
+    if (wy == 0.f) continue;
+    float row = 0.f;
+    for (int x = rx.lo; x < rx.hi; ++x) {
+      const float wx = resize_tap_weight(x, ix, left, Wi, full_Wo);
+      if (wx != 0.f) row = fmaf(wx, g[(long long)y * Wo + x], row);
+    }
+    sum = fmaf(wy, row, sum);
+  }
+  din[idx] = accumulate ? din[idx] + sum : sum;
+}
+
+int launch_resize_crop_backward(const float* dout, float* din, long long N, int C, int Hi, int Wi, int full_Ho, int full_Wo, int top,
+                                int left, int Ho, int Wo, int accumulate, hipStream_t s) {
+  R3M_REQUIRE(full_Ho >= 1 && full_Wo >= 1 && top >= 0 && left >= 0 && top + Ho <= full_Ho && left + Wo <= full_Wo,
+              "resize_crop_backward: window %dx%d at (%d,%d) outside the %dx%d resized frame", Ho, Wo, top, left, full_Ho, full_Wo);
+  R3M_REQUIRE(Hi >= 1 && Wi >= 1 && N >= 0 && C >= 1, "resize_crop_backward: frames %lldx%dx%dx%d", N, C, Hi, Wi);
+  const long long total = N * C * Hi * Wi;
+  if (total == 0) return 0;
+  hipLaunchKernelGGL(resize_crop_bwd_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, dout, din, total, Hi, Wi, full_Ho, full_Wo,
+                     top, left, Ho, Wo, accumulate);
+  return check_launch("resize_crop_backward");
+}
+
 }  // namespace r3m

@@ -7,8 +7,12 @@ mkdir -p "$OUT" "$HERE/../../build/obj"
 OBJ="$HERE/../../build/obj"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $*"
-pids=()
-SRCS="conv conv_pw wgrad_win conv_bf16 conv_row16 conv_pw16 stem_bf16 bn loss adam lang augment engine capi"
+# at most MAX_JOBS (default: the CPU count, at most 16) compiles at once; a failed compile is named on stdout and stderr
+JOBS="${MAX_JOBS:-$(nproc 2>/dev/null || echo 8)}"
+[ "$JOBS" -ge 1 ] 2>/dev/null || JOBS=8
+[ "$JOBS" -gt 16 ] && JOBS=16
+launched=""
+SRCS="conv conv_pw wgrad_win conv_bf16 conv_row16 conv_pw16 stem_bf16 stem_dgrad bn loss adam lang augment engine capi"
 for f in $SRCS; do
   [ -f "$HERE/$f.hip" ] || continue
   stale=0
@@ -20,11 +24,24 @@ for f in $SRCS; do
     EXTRA=""
     # conv_pw16: the tile tickets are requested one tile before they are used; the wave-level atomic optimizer would wait for each at once
     [ "$f" = conv_pw16 ] && EXTRA="-mllvm -amdgpu-atomic-optimizer-strategy=None"
-    $HIPCC $FLAGS $EXTRA -c "$HERE/$f.hip" -o "$OBJ/$f.o" &
-    pids+=($!)
+    while [ "$(jobs -rp | wc -l)" -ge "$JOBS" ]; do wait -n || true; done
+    rm -f "$OBJ/$f.rc" "$OBJ/$f.o"
+    launched="$launched $f"
+    ( rc=0; $HIPCC $FLAGS $EXTRA -c "$HERE/$f.hip" -o "$OBJ/$f.o" || rc=$?; echo "$rc" > "$OBJ/$f.rc" ) &
   fi
 done
-for p in "${pids[@]}"; do wait "$p"; done
+wait
+failed=""
+for f in $launched; do
+  rc="$(cat "$OBJ/$f.rc" 2>/dev/null || echo killed)"
+  rm -f "$OBJ/$f.rc"
+  if [ "$rc" != 0 ]; then failed="$failed $f.hip($rc)"; rm -f "$OBJ/$f.o"; fi
+done
+if [ -n "$failed" ]; then
+  echo "build.sh: compile failed:$failed"
+  echo "build.sh: compile failed:$failed" >&2
+  exit 1
+fi
 objs=()
 for f in $SRCS; do [ -f "$OBJ/$f.o" ] && objs+=("$OBJ/$f.o"); done
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libr3m_hip.so" "${objs[@]}"

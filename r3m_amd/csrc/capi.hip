@@ -115,7 +115,7 @@ int plan_forward(Plan& P, const float* x_nchw, const float* params, float* bufs,
 int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena,
                      float* h_out, int training, hipStream_t s);
 int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
-                  int accumulate, int* gd_io, hipStream_t s);
+                  int accumulate, int* gd_io, hipStream_t s, float* dx, int dx_accumulate);
 int conv_forward_launch(const float* X, const float* W, float* Y, float* stats, const float* bias, int N, int Hi, int Wi, int Ci,
                         int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
 int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* add0, const float* add1, const unsigned* addbits,
@@ -151,6 +151,8 @@ int launch_crop_resize(const void* in, int in_is_u8, const int* boxes, float* ou
                        int Wo, int frames_per_box, hipStream_t s);
 int launch_resize_crop(const void* in, int in_is_u8, float* out, long long N, int C, int Hi, int Wi, int full_Ho, int full_Wo,
                        int top, int left, int Ho, int Wo, hipStream_t s);
+int launch_resize_crop_backward(const float* dout, float* din, long long N, int C, int Hi, int Wi, int full_Ho, int full_Wo, int top,
+                                int left, int Ho, int Wo, int accumulate, hipStream_t s);
 // lang.hip
 long long langrew_num_params(int D, int H, int LD);
 size_t langrew_ws_floats(int B, int D, int H, int LD);
@@ -291,7 +293,14 @@ int r3m_resnet_backward(r3m_resnet_t h, const float* dh, const float* params, fl
   R3M_REQUIRE(h && dh && params && grads && arena, "resnet_backward: null argument");
   R3M_REQUIRE(0 <= stage_begin && stage_begin <= stage_end && stage_end <= 4, "resnet_backward: stages [%d,%d)", stage_begin, stage_end);
   return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, plan_gd(PLAN(h)),
-                       S(stream));
+                       S(stream), nullptr, 0);
+}
+int r3m_resnet_backward_ex(r3m_resnet_t h, const float* dh, const float* params, float* grads, void* arena, int stage_begin,
+                           int stage_end, int accumulate, float* dx, int dx_accumulate, r3m_stream_t stream) {
+  R3M_REQUIRE(h && dh && params && arena, "resnet_backward_ex: null argument");
+  R3M_REQUIRE(0 <= stage_begin && stage_begin <= stage_end && stage_end <= 4, "resnet_backward_ex: stages [%d,%d)", stage_begin, stage_end);
+  return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, plan_gd(PLAN(h)),
+                       S(stream), dx, dx_accumulate);
 }
 
 int r3m_conv2d_stats_rows(int N, int Hi, int Wi, int Co, int k, int stride, int pad) {
@@ -397,6 +406,11 @@ int r3m_stem_conv_wgrad_dt(const float* xn, const void* dy, float* dw_ohwi, void
 int r3m_stem_conv_wgrad(const float* xn, const float* dy, float* dw_ohwi, void* ws, size_t ws_bytes, int frames, int accumulate,
                         r3m_stream_t stream) {
   return r3m_stem_conv_wgrad_dt(xn, dy, dw_ohwi, ws, ws_bytes, frames, accumulate, DT_F32, stream);
+}
+int r3m_stem_input_grad(const void* dz, int dz_dtype, const float* w_ohwi, float* dx_nchw, int frames, int accumulate, r3m_stream_t stream) {
+  R3M_REQUIRE(dz && w_ohwi && dx_nchw, "stem_input_grad: null argument");
+  if (check_dt(dz_dtype, "stem_input_grad")) return 1;
+  return launch_stem_input_grad(dz, dz_dtype, w_ohwi, dx_nchw, frames, accumulate, S(stream));
 }
 
 // stem on the bf16 MFMA (what bf16 plans run): padded bf16 image of the normalised frames, forward, weight gradient
@@ -580,6 +594,11 @@ int r3m_resize_crop(const void* frames, int frames_are_u8, float* out, long long
                     int top, int left, int Ho, int Wo, r3m_stream_t stream) {
   R3M_REQUIRE(frames && out, "resize_crop: null argument");
   return launch_resize_crop(frames, frames_are_u8, out, N, C, Hi, Wi, resized_h, resized_w, top, left, Ho, Wo, S(stream));
+}
+int r3m_resize_crop_backward(const float* dout, float* din, long long N, int C, int Hi, int Wi, int resized_h, int resized_w, int top,
+                             int left, int Ho, int Wo, int accumulate, r3m_stream_t stream) {
+  R3M_REQUIRE(dout && din, "resize_crop_backward: null argument");
+  return launch_resize_crop_backward(dout, din, N, C, Hi, Wi, resized_h, resized_w, top, left, Ho, Wo, accumulate, S(stream));
 }
 
 size_t r3m_loss_workspace_bytes(int B) { return loss_workspace_floats(B) * 4; }

@@ -195,6 +195,8 @@ int launch_stem_prep16(const float* x_nchw, void* xn16, int F, hipStream_t s);
 int launch_stem_fwd16(const void* xn16, const float* w147, void* y, float* stats, int F, hipStream_t s);
 size_t stem_wgrad16_ws_floats();
 int launch_stem_wgrad16(const void* xn16, const void* dY, float* dw147, float* ws, int F, int accumulate, hipStream_t s);
+// ---- launcher (stem_dgrad.hip): input gradient of the stem, dz [F,112,112,64] fp32 / bf16 -> dx [F,3,224,224] fp32 NCHW (= or +=) ----
+int launch_stem_input_grad(const void* dz, int dt, const float* w147, float* dx, int F, int accumulate, hipStream_t s);
 
 // ---- launchers (bn.hip) ----
 size_t bn_acc_bytes(int C);   // fp64 slice accumulator: [slices <= max(64, min(256, 131072 / C))][2][C]

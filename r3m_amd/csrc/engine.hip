@@ -74,6 +74,8 @@ struct Plan {
   long long arena_floats = 0;
   long long gmax = 0;
   int last_training = 1;
+  int last_crop = 0;      // the last forward read raw clips through crop boxes (r3m_resnet_forward_crop): no frames to differentiate
+  long long gsc_off = 0;  // arena: [2][2048] BatchNorm parameter-gradient sums of a backward without parameter gradients (grads == NULL)
   int gd = 0;             // which G buffer holds the running output-gradient between backward stages
   // side stream: wgrad(L) runs concurrently with dgrad(L) (both only need dY_L), filling each other's tile-quantisation tails
   hipStream_t side = nullptr;
@@ -244,6 +246,7 @@ Plan* plan_create(int size, int F, int dtype) {
   }
   if (dtype == DT_BF16) P.w16_off = take((P.n_params + 1) / 2);
   P.wgp_off = take(wgp_max);
+  P.gsc_off = take(2LL * 2048);
   P.ctr_off = take(5LL * (long long)P.convs.size() * 8);
   P.gmax = gmax;
   for (int g = 0; g < 5; ++g) P.G_off[g] = take(gmax);
@@ -268,6 +271,11 @@ struct Ctx {
   int training;
   int accumulate;
   int dt;
+  // where BatchNorm backward puts d gamma / d beta of layer L: the flat gradient buffer, or plan scratch when no parameter gradient
+  // is wanted (the sums themselves are still formed: train-mode dz needs c1 / c2 from the same pass)
+  float* dgamma(const ConvSpec& L) const { return grads ? grads + L.gamma_off : arena + P.gsc_off; }
+  float* dbeta(const ConvSpec& L) const { return grads ? grads + L.beta_off : arena + P.gsc_off + 2048; }
+  int bn_accumulate() const { return grads ? accumulate : 0; }
 };
 
 static void fill_taps_fwd(GatherGemmParams& g, int k, int pad) {
@@ -487,6 +495,7 @@ int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, cons
   if (infer) training = 0;
   Ctx c{P, params, nullptr, bufs, arena, s, training, 0, P.dtype};
   P.last_training = training;
+  P.last_crop = crop ? 1 : 0;
   P.next_stage = infer ? -3 : 0;   // a new forward invalidates whatever an unfinished backward left behind (-3: nothing to differentiate)
   P.dout_fused_rows = 0;
   const int F = P.F;
@@ -651,8 +660,8 @@ static int bn_backward_sums(Ctx& c, const ConvSpec& L, const float* dZ, const un
     prow = bn_bwd_partial_rows(rows, L.Co, c.dt);
   }
   TRY(launch_bn_stats_reduce(partial, prow, L.Co, acc, c.s));
-  return launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.grads + L.gamma_off, c.grads + L.beta_off, coef(c, L, 4),
-                                     coef(c, L, 5), c.accumulate, L.Co, c.s, fused_rows ? coef(c, L, 1) : nullptr);
+  return launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.dgamma(L), c.dbeta(L), coef(c, L, 4),
+                                     coef(c, L, 5), c.bn_accumulate(), L.Co, c.s, fused_rows ? coef(c, L, 1) : nullptr);
 }
 static int bn_backward(Ctx& c, const ConvSpec& L, const float* dZ, const unsigned* Zbits, float* dY, int fused_rows = 0) {
   TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
@@ -680,8 +689,8 @@ static int bn_backward_pair(Ctx& c, const ConvSpec& L, const ConvSpec& Ld, const
     for (int k = 0; k < 2; ++k) {
       const ConvSpec& Q = *two[k];
       TRY(launch_bn_stats_reduce(partial + k * set, prow, Q.Co, acc, c.s));
-      TRY(launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.grads + Q.gamma_off, c.grads + Q.beta_off, coef(c, Q, 4),
-                                      coef(c, Q, 5), c.accumulate, Q.Co, c.s, nullptr));
+      TRY(launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.dgamma(Q), c.dbeta(Q), coef(c, Q, 4),
+                                      coef(c, Q, 5), c.bn_accumulate(), Q.Co, c.s, nullptr));
     }
   } else {
     TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
@@ -759,12 +768,19 @@ static int side_init(Plan& P) {
   return 0;
 }
 
+// grads == nullptr: no parameter gradient (frozen encoder) — no weight-gradient launch is enqueued, the side stream stays idle and
+// the BatchNorm parameter sums go to plan scratch. dx != nullptr (only with stage 3 in range): d/d(frames) [F,3,224,224] fp32 NCHW
+// of the frames of the last forward (stem_dgrad.hip), written (dx_accumulate = 0) or added.
 int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
-                  int accumulate, int* gd_io, hipStream_t s) {
+                  int accumulate, int* gd_io, hipStream_t s, float* dx, int dx_accumulate) {
   Ctx c{P, params, grads, nullptr, arena, s, P.last_training, accumulate, P.dtype};
   const int dt = P.dtype;
   R3M_REQUIRE(stage_begin >= 0 && stage_end <= 4 && stage_begin < stage_end, "resnet_backward: stages [%d, %d) outside [0, 4)", stage_begin, stage_end);
   R3M_REQUIRE(P.next_stage != -3, "resnet_backward: the last forward on this plan ran in inference mode (training = 2): nothing was kept for a backward");
+  R3M_REQUIRE(!dx || stage_end == 4, "resnet_backward: dx (the input gradient) is formed by the stem, in stage 3; stages [%d, %d) do not "
+              "include it", stage_begin, stage_end);
+  R3M_REQUIRE(!dx || !P.last_crop, "resnet_backward: no input gradient after r3m_resnet_forward_crop (the frames were resampled from raw "
+              "clips inside the stem pre-pass; pass dx = NULL)");
   R3M_REQUIRE(P.next_stage != -1, "resnet_backward: no forward has run on this plan");
   // stage 0 may always (re)start a backward over the saved activations (retain_graph); any other stage must continue the
   // sequence the previous call left off at — its inputs (running output gradient, pending EPI_BNRED partials) live in the plan
@@ -800,7 +816,7 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
     }
     TRY(launch_transpose_w_all(params, arena + P.wt_off, P.d_wt_tab, P.d_wt_tile0, (int)P.wt_tab.size(), P.wt_tile0.back(), P.dtype, s));
   }
-  const bool side_on = P.use_side && P.side;
+  const bool side_on = P.use_side && P.side && grads;
   Ctx cs = c;                       // context whose launches go to the side stream
   cs.s = side_on ? P.side : s;
   const int F = P.F;
@@ -820,6 +836,7 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
   };
   // call right AFTER dgrad(L) was enqueued on the main stream: wgrad(L) starts on the side stream once that dgrad is done (mode 1)
   auto wgrad_async = [&](const ConvSpec& L, const float* X, const float* dY, int ai) -> int {
+    if (!grads) return 0;                  // frozen encoder: no weight gradient
     if (!side_on) return wgrad(c, L, X, dY);
     if (!side_co && (hipEventRecord(P.ev_dy, s) != hipSuccess || hipStreamWaitEvent(P.side, P.ev_dy, 0) != hipSuccess)) {
       set_last_error("side stream: event ordering failed");
@@ -936,7 +953,7 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
       const int t = role[0]; role[0] = role[4]; role[4] = t;
     }
     if (st == 3) {
-      // stem: maxpool + BN/ReLU backward (fused) -> conv1 weight gradient (no input gradient)
+      // stem: maxpool + BN/ReLU backward (fused) -> conv1 weight gradient [-> input gradient]
       const ConvSpec& L0 = P.convs[0];
       float* Gc = Gp(4);
       {   // MaxPool backward gathered inside both BatchNorm-backward passes (no dZ0 tensor)
@@ -948,14 +965,18 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
                                       F, 112, 112, 64, dt, s));
         const int prow = bn_bwd_pool_partial_rows(F, 112, 112, 64);
         TRY(launch_bn_stats_reduce(partial, prow, 64, acc, s));
-        TRY(launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, grads + L0.gamma_off, grads + L0.beta_off, coef(c, L0, 4),
-                                        coef(c, L0, 5), accumulate, 64, s));
+        TRY(launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.dgamma(L0), c.dbeta(L0), coef(c, L0, 4),
+                                        coef(c, L0, 5), c.bn_accumulate(), 64, s));
         TRY(launch_bn_bwd_apply_pool(Gp(0), am, arena + L0.Y_off, coef(c, L0, 2), coef(c, L0, 3), coef(c, L0, 0), coef(c, L0, 1),
                                      coef(c, L0, 4), coef(c, L0, 5), Gc, F, 112, 112, 64, dt, s));
       }
       TRY(join_side());   // the stem wgrad shares the split-K scratch with the side stream's wgrads
-      if (dt == DT_BF16) TRY(launch_stem_wgrad16(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, s));
-      else TRY(launch_stem_wgrad(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, dt, s));
+      if (grads) {
+        if (dt == DT_BF16) TRY(launch_stem_wgrad16(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, s));
+        else TRY(launch_stem_wgrad(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, dt, s));
+      }
+      // Gc = conv1's output gradient; the bf16 rounding of the normalised frames is taken as identity (as autocast does)
+      if (dx) TRY(launch_stem_input_grad(Gc, dt, params + L0.w_off, dx, F, dx_accumulate, s));
     }
     TRY(join_side());     // a finished stage's gradients are complete on the main stream (all-reduce hook, Adam)
   }

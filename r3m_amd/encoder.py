@@ -47,7 +47,8 @@ def _tensor_table(size):
 
 
 class _EncoderFn(torch.autograd.Function):
-    """h = encoder(x). Backward writes parameter gradients straight into the module's flat gradient buffer."""
+    """h = encoder(x). Backward writes parameter gradients straight into the module's flat gradient buffer (none when no parameter
+    requires grad) and returns d/dx when x requires grad."""
 
     @staticmethod
     def forward(ctx, x, anchor, module, training, crop=None):
@@ -70,12 +71,16 @@ class _EncoderFn(torch.autograd.Function):
         # exception before backward — stops counting when its node is collected; round 5 kept a manual counter that such a forward
         # left raised for good, silently costing every later step its comm / compute overlap: ADVICE r5).
         others = sum(1 for sl in m._ring if sl.live and sl.waiting() is not ctx)
-        m._run_backward(dh.contiguous(), ctx.generation, ctx.slot, fire_hooks=others == 0)
+        params, input_grad = any(p.requires_grad for p in m.parameters()), ctx.needs_input_grad[0]
+        if params and not input_grad:          # the pre-training backward
+            dx = m._run_backward(dh.contiguous(), ctx.generation, ctx.slot, fire_hooks=others == 0)
+        else:
+            dx = m._run_backward(dh.contiguous(), ctx.generation, ctx.slot, fire_hooks=others == 0, params=params, input_grad=input_grad)
         if 0 <= ctx.slot < len(m._ring):
             w = m._ring[ctx.slot].waiting
             if w is not None and w() is ctx:
                 m._ring[ctx.slot].waiting = None
-        return None, None, None, None, None
+        return dx, None, None, None, None
 
 
 PRECISIONS = {"fp32": 0, "bf16": 1}   # R3M_DT_F32 / R3M_DT_BF16 (include/r3m_hip.h)
@@ -400,7 +405,9 @@ class HipResNet(nn.Module):
         self._last_forward = (si, slot.generation)
         return out
 
-    def _run_backward(self, dh, generation, si=0, fire_hooks=True):
+    def _run_backward(self, dh, generation, si=0, fire_hooks=True, params=True, input_grad=False):
+        """params: write parameter gradients into the flat gradient buffer (False: frozen encoder — no weight-gradient launch, the
+        buffer is neither created nor touched, no stage hook fires). input_grad: return d/d(frames) [F,3,224,224] fp32."""
         slot = self._slot(si)
         if generation != slot.generation or slot.arena is None:
             raise RuntimeError(f"r3m_amd: the encoder ran {len(self._ring)} other forward(s) before this backward; its saved "
@@ -408,16 +415,24 @@ class HipResNet(nn.Module):
                                f"max_live_forwards=k (R3M(..., max_live_forwards=k)) to keep k forwards alive at once")
         L = _lib.lib()
         h = self._plan(slot.F, si)
-        g = self.flat_grads()
+        g = self.flat_grads() if params else None
         accumulate = 0 if self._grad_fresh else 1
+        dx = torch.empty((slot.F, 3, 224, 224), dtype=torch.float32, device=dh.device) if input_grad else None
         with _lib.on(dh):
             for stage in range(4):
-                _lib.check(L.r3m_resnet_backward(h, dh.data_ptr(), self._flat_p.data_ptr(), g.data_ptr(), slot.arena.data_ptr(), stage,
-                                                 stage + 1, accumulate, _lib.stream_ptr(dh.device)), "resnet_backward")
-                if self._stage_hook is not None and fire_hooks:
+                if g is not None and dx is None:     # the pre-training path: unchanged launch sequence
+                    _lib.check(L.r3m_resnet_backward(h, dh.data_ptr(), self._flat_p.data_ptr(), g.data_ptr(), slot.arena.data_ptr(),
+                                                     stage, stage + 1, accumulate, _lib.stream_ptr(dh.device)), "resnet_backward")
+                else:
+                    _lib.check(L.r3m_resnet_backward_ex(h, dh.data_ptr(), self._flat_p.data_ptr(), _lib.ptr(g), slot.arena.data_ptr(),
+                                                        stage, stage + 1, accumulate, _lib.ptr(dx) if stage == 3 else None, 0,
+                                                        _lib.stream_ptr(dh.device)), "resnet_backward_ex")
+                if g is not None and self._stage_hook is not None and fire_hooks:
                     off, cnt = self.stage_range(stage)
                     self._stage_hook(stage, off, cnt)
-        self._grad_fresh = False
+        if g is not None:
+            self._grad_fresh = False
+        return dx
 
     def forward(self, x):
         """x: [F,3,224,224] float32 CUDA tensor with values in 0..255 (the /255 and Normalize of R3M.forward are fused into
@@ -438,7 +453,10 @@ class HipResNet(nn.Module):
             x = x.contiguous()
             if x.dtype != torch.float32:
                 x = x.float()
-        needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        # a graph is recorded when anything upstream wants a gradient: the parameters (training) or the frames (obs.grad: the
+        # encoder as a differentiable reward / perceptual loss, parameters frozen or not)
+        needs_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                                  or (crop is None and x.requires_grad))
         if needs_grad:
             anchor = next(self.parameters())
             return _EncoderFn.apply(None if crop is not None else x, anchor, self, self.training, crop)
