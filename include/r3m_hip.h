@@ -53,6 +53,11 @@ int r3m_debug_set_fused_inference(int on);
    kernel-row 3x3 kernel (csrc/conv_row16.hip). Returns the number of launches (a stride-2 dgrad has up to four), -1 on error. */
 int r3m_debug_conv_route(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int dgrad, int flags, int mask_bits, int dtype,
                          int* routes, int cap);
+/* Diagnostic, runs without a GPU: 1 when the inference forward of this convolution with epilogue `flags` (128 eval BatchNorm [| 2 add
+   onto the residual in the output] [| 16 ReLU]) runs on a kernel built for those flags, so the engine stores the activated block
+   output from the convolution itself; 0 when the engine runs that block's unfused sequence instead. r3m_debug_conv_route with the same
+   flags (dgrad = 0) reports the route the fused launch takes. */
+int r3m_debug_conv_fuses_affine(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int flags, int dtype);
 void r3m_profile_enable(int on);
 /* which kernel classes are bracketed while profiling is on: bit k = class k (0 conv fwd/dgrad 128-wide, 1 64-wide, 2 / 3 the weight
    gradients); default all. Each bracket costs the stream two event records. Returns the old mask. */
@@ -78,7 +83,8 @@ int r3m_resnet_tensor_info(r3m_resnet_t h, int i, char* name, int name_cap, int*
                            int* shape4);
 /* backward stage s (0: avgpool+layer4, 1: layer3, 2: layer2, 3: layer1+stem) finishes params [offset, offset+count) */
 int r3m_resnet_stage_range(r3m_resnet_t h, int stage, long long* offset, long long* count);
-/* x: [frames,3,224,224] fp32 NCHW in 0..255 (models_r3m.py:96: "Input must be [0, 255]"); h_out: [frames, out_dim].
+/* x: [frames,3,224,224] fp32 NCHW in 0..255 ([frames,3,H,W] for r3m_resnet_create_hw plans; models_r3m.py:96: "Input must be
+ * [0, 255]"); h_out: [frames, out_dim].
  * training=1: batch statistics + running-stat update (momentum 0.1, eps 1e-5); 0: running statistics, everything a backward needs
  * kept (fine-tuning with frozen statistics); 2: INFERENCE — running statistics and nothing kept: BatchNorm, the residual join and the
  * ReLU are applied where each convolution stores its result (no raw conv outputs, no stand-alone BatchNorm passes, no mask bits), an
@@ -186,6 +192,36 @@ int r3m_avgpool_bwd(const float* dh, float* dx, int N, int HW, int C, r3m_stream
 enum { R3M_DT_F32 = 0, R3M_DT_BF16 = 1 };
 r3m_resnet_t r3m_resnet_create_dt(int size /*18|34|50*/, int frames, int dtype);
 int r3m_resnet_dtype(r3m_resnet_t h);
+/* Native resolution: a plan for frames [frames,3,height,width], any height and width in 32..512 (torchvision's ResNet takes any size:
+ * every layer's output is floor((n + 2 pad - k) / stride) + 1 per dimension, the global average pool ends in [frames, out_dim]).
+ * r3m_resnet_create_hw(size, frames, dtype, 224, 224) is r3m_resnet_create_dt(size, frames, dtype): same plan, same arena, same kernels.
+ * Other sizes run the general stem kernels (csrc/stem_gen.hip) and the same layer kernels as 224. r3m_resnet_forward / _backward(_ex)
+ * then take x and dx as [frames,3,height,width]; r3m_resnet_forward_crop (224 crops) returns an error on a plan that is not 224 x 224.
+ * Returns NULL with r3m_last_error() set for sizes outside 32..512 and when some tensor of the plan would hold 2^31 elements or more
+ * (the kernels index with 32-bit integers). Needs no GPU. */
+r3m_resnet_t r3m_resnet_create_hw(int size /*18|34|50*/, int frames, int dtype, int height, int width);
+int r3m_resnet_input_hw(r3m_resnet_t h, int* height, int* width);
+/* Read-only geometry of convolution i (0 = conv1, then torchvision's module order of each block: conv1, conv2[, conv3][, downsample.0]):
+ * channels in / out, kernel size, stride, pad, input and output height / width. r3m_resnet_num_convs gives the count. Needs no GPU. */
+int r3m_resnet_num_convs(r3m_resnet_t h);
+int r3m_resnet_conv_info(r3m_resnet_t h, int i, int* Ci, int* Co, int* k, int* stride, int* pad, int* Hi, int* Wi, int* Ho, int* Wo);
+/* Diagnostic (same-process A/B, tests): 1 = forwards of 224 x 224 plans run the general stem kernels too (the frames must come through
+ * r3m_resnet_forward; the backward follows what the last forward ran); 0 (default) = the 224-specialised stem. Returns the old value. */
+int r3m_debug_set_generic_stem(int on);
+/* The general stem kernels one by one (tests, tools/resolution_bench.py). xn: the normalised image [F][H][W*3], fp32 (dtype 0) or bf16
+ * (dtype 1), r3m_stem_gen_image_bytes() long; w147: fp32 conv1 weights OHWI [64][7][7][3]; y / dy: [F,Ho,Wo,64] of the dtype;
+ * stats (optional): BatchNorm partial rows [ceil(F Ho Wo / 256)][2][64] (sum, sum of squares); ws: r3m_stem_gen_wgrad_ws_bytes();
+ * dx: fp32 NCHW [F,3,H,W]. */
+size_t r3m_stem_gen_image_bytes(int F, int H, int W, int dtype);
+size_t r3m_stem_gen_wgrad_ws_bytes(void);
+int r3m_stem_gen_prep(const float* x_nchw, void* xn, int F, int H, int W, int dtype, r3m_stream_t stream);
+int r3m_stem_gen_fwd(const void* xn, const float* w147, void* y, float* stats, int F, int H, int W, int dtype, r3m_stream_t stream);
+int r3m_stem_gen_wgrad(const void* xn, const void* dy, float* dw147, void* ws, int F, int H, int W, int accumulate, int dtype,
+                       r3m_stream_t stream);
+int r3m_stem_gen_input_grad(const void* dy, const float* w147, float* dx, int F, int H, int W, int accumulate, int dtype,
+                            r3m_stream_t stream);
+/* LDS bytes per block of the three general stem kernels at F x H x W (at most 160 KiB over the supported range). Needs no GPU. */
+int r3m_stem_gen_lds_bytes(int F, int H, int W, int* fwd, int* wgrad, int* input_grad);
 int r3m_convert_bf16(const float* src, void* dst_bf16, long long n /* multiple of 4 */, r3m_stream_t stream);
 int r3m_conv2d_fwd_dt(const void* x, const void* w_ohwi, void* y, float* stats, int N, int Hi, int Wi, int Ci, int Co, int k,
                       int stride, int pad, int dtype, r3m_stream_t stream);

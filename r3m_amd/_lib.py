@@ -29,6 +29,7 @@ SIGNATURES = {
     "r3m_debug_set_conv3x3_bf16": (c_i, [c_i]),
     "r3m_debug_set_fused_inference": (c_i, [c_i]),
     "r3m_debug_conv_route": (c_i, [c_i] * 12 + [C.POINTER(c_i), c_i]),
+    "r3m_debug_conv_fuses_affine": (c_i, [c_i] * 10),
     "r3m_profile_enable": (None, [c_i]),
     "r3m_profile_classes": (C.c_uint, [C.c_uint]),
     "r3m_profile_collect": (c_i, [C.POINTER(c_d), C.POINTER(c_ll), C.POINTER(c_d)]),
@@ -72,6 +73,18 @@ SIGNATURES = {
     "r3m_avgpool_bwd": (c_i, [c_f, c_f, c_i, c_i, c_i, c_f]),
     "r3m_resnet_create_dt": (C.c_void_p, [c_i, c_i, c_i]),
     "r3m_resnet_dtype": (c_i, [C.c_void_p]),
+    "r3m_resnet_create_hw": (C.c_void_p, [c_i, c_i, c_i, c_i, c_i]),
+    "r3m_resnet_input_hw": (c_i, [C.c_void_p, C.POINTER(c_i), C.POINTER(c_i)]),
+    "r3m_resnet_num_convs": (c_i, [C.c_void_p]),
+    "r3m_resnet_conv_info": (c_i, [C.c_void_p, c_i] + [C.POINTER(c_i)] * 9),
+    "r3m_debug_set_generic_stem": (c_i, [c_i]),
+    "r3m_stem_gen_image_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "r3m_stem_gen_wgrad_ws_bytes": (c_sz, []),
+    "r3m_stem_gen_prep": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_stem_gen_fwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_stem_gen_wgrad": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_stem_gen_input_grad": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_stem_gen_lds_bytes": (c_i, [c_i, c_i, c_i, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i)]),
     "r3m_convert_bf16": (c_i, [c_f, c_f, c_ll, c_f]),
     "r3m_conv2d_fwd_dt": (c_i, [c_f, c_f, c_f, c_f] + [c_i] * 9 + [c_f]),
     "r3m_conv2d_dgrad_dt": (c_i, [c_f, c_f, c_f, c_f, c_sz] + [c_i] * 9 + [c_f]),

@@ -108,7 +108,11 @@ void prof_end(hipStream_t s) {
 int debug_occupancy(int* out4);
 // engine.hip
 struct Plan;
-Plan* plan_create(int size, int F, int dtype);
+Plan* plan_create(int size, int F, int dtype, int H, int W);
+int engine_set_generic_stem(int on);
+int plan_input_hw(Plan* P, int* H, int* W);
+int plan_num_convs(Plan* P);
+int plan_conv_info(Plan* P, int i, int* geo10);
 int plan_dtype(Plan*);
 int plan_forward(Plan& P, const float* x_nchw, const float* params, float* bufs, float* arena, float* h_out, int training,
                  hipStream_t s);
@@ -118,6 +122,9 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
                   int accumulate, int* gd_io, hipStream_t s, float* dx, int dx_accumulate);
 int conv_forward_launch(const float* X, const float* W, float* Y, float* stats, const float* bias, int N, int Hi, int Wi, int Ci,
                         int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
+int conv_forward_launch_affine(const float* X, const float* W, float* out, const float* scale, const float* shift, int N, int Hi, int Wi,
+                               int Ci, int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
+bool conv_forward_affine_fusable(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt);
 int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* add0, const float* add1, const unsigned* addbits,
                       int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
 int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, int N, int Hi, int Wi, int Ci, int Co, int k,
@@ -195,6 +202,9 @@ int r3m_debug_set_dynamic_tiles(int on) { return r3m::gg_set_dynamic_tiles(on); 
 int r3m_debug_set_pw16(int mode) { return r3m::pw16_set_mode(mode); }
 int r3m_debug_set_conv3x3_bf16(int mode) { return r3m::row16_set_mode(mode); }
 int r3m_debug_set_fused_inference(int on) { return r3m::engine_set_fused_inference(on); }
+int r3m_debug_conv_fuses_affine(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int flags, int dtype) {
+  return r3m::conv_forward_affine_fusable(N, H, W, Ci, Co, k, stride, pad, flags, dtype) ? 1 : 0;
+}
 int r3m_debug_conv_route(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int dgrad, int flags, int mask_bits, int dtype,
                          int* routes, int cap) {
   R3M_REQUIRE(routes && cap >= 1, "debug_conv_route: routes buffer");
@@ -202,7 +212,10 @@ int r3m_debug_conv_route(int N, int H, int W, int Ci, int Co, int k, int stride,
   const unsigned* some_bits = reinterpret_cast<const unsigned*>(static_cast<uintptr_t>(64));
   r3m::gg_route_record_begin(routes, cap);
   int rc;
-  if (!dgrad) {
+  if (!dgrad && (flags & EPI_AFFINE)) {        // inference forward: the coefficient pointers the epilogue reads must be set
+    const float* coef = reinterpret_cast<const float*>(some_bits);
+    rc = r3m::conv_forward_launch_affine(nullptr, nullptr, nullptr, coef, coef, N, H, W, Ci, Co, k, stride, pad, flags, dtype, nullptr);
+  } else if (!dgrad) {
     rc = r3m::conv_forward_launch(nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, Ci, Co, k, stride, pad, flags, dtype, nullptr);
   } else {
     r3m::BnRedArgs br{nullptr, mask_bits ? some_bits : nullptr, nullptr, nullptr, nullptr, nullptr, 0};
@@ -257,8 +270,26 @@ int r3m_profile_collect(double* ms, long long* launches, double* flops) {
 }
 const char* r3m_last_error(void) { return g_err; }
 
-r3m_resnet_t r3m_resnet_create(int size, int frames) { return reinterpret_cast<r3m_resnet_t>(plan_create(size, frames, DT_F32)); }
-r3m_resnet_t r3m_resnet_create_dt(int size, int frames, int dtype) { return reinterpret_cast<r3m_resnet_t>(plan_create(size, frames, dtype)); }
+r3m_resnet_t r3m_resnet_create(int size, int frames) { return reinterpret_cast<r3m_resnet_t>(plan_create(size, frames, DT_F32, 224, 224)); }
+r3m_resnet_t r3m_resnet_create_dt(int size, int frames, int dtype) { return reinterpret_cast<r3m_resnet_t>(plan_create(size, frames, dtype, 224, 224)); }
+r3m_resnet_t r3m_resnet_create_hw(int size, int frames, int dtype, int height, int width) {
+  return reinterpret_cast<r3m_resnet_t>(plan_create(size, frames, dtype, height, width));
+}
+int r3m_resnet_input_hw(r3m_resnet_t h, int* height, int* width) {
+  R3M_REQUIRE(h, "resnet_input_hw: null handle");
+  return plan_input_hw(PLAN(h), height, width);
+}
+int r3m_resnet_num_convs(r3m_resnet_t h) { return h ? plan_num_convs(PLAN(h)) : -1; }
+int r3m_resnet_conv_info(r3m_resnet_t h, int i, int* Ci, int* Co, int* k, int* stride, int* pad, int* Hi, int* Wi, int* Ho, int* Wo) {
+  R3M_REQUIRE(h, "resnet_conv_info: null handle");
+  int g[10];
+  if (int e = plan_conv_info(PLAN(h), i, g)) return e;
+  int* outs[9] = {Ci, Co, k, stride, pad, Hi, Wi, Ho, Wo};
+  for (int j = 0; j < 9; ++j)
+    if (outs[j]) *outs[j] = g[j];
+  return 0;
+}
+int r3m_debug_set_generic_stem(int on) { return engine_set_generic_stem(on); }
 int r3m_resnet_dtype(r3m_resnet_t h) { return plan_dtype(PLAN(h)); }
 void r3m_resnet_destroy(r3m_resnet_t h) { if (h) plan_destroy(PLAN(h)); }
 int r3m_resnet_out_dim(r3m_resnet_t h) { return plan_out_dim(PLAN(h)); }
@@ -412,6 +443,31 @@ int r3m_stem_input_grad(const void* dz, int dz_dtype, const float* w_ohwi, float
   if (check_dt(dz_dtype, "stem_input_grad")) return 1;
   return launch_stem_input_grad(dz, dz_dtype, w_ohwi, dx_nchw, frames, accumulate, S(stream));
 }
+
+// the general stem (stem_gen.hip): what plans of frames other than 224 x 224 run
+size_t r3m_stem_gen_image_bytes(int F, int H, int W, int dtype) { return (size_t)F * H * W * 3 * (dtype == DT_BF16 ? 2 : 4); }
+size_t r3m_stem_gen_wgrad_ws_bytes(void) { return stem_wgrad_gen_ws_floats() * 4; }
+int r3m_stem_gen_prep(const float* x, void* xn, int F, int H, int W, int dtype, r3m_stream_t stream) {
+  R3M_REQUIRE(x && xn && F >= 1, "stem_gen_prep: null argument or frames=%d", F);
+  if (check_dt(dtype, "stem_gen_prep")) return 1;
+  return launch_stem_prep_gen(x, static_cast<float*>(xn), F, H, W, dtype, S(stream));
+}
+int r3m_stem_gen_fwd(const void* xn, const float* w147, void* y, float* stats, int F, int H, int W, int dtype, r3m_stream_t stream) {
+  R3M_REQUIRE(xn && w147 && y && F >= 1, "stem_gen_fwd: null argument or frames=%d", F);
+  if (check_dt(dtype, "stem_gen_fwd")) return 1;
+  return launch_stem_fwd_gen(static_cast<const float*>(xn), w147, y, stats, F, H, W, dtype, S(stream));
+}
+int r3m_stem_gen_wgrad(const void* xn, const void* dy, float* dw147, void* ws, int F, int H, int W, int accumulate, int dtype,
+                       r3m_stream_t stream) {
+  R3M_REQUIRE(xn && dy && dw147 && ws && F >= 1, "stem_gen_wgrad: null argument or frames=%d", F);
+  if (check_dt(dtype, "stem_gen_wgrad")) return 1;
+  return launch_stem_wgrad_gen(static_cast<const float*>(xn), dy, dw147, static_cast<float*>(ws), F, H, W, accumulate, dtype, S(stream));
+}
+int r3m_stem_gen_input_grad(const void* dy, const float* w147, float* dx, int F, int H, int W, int accumulate, int dtype, r3m_stream_t stream) {
+  R3M_REQUIRE(dy && w147 && dx, "stem_gen_input_grad: null argument");
+  return launch_stem_input_grad_gen(dy, dtype, w147, dx, F, H, W, accumulate, S(stream));
+}
+int r3m_stem_gen_lds_bytes(int F, int H, int W, int* fwd, int* wgrad, int* input_grad) { return stem_gen_lds(F, H, W, fwd, wgrad, input_grad); }
 
 // stem on the bf16 MFMA (what bf16 plans run): padded bf16 image of the normalised frames, forward, weight gradient
 size_t r3m_stem_xn16_bytes(int frames) { return stem_xn16_bytes(frames); }

@@ -182,6 +182,7 @@ static inline int pw16_form(const GatherGemmParams&) { return 0; }
 static inline int launch_pw16(const GatherGemmParams&, hipStream_t) { return 1; }
 static inline int pw16_set_mode(int) { return -1; }
 #endif
+bool gg16_route_builds(int route, int flags);            // conv_bf16.hip: whether bf16 route `route` has a kernel for epilogue `flags`
 int gg16_route(const GatherGemmParams& p);              // conv_bf16.hip: kernel family of a bf16 launch (r3m_debug_conv_route): 30 gather, 31 halo, 32 kernel-row, 33 probe-build persistent kernel
 // conv_row16.hip (round 6): persistent kernel-row kernel of the 128-multiple-wide bf16 3x3 / stride-1 launches
 bool row16_eligible(const GatherGemmParams& p);
@@ -197,6 +198,17 @@ size_t stem_wgrad16_ws_floats();
 int launch_stem_wgrad16(const void* xn16, const void* dY, float* dw147, float* ws, int F, int accumulate, hipStream_t s);
 // ---- launcher (stem_dgrad.hip): input gradient of the stem, dz [F,112,112,64] fp32 / bf16 -> dx [F,3,224,224] fp32 NCHW (= or +=) ----
 int launch_stem_input_grad(const void* dz, int dt, const float* w147, float* dx, int F, int accumulate, hipStream_t s);
+// ---- launchers (stem_gen.hip): the stem for frames of any H x W in [STEM_GEN_MIN, STEM_GEN_MAX]; xn = [F][H][W*3] normalised frames,
+// fp32 (dt = DT_F32) or bf16 (DT_BF16) behind a float pointer ----
+constexpr int STEM_GEN_MIN = 32, STEM_GEN_MAX = 512;
+int stem_gen_check(int F, int H, int W);
+int launch_stem_prep_gen(const float* x_nchw, float* xn, int F, int H, int W, int dt, hipStream_t s);
+int launch_stem_fwd_gen(const float* xn, const float* w147, void* y, float* stats, int F, int H, int W, int dt, hipStream_t s);
+size_t stem_wgrad_gen_ws_floats();
+int launch_stem_wgrad_gen(const float* xn, const void* dY, float* dw147, float* ws, int F, int H, int W, int accumulate, int dt,
+                          hipStream_t s);
+int launch_stem_input_grad_gen(const void* dz, int dt, const float* w147, float* dx, int F, int H, int W, int accumulate, hipStream_t s);
+int stem_gen_lds(int F, int H, int W, int* fwd, int* wgrad, int* dgrad);
 
 // ---- launchers (bn.hip) ----
 size_t bn_acc_bytes(int C);   // fp64 slice accumulator: [slices <= max(64, min(256, 131072 / C))][2][C]

@@ -968,7 +968,7 @@ bool gather_gemm_fuses_affine(const GatherGemmParams& p_in) {
   GatherGemmParams p = p_in;
   for (int t = 0; t < p.ntaps; ++t)
     p.tap[t] = (int)((unsigned)(unsigned char)p.dy[t] | ((unsigned)(unsigned char)p.dx[t] << 8) | ((unsigned)p.wt[t] << 16));
-  if (p.dtype == DT_BF16) return (p.Nc & 7) == 0 && (p.Ci & 63) == 0;
+  if (p.dtype == DT_BF16) return (p.Nc & 7) == 0 && (p.Ci & 63) == 0 && gg16_route_builds(gg16_route(p), p.flags);
   const int r = gg_route(p);
   if (r == GG_ROUTE_WIN) return p.flags == (EPI_AFFINE | EPI_RELU) || p.flags == (EPI_AFFINE | EPI_ACCUM | EPI_RELU);
   return r > GG_ROUTE_PW && r < GG_ROUTE_K16;

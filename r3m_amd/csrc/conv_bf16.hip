@@ -557,6 +557,18 @@ static int gg16_big() {
 }
 
 // which kernel family launch_gather_gemm_bf16 runs (a pure function of the launch parameters; r3m_debug_conv_route reports it without a GPU)
+// Which epilogue flag combinations each bf16 route builds (the switches of gg16_launch, halo_launch, row16_launch; the probe-build
+// persistent kernel conv_pw16.hip has no inference epilogue). What gather_gemm_fuses_affine answers from, as the fp32 branch from gg_route.
+bool gg16_route_builds(int route, int flags) {
+  switch (flags) {
+    case 0: case EPI_STATS: case EPI_ACCUM: case EPI_MASKED_ADD: case EPI_BNRED: case EPI_BNRED | EPI_MASKED_ADD:
+      return route >= 30 && route <= 32;
+    case EPI_AFFINE | EPI_RELU: case EPI_AFFINE | EPI_ACCUM | EPI_RELU: return route >= 30 && route <= 32;
+    case EPI_AFFINE: return route == 30;
+    default: return false;
+  }
+}
+
 int gg16_route(const GatherGemmParams& p) {
   if (row16_eligible(p)) return 32;
   if (gg16_halo() && halo_eligible(p) && pw16_form(p) != 3 && halo_tile_rows(p)) return 31;

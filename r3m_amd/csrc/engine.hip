@@ -58,6 +58,10 @@ struct TensorInfo {
 
 struct Plan {
   int size, F, D;
+  int H = 224, W = 224;   // input frames [F,3,H,W]
+  int H1 = 112, W1 = 112; // stem output (conv1), the maxpool's input
+  int Hp = 56, Wp = 56;   // maxpool output, layer1's input
+  int stem_gen = 0;       // the last forward ran the general stem (stem_gen.hip): its backward must too (the normalised image layout)
   int dtype = DT_F32;     // activation storage: fp32, or bf16 (bf16 conv operands, fp32 accumulation / statistics / gradients of weights)
   long long w16_off = 0;  // arena: bf16 image of the flat parameter buffer (DT_BF16 only)
   std::vector<ConvSpec> convs;
@@ -132,13 +136,29 @@ static int add_conv(Plan& P, const std::string& name, const std::string& bn, int
   return (int)P.convs.size() - 1;
 }
 
-Plan* plan_create(int size, int F, int dtype) {
+static int g_generic_stem = 0;   // r3m_debug_set_generic_stem: 1 = 224 x 224 frames run the general stem kernels too (tests, A/B)
+int engine_set_generic_stem(int on) { const int old = g_generic_stem; g_generic_stem = on ? 1 : 0; return old; }
+
+// torchvision's output size of a k x k / stride / pad layer, per dimension
+static int out_dim(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
+
+Plan* plan_create(int size, int F, int dtype, int H, int W) {
   if (size != 18 && size != 34 && size != 50) { set_last_error("resnet: unsupported size %d (18, 34, 50)", size); return nullptr; }
   if (dtype != DT_F32 && dtype != DT_BF16) { set_last_error("resnet: unsupported dtype %d (0 fp32, 1 bf16)", dtype); return nullptr; }
   if (F < 1) { set_last_error("resnet: F=%d must be >= 1", F); return nullptr; }
+  if (H < STEM_GEN_MIN || W < STEM_GEN_MIN || H > STEM_GEN_MAX || W > STEM_GEN_MAX) {
+    set_last_error("resnet: frames %d x %d outside the supported %d..%d per side (below %d a stem tile could span more than two "
+                   "frames; above %d the general stem's staged rows leave the 160 KiB LDS of a CU)", H, W, STEM_GEN_MIN, STEM_GEN_MAX,
+                   STEM_GEN_MIN, STEM_GEN_MAX);
+    return nullptr;
+  }
   Plan* Pp = new Plan();
   Plan& P = *Pp;
   P.size = size; P.F = F; P.dtype = dtype;
+  P.H = H; P.W = W;
+  P.H1 = out_dim(H, 7, 2, 3); P.W1 = out_dim(W, 7, 2, 3);
+  P.Hp = out_dim(P.H1, 3, 2, 1); P.Wp = out_dim(P.W1, 3, 2, 1);
+  const bool is224 = H == 224 && W == 224;
   P.fuse_bnred = dtype == DT_F32 ? 1 : 0;   // see side_init(): measured gain for fp32 plans, measured loss for bf16 plans
   const bool bottleneck = (size == 50);
   const int expansion = bottleneck ? 4 : 1;
@@ -146,9 +166,9 @@ Plan* plan_create(int size, int F, int dtype) {
   P.D = 512 * expansion;
 
   // ---- layer table in torchvision parameter order ----
-  add_conv(P, "conv1", "bn1", 3, 64, 7, 2, 3, 224, 224);
+  add_conv(P, "conv1", "bn1", 3, 64, 7, 2, 3, H, W);
   P.stage_param_begin[0] = 0;
-  int inC = 64, H = 56;
+  int inC = 64, Hc = P.Hp, Wc = P.Wp;
   for (int L = 0; L < 4; ++L) {
     const int planes = 64 << L;
     if (L > 0) P.stage_param_begin[L] = P.n_params;
@@ -159,26 +179,53 @@ Plan* plan_create(int size, int F, int dtype) {
       const std::string p(pre);
       BlockSpec B;
       B.stage = L; B.ds = -1;
-      const int Hout = H / stride;
+      const int Hout = out_dim(Hc, 3, stride, 1), Wout = out_dim(Wc, 3, stride, 1);   // == the 1x1 / stride downsample's
       if (bottleneck) {
         B.nconv = 3;
-        B.conv[0] = add_conv(P, p + ".conv1", p + ".bn1", inC, planes, 1, 1, 0, H, H);
-        B.conv[1] = add_conv(P, p + ".conv2", p + ".bn2", planes, planes, 3, stride, 1, H, H);
-        B.conv[2] = add_conv(P, p + ".conv3", p + ".bn3", planes, planes * 4, 1, 1, 0, Hout, Hout);
+        B.conv[0] = add_conv(P, p + ".conv1", p + ".bn1", inC, planes, 1, 1, 0, Hc, Wc);
+        B.conv[1] = add_conv(P, p + ".conv2", p + ".bn2", planes, planes, 3, stride, 1, Hc, Wc);
+        B.conv[2] = add_conv(P, p + ".conv3", p + ".bn3", planes, planes * 4, 1, 1, 0, Hout, Wout);
       } else {
         B.nconv = 2;
-        B.conv[0] = add_conv(P, p + ".conv1", p + ".bn1", inC, planes, 3, stride, 1, H, H);
-        B.conv[1] = add_conv(P, p + ".conv2", p + ".bn2", planes, planes, 3, 1, 1, Hout, Hout);
+        B.conv[0] = add_conv(P, p + ".conv1", p + ".bn1", inC, planes, 3, stride, 1, Hc, Wc);
+        B.conv[1] = add_conv(P, p + ".conv2", p + ".bn2", planes, planes, 3, 1, 1, Hout, Wout);
         B.conv[2] = -1;
       }
       if (stride != 1 || inC != planes * expansion)
-        B.ds = add_conv(P, p + ".downsample.0", p + ".downsample.1", inC, planes * expansion, 1, stride, 0, H, H);
-      B.Ho = B.Wo = Hout; B.Co = planes * expansion;
+        B.ds = add_conv(P, p + ".downsample.0", p + ".downsample.1", inC, planes * expansion, 1, stride, 0, Hc, Wc);
+      B.Ho = Hout; B.Wo = Wout; B.Co = planes * expansion;
       P.blocks.push_back(B);
-      inC = planes * expansion; H = Hout;
+      inC = planes * expansion; Hc = Hout; Wc = Wout;
     }
   }
   P.stage_param_begin[4] = P.n_params;
+  if (!is224) {
+    // Native-resolution plans (224 plans are as they always were). The binding 32-bit index is the GEMM row count M = F Ho Wo: an
+    // int in GatherGemmParams / WgradParams, the row index of gg_epilogue and the general stem's tile origin (stem_gen.hip,
+    // m0 = tile * 256, which must stay below 2^31 after rounding up to 256 rows). Element offsets are formed in 64 bits there, but
+    // no kernel has run on a tensor of 2^31 elements or more (the largest 224 plan, ResNet-50 x 1280 frames, reaches 1.03e9), so
+    // such plans are refused too rather than trusted.
+    long long most_m = 0, most_e = (long long)F * 3 * H * W;
+    std::string what_m, what_e = "the input frames";
+    for (const ConvSpec& c : P.convs) {
+      const long long m = (long long)F * c.Ho * c.Wo;
+      const long long n = std::max((long long)F * c.Hi * c.Wi * c.Ci, m * c.Co);
+      if (m > most_m) { most_m = m; what_m = c.name; }
+      if (n > most_e) { most_e = n; what_e = c.name; }
+    }
+    if (most_m > 0x7fffffffLL - 256) {
+      set_last_error("resnet: %d frames of %d x %d give %lld GEMM rows at %s: GatherGemmParams::M, WgradParams::M and the stem's "
+                     "tile index are 32-bit (limit 2^31 - 257); use fewer frames per plan", F, H, W, most_m, what_m.c_str());
+      delete Pp;
+      return nullptr;
+    }
+    if (most_e > 0x7fffffffLL) {
+      set_last_error("resnet: %d frames of %d x %d give %lld elements at %s: tensors of 2^31 elements or more are not supported "
+                     "(32-bit index range); use fewer frames per plan", F, H, W, most_e, what_e.c_str());
+      delete Pp;
+      return nullptr;
+    }
+  }
 
   // ---- arena layout ----
   long long off = 0;
@@ -188,7 +235,8 @@ Plan* plan_create(int size, int F, int dtype) {
   auto act = [&](long long n) { return dtype == DT_BF16 ? (n + 1) / 2 : n; };
   // private normalised copy of the input frames (the stem's weight gradient re-reads it in backward): fp32 channel-interleaved
   // rows, or for bf16 plans the padded bf16 image of stem_bf16.hip
-  P.col_off = take(dtype == DT_BF16 ? (long long)((stem_xn16_bytes(F) + 3) / 4) : Fll * 3 * 224 * 224);
+  // (the general stem, stem_gen.hip, keeps plain [F][H][W*3] rows: at 224 they fit in either image)
+  P.col_off = take(dtype == DT_BF16 ? (is224 ? (long long)((stem_xn16_bytes(F) + 3) / 4) : (Fll * 3 * H * W + 1) / 2) : Fll * 3 * H * W);
   long long gmax = 0, partial_max = 0, wmax = 0, wgp_max = 0;
   auto act_elems = [&](const ConvSpec& c) { return Fll * c.Ho * c.Wo * c.Co; };
   for (size_t i = 0; i < P.convs.size(); ++i) {
@@ -209,7 +257,8 @@ Plan* plan_create(int size, int F, int dtype) {
     const long long welems = (long long)c.Co * c.k * c.k * c.Ci;
     if (welems > wmax) wmax = welems;
     if (i == 0) {
-      const long long need = dtype == DT_BF16 ? (long long)stem_wgrad16_ws_floats() : (long long)stem_wgrad_ws_floats() + 64 * 160;
+      long long need = (long long)stem_wgrad_gen_ws_floats();
+      if (is224) need = std::max(need, dtype == DT_BF16 ? (long long)stem_wgrad16_ws_floats() : (long long)stem_wgrad_ws_floats() + 64 * 160);
       if (need > wgp_max) wgp_max = need;
     } else {
       const int split = dtype == DT_BF16 ? wgrad_bf16_pick_split(M, c.Co, c.Ci, c.k * c.k) : wgrad_pick_split(M, c.Co, c.Ci, c.k * c.k);
@@ -217,8 +266,8 @@ Plan* plan_create(int size, int F, int dtype) {
     }
   }
   // stem: P0 (pooled) and the argmax bytes; the pre-pool activation Z0 is never materialised (bn.hip: fused stem tail)
-  P.P0_off = take(act(Fll * 56 * 56 * 64));
-  P.amax_off = take((Fll * 56 * 56 * 64 + 3) / 4);
+  P.P0_off = take(act(Fll * P.Hp * P.Wp * 64));
+  P.amax_off = take((Fll * P.Hp * P.Wp * 64 + 3) / 4);
   long long cur_in = P.P0_off;
   for (auto& B : P.blocks) {
     B.in_off = cur_in;
@@ -494,6 +543,8 @@ int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, cons
   const bool infer = training == 2;
   if (infer) training = 0;
   Ctx c{P, params, nullptr, bufs, arena, s, training, 0, P.dtype};
+  R3M_REQUIRE(!crop || (P.H == 224 && P.W == 224), "resnet_forward_crop: the crops are 224 x 224 but this plan takes %d x %d frames "
+              "(create it for 224 x 224)", P.H, P.W);
   P.last_training = training;
   P.last_crop = crop ? 1 : 0;
   P.next_stage = infer ? -3 : 0;   // a new forward invalidates whatever an unfinished backward left behind (-3: nothing to differentiate)
@@ -508,9 +559,14 @@ int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, cons
   if (dt == DT_BF16) TRY(launch_convert_bf16(params, arena + P.w16_off, P.n_params, s));   // bf16 image of every weight (45 MB for ResNet-50)
   // ---- stem: x/255 -> Normalize -> conv1 7x7/2 straight from the NCHW frames (csrc/conv.hip stem_fwd_kernel) ----
   const ConvSpec& L0 = P.convs[0];
+  // frames other than 224 x 224 (and 224 under r3m_debug_set_generic_stem) run the general stem kernels (stem_gen.hip)
+  const bool gen = !crop && (P.H != 224 || P.W != 224 || g_generic_stem);
+  P.stem_gen = gen ? 1 : 0;
   // normalised, channel-interleaved copy of the frames (0.6 MB/frame): read by the stem forward now and by its weight
   // gradient in backward (the caller's tensor may be gone by then)
-  if (crop) {
+  if (gen) {
+    TRY(launch_stem_prep_gen(x_nchw, arena + P.col_off, F, P.H, P.W, dt, s));
+  } else if (crop) {
     if (dt == DT_BF16) TRY(launch_stem_prep16_crop(*crop, arena + P.col_off, F, s));
     else TRY(launch_stem_prep_crop(*crop, arena + P.col_off, F, s));
   } else if (dt == DT_BF16) {
@@ -521,11 +577,12 @@ int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, cons
   {
     float* partial = arena + P.partial_off;
     double* acc = reinterpret_cast<double*>(arena + P.acc_off);
-    if (dt == DT_BF16) TRY(launch_stem_fwd16(arena + P.col_off, params + L0.w_off, arena + L0.Y_off, training ? partial : nullptr, F, s));
+    if (gen) TRY(launch_stem_fwd_gen(arena + P.col_off, params + L0.w_off, arena + L0.Y_off, training ? partial : nullptr, F, P.H, P.W, dt, s));
+    else if (dt == DT_BF16) TRY(launch_stem_fwd16(arena + P.col_off, params + L0.w_off, arena + L0.Y_off, training ? partial : nullptr, F, s));
     else TRY(launch_stem_fwd(arena + P.col_off, params + L0.w_off, arena + L0.Y_off, training ? partial : nullptr, F, dt, s));
     if (training) {
       TRY(launch_bn_stats_reduce(partial, L0.stats_rows, 64, acc, s));
-      TRY(launch_bn_finalize_rows(acc, L0.stats_rows, (long long)F * 12544, params + L0.gamma_off, params + L0.beta_off,
+      TRY(launch_bn_finalize_rows(acc, L0.stats_rows, (long long)F * L0.Ho * L0.Wo, params + L0.gamma_off, params + L0.beta_off,
                                   bufs + L0.rm_off, bufs + L0.rv_off, 0.1f, 1e-5f, coef(c, L0, 0), coef(c, L0, 1), coef(c, L0, 2),
                                   coef(c, L0, 3), 64, s));
     } else {
@@ -535,7 +592,7 @@ int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, cons
   }
   // BatchNorm + ReLU + MaxPool in one pass over Y0
   TRY(launch_bn_relu_maxpool_fwd(arena + L0.Y_off, coef(c, L0, 2), coef(c, L0, 3), arena + P.P0_off,
-                                 reinterpret_cast<unsigned char*>(arena + P.amax_off), F, 112, 112, 64, dt, s));
+                                 reinterpret_cast<unsigned char*>(arena + P.amax_off), F, P.H1, P.W1, 64, dt, s));
   // ---- residual stages ----
   if (infer && g_fused_inference) {
     // Inference: per block, every convolution stores its activated output itself — inner convs relu(bn(conv)), the downsample conv
@@ -769,7 +826,7 @@ static int side_init(Plan& P) {
 }
 
 // grads == nullptr: no parameter gradient (frozen encoder) — no weight-gradient launch is enqueued, the side stream stays idle and
-// the BatchNorm parameter sums go to plan scratch. dx != nullptr (only with stage 3 in range): d/d(frames) [F,3,224,224] fp32 NCHW
+// the BatchNorm parameter sums go to plan scratch. dx != nullptr (only with stage 3 in range): d/d(frames) [F,3,H,W] fp32 NCHW
 // of the frames of the last forward (stem_dgrad.hip), written (dx_accumulate = 0) or added.
 int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
                   int accumulate, int* gd_io, hipStream_t s, float* dx, int dx_accumulate) {
@@ -958,25 +1015,29 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
       float* Gc = Gp(4);
       {   // MaxPool backward gathered inside both BatchNorm-backward passes (no dZ0 tensor)
         const unsigned char* am = reinterpret_cast<const unsigned char*>(arena + P.amax_off);
-        const long long rows = (long long)F * 112 * 112;
+        const long long rows = (long long)F * P.H1 * P.W1;
         float* partial = arena + P.partial_off;
         double* acc = reinterpret_cast<double*>(arena + P.acc_off);
         TRY(launch_bn_bwd_reduce_pool(Gp(0), am, arena + L0.Y_off, coef(c, L0, 2), coef(c, L0, 3), coef(c, L0, 0), coef(c, L0, 1), partial,
-                                      F, 112, 112, 64, dt, s));
-        const int prow = bn_bwd_pool_partial_rows(F, 112, 112, 64);
+                                      F, P.H1, P.W1, 64, dt, s));
+        const int prow = bn_bwd_pool_partial_rows(F, P.H1, P.W1, 64);
         TRY(launch_bn_stats_reduce(partial, prow, 64, acc, s));
         TRY(launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.dgamma(L0), c.dbeta(L0), coef(c, L0, 4),
                                         coef(c, L0, 5), c.bn_accumulate(), 64, s));
         TRY(launch_bn_bwd_apply_pool(Gp(0), am, arena + L0.Y_off, coef(c, L0, 2), coef(c, L0, 3), coef(c, L0, 0), coef(c, L0, 1),
-                                     coef(c, L0, 4), coef(c, L0, 5), Gc, F, 112, 112, 64, dt, s));
+                                     coef(c, L0, 4), coef(c, L0, 5), Gc, F, P.H1, P.W1, 64, dt, s));
       }
       TRY(join_side());   // the stem wgrad shares the split-K scratch with the side stream's wgrads
       if (grads) {
-        if (dt == DT_BF16) TRY(launch_stem_wgrad16(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, s));
+        if (P.stem_gen) TRY(launch_stem_wgrad_gen(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, P.H, P.W, accumulate, dt, s));
+        else if (dt == DT_BF16) TRY(launch_stem_wgrad16(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, s));
         else TRY(launch_stem_wgrad(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, dt, s));
       }
       // Gc = conv1's output gradient; the bf16 rounding of the normalised frames is taken as identity (as autocast does)
-      if (dx) TRY(launch_stem_input_grad(Gc, dt, params + L0.w_off, dx, F, dx_accumulate, s));
+      if (dx) {
+        if (P.stem_gen) TRY(launch_stem_input_grad_gen(Gc, dt, params + L0.w_off, dx, F, P.H, P.W, dx_accumulate, s));
+        else TRY(launch_stem_input_grad(Gc, dt, params + L0.w_off, dx, F, dx_accumulate, s));
+      }
     }
     TRY(join_side());     // a finished stage's gradients are complete on the main stream (all-reduce hook, Adam)
   }
@@ -987,6 +1048,19 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
 
 // ---- accessors for the C ABI ----
 int plan_out_dim(Plan* P) { return P->D; }
+int plan_input_hw(Plan* P, int* H, int* W) {
+  if (H) *H = P->H;
+  if (W) *W = P->W;
+  return 0;
+}
+int plan_num_convs(Plan* P) { return (int)P->convs.size(); }
+int plan_conv_info(Plan* P, int i, int* geo10) {
+  R3M_REQUIRE(i >= 0 && i < (int)P->convs.size(), "conv_info: index %d out of range [0, %d)", i, (int)P->convs.size());
+  const ConvSpec& c = P->convs[i];
+  const int v[10] = {c.Ci, c.Co, c.k, c.stride, c.pad, c.Hi, c.Wi, c.Ho, c.Wo, 0};
+  for (int k = 0; k < 10; ++k) geo10[k] = v[k];
+  return 0;
+}
 int plan_dtype(Plan* P) { return P->dtype; }
 long long plan_num_params(Plan* P) { return P->n_params; }
 long long plan_num_buffers(Plan* P) { return P->n_buffers; }

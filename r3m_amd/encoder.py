@@ -89,10 +89,10 @@ PRECISIONS = {"fp32": 0, "bf16": 1}   # R3M_DT_F32 / R3M_DT_BF16 (include/r3m_hi
 class _LiveSlot:
     """Saved state of one forward pass: native plans (per frame count; a plan also carries the staged-backward state), the HBM
     arena holding that forward's activations, and a generation counter that tells a late backward its activations are gone."""
-    __slots__ = ("plans", "arena", "generation", "F", "waiting")
+    __slots__ = ("plans", "arena", "generation", "F", "hw", "waiting")
 
     def __init__(self):
-        self.plans, self.arena, self.generation, self.F = {}, None, 0, None
+        self.plans, self.arena, self.generation, self.F, self.hw = {}, None, 0, None, (224, 224)
         self.waiting = None      # weakref to the autograd node whose backward will read this slot's activations (None: nobody)
 
     @property
@@ -335,15 +335,39 @@ class HipResNet(nn.Module):
         if self._scratch is not None:
             self._scratch.arena = None
 
-    def _plan(self, F, slot=0):
+    def _plan(self, F, slot=0, hw=(224, 224)):
+        """the slot's native plan for F frames of hw = (H, W); cached under F for 224 x 224 frames, under (F, H, W) otherwise"""
         plans = self._slot(slot).plans
-        h = plans.get(F)
+        hw = (int(hw[0]), int(hw[1]))
+        key = F if hw == (224, 224) else (F,) + hw
+        h = plans.get(key)
         if h is None:
-            h = _lib.lib().r3m_resnet_create_dt(self.size, F, PRECISIONS[self.precision])
-            if not h:
-                raise RuntimeError(_lib.last_error())
-            plans[F] = h
+            if hw == (224, 224):
+                h = _lib.lib().r3m_resnet_create_dt(self.size, F, PRECISIONS[self.precision])
+                if not h:
+                    raise RuntimeError(_lib.last_error())
+            else:
+                h = _lib.lib().r3m_resnet_create_hw(self.size, F, PRECISIONS[self.precision], hw[0], hw[1])
+                if not h:
+                    raise ValueError(f"r3m_amd: {F} frames of {hw[0]}x{hw[1]}: {_lib.last_error()}")
+            plans[key] = h
         return h
+
+    _HW_OK = set()
+
+    @classmethod
+    def check_input_hw(cls, H, W):
+        """ValueError with the engine's message when no plan takes [F,3,H,W] frames (sizes outside 32..512). Checked before a forward
+        takes a ring slot, so a refused size never evicts a live forward."""
+        hw = (int(H), int(W))
+        if hw in cls._HW_OK:
+            return
+        L = _lib.lib()
+        h = L.r3m_resnet_create_hw(18, 1, 0, hw[0], hw[1])
+        if not h:
+            raise ValueError(f"r3m_amd: frames of {hw[0]}x{hw[1]}: {_lib.last_error()}")
+        L.r3m_resnet_destroy(h)
+        cls._HW_OK.add(hw)
 
     def __del__(self):
         try:
@@ -369,15 +393,17 @@ class HipResNet(nn.Module):
             p.grad = None
 
     def _run_forward(self, x, training, crop=None, saved=False):
-        """x: [F,3,224,224] fp32 frames, or None with crop = augment.CroppedClips (raw clips + boxes, resampled in the stem pre-pass).
+        """x: [F,3,H,W] fp32 frames, or None with crop = augment.CroppedClips (raw clips + boxes, resampled in the stem pre-pass).
         saved: the call comes from autograd (_EncoderFn) and a backward will read this forward's activations."""
         L = _lib.lib()
         src = crop.raw if crop is not None else x
         F = src.shape[0]
-        si, self._ring_pos = _pick_slot([sl.live for sl in self._ring], self._ring_pos, saved)
+        hw = (224, 224) if crop is not None else (x.shape[2], x.shape[3])
+        si, pos = _pick_slot([sl.live for sl in self._ring], self._ring_pos, saved)
+        h = self._plan(F, si, hw)                        # a refused (F, H, W) raises here, before the slot's live forward is dropped
+        self._ring_pos = pos
         slot = self._slot(si)
         slot.waiting = None                              # whatever forward was saved here is gone now
-        h = self._plan(F, si)
         need = L.r3m_resnet_arena_bytes(h)
         if slot.arena is None or slot.arena.numel() < need or slot.arena.device != src.device:
             slot.arena = None   # release first: the arena is the dominant HBM allocation
@@ -401,23 +427,23 @@ class HipResNet(nn.Module):
         if training:
             self._flat_nbt += 1
         slot.generation += 1
-        slot.F = F
+        slot.F, slot.hw = F, hw
         self._last_forward = (si, slot.generation)
         return out
 
     def _run_backward(self, dh, generation, si=0, fire_hooks=True, params=True, input_grad=False):
         """params: write parameter gradients into the flat gradient buffer (False: frozen encoder — no weight-gradient launch, the
-        buffer is neither created nor touched, no stage hook fires). input_grad: return d/d(frames) [F,3,224,224] fp32."""
+        buffer is neither created nor touched, no stage hook fires). input_grad: return d/d(frames) [F,3,H,W] fp32."""
         slot = self._slot(si)
         if generation != slot.generation or slot.arena is None:
             raise RuntimeError(f"r3m_amd: the encoder ran {len(self._ring)} other forward(s) before this backward; its saved "
                                f"activations (one HBM arena per live forward) were overwritten. Construct the encoder with "
                                f"max_live_forwards=k (R3M(..., max_live_forwards=k)) to keep k forwards alive at once")
         L = _lib.lib()
-        h = self._plan(slot.F, si)
+        h = self._plan(slot.F, si, slot.hw)
         g = self.flat_grads() if params else None
         accumulate = 0 if self._grad_fresh else 1
-        dx = torch.empty((slot.F, 3, 224, 224), dtype=torch.float32, device=dh.device) if input_grad else None
+        dx = torch.empty((slot.F, 3) + tuple(slot.hw), dtype=torch.float32, device=dh.device) if input_grad else None
         with _lib.on(dh):
             for stage in range(4):
                 if g is not None and dx is None:     # the pre-training path: unchanged launch sequence
@@ -435,8 +461,9 @@ class HipResNet(nn.Module):
         return dx
 
     def forward(self, x):
-        """x: [F,3,224,224] float32 CUDA tensor with values in 0..255 (the /255 and Normalize of R3M.forward are fused into
-        the stem kernel). Returns [F, outdim]."""
+        """x: [F,3,H,W] float32 CUDA tensor with values in 0..255, any H and W in 32..512 (torchvision's ResNet takes any size; 224 x 224
+        runs the specialised stem kernels, other sizes the general ones). The /255 and Normalize of R3M.forward are fused into the stem
+        kernel. Returns [F, outdim]."""
         if not x.is_cuda:
             raise RuntimeError("r3m_amd: the encoder runs on MI355X through libr3m_hip.so only; got a CPU tensor "
                                "(no CPU / eager fallback exists — the CPU oracle lives under oracle/ for tests)")
@@ -444,8 +471,11 @@ class HipResNet(nn.Module):
         crop = x if isinstance(x, CroppedClips) else None
         if crop is not None and tuple(crop.out_hw) != (224, 224):
             raise ValueError(f"CroppedClips must resample to 224x224, got {crop.out_hw}")
-        if crop is None and (x.dim() != 4 or tuple(x.shape[1:]) != (3, 224, 224)):
-            raise ValueError(f"expected [F,3,224,224], got {tuple(x.shape)}")
+        if crop is None:
+            if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
+                raise ValueError(f"expected [F,3,H,W] frames, got {tuple(x.shape)}")
+            if tuple(x.shape[2:]) != (224, 224):
+                self.check_input_hw(x.shape[2], x.shape[3])
         self._ensure()
         if self._flat_p.device != x.device:
             raise RuntimeError(f"encoder parameters on {self._flat_p.device}, input on {x.device}")

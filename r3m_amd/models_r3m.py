@@ -78,7 +78,9 @@ class R3M(nn.Module):
             # as 224x224; example.py users with other sizes land here). One HIP gather pass that computes only the crop window.
             from .augment import resize_center_crop
             obs = resize_center_crop(obs.reshape(-1, *obs.shape[-3:]))
-        # "Input must be [0, 255], [3,224,224]" (models_r3m.py:96): x.float()/255 -> Normalize -> convnet, all in the engine
+        # "Input must be [0, 255], [3,224,224]" (models_r3m.py:96): x.float()/255 -> Normalize -> convnet, all in the engine. With the
+        # default obs_shape the reference hands the frames to torchvision's ResNet at whatever size they have: so does this (any H, W
+        # in 32..512; HipResNet.forward)
         return self.convnet(obs)
 
     def sim(self, tensor1, tensor2):

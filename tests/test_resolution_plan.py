@@ -1,0 +1,236 @@
+"""CPU: native-resolution plans (r3m_resnet_create_hw). Every convolution's geometry matches torchvision's shapes for the same input
+size (taken from the pinned oracle, oracle/resnet_ref.py, with forward hooks on a meta tensor), a 224 x 224 plan is the plan
+r3m_resnet_create_dt makes, out-of-range sizes are refused with a message, and the general stem stays inside a CU's LDS."""
+import ctypes as C
+
+import pytest
+import torch
+
+SWEEP = [(s, s) for s in (32, 33, 47, 84, 96, 127, 128, 160, 223, 225, 256, 320, 511, 512)] + [(96, 160), (97, 131), (160, 96),
+                                                                                              (33, 512), (512, 47)]
+
+
+@pytest.fixture(scope="module")
+def L():
+    from r3m_amd import _lib
+    return _lib.lib()
+
+
+def _torch_convs(size, H, W):
+    """[(Ci, Co, k, stride, pad, Hi, Wi, Ho, Wo)] of the oracle's convolutions in module order (= the engine's table order)"""
+    from oracle import resnet_ref
+    with torch.device("meta"):
+        m = getattr(resnet_ref, f"resnet{size}")()
+    m.eval()                     # eval BatchNorm: one frame at 32 x 32 leaves layer4 a single value per channel
+    out = []
+
+    def hook(mod, inp, res):
+        x = inp[0]
+        out.append((mod.in_channels, mod.out_channels, mod.kernel_size[0], mod.stride[0], mod.padding[0], x.shape[2], x.shape[3],
+                    res.shape[2], res.shape[3]))
+    for mod in m.modules():
+        if isinstance(mod, torch.nn.Conv2d):
+            mod.register_forward_hook(hook)
+    with torch.no_grad():
+        m(torch.empty(1, 3, H, W, device="meta"))
+    return out
+
+
+def _plan_convs(L, h):
+    v = [C.c_int() for _ in range(9)]
+    out = []
+    for i in range(L.r3m_resnet_num_convs(h)):
+        assert L.r3m_resnet_conv_info(h, i, *[C.byref(x) for x in v]) == 0, L.r3m_last_error()
+        out.append(tuple(x.value for x in v))
+    return out
+
+
+@pytest.mark.parametrize("size", [18, 34, 50])
+def test_conv_geometry_matches_torchvision(L, size):
+    for H, W in SWEEP:
+        for dt in (0, 1):
+            h = L.r3m_resnet_create_hw(size, 3, dt, H, W)
+            assert h, L.r3m_last_error()
+            try:
+                hh, ww = C.c_int(), C.c_int()
+                assert L.r3m_resnet_input_hw(h, C.byref(hh), C.byref(ww)) == 0 and (hh.value, ww.value) == (H, W)
+                assert _plan_convs(L, h) == _torch_convs(size, H, W), (size, H, W)
+                assert L.r3m_resnet_arena_bytes(h) > 0
+            finally:
+                L.r3m_resnet_destroy(h)
+
+
+@pytest.mark.parametrize("size", [18, 34, 50])
+@pytest.mark.parametrize("dt", [0, 1])
+def test_create_hw_224_is_create_dt(L, size, dt):
+    a = L.r3m_resnet_create_dt(size, 16, dt)
+    b = L.r3m_resnet_create_hw(size, 16, dt, 224, 224)
+    try:
+        for q in ("r3m_resnet_num_params", "r3m_resnet_num_buffers", "r3m_resnet_arena_bytes", "r3m_resnet_num_tensors",
+                  "r3m_resnet_out_dim", "r3m_resnet_num_convs"):
+            assert getattr(L, q)(a) == getattr(L, q)(b), q
+        name = C.create_string_buffer(128)
+        kind, ndim, off = C.c_int(), C.c_int(), C.c_longlong()
+        shape = (C.c_int * 4)()
+        for i in range(L.r3m_resnet_num_tensors(a)):
+            rows = []
+            for h in (a, b):
+                assert L.r3m_resnet_tensor_info(h, i, name, 128, C.byref(kind), C.byref(off), C.byref(ndim), shape) == 0
+                rows.append((name.value, kind.value, off.value, ndim.value, tuple(shape)))
+            assert rows[0] == rows[1]
+        assert _plan_convs(L, a) == _plan_convs(L, b)
+    finally:
+        L.r3m_resnet_destroy(a)
+        L.r3m_resnet_destroy(b)
+
+
+def test_the_224_arena_is_unchanged(L):
+    """the arena bytes of the 224 plans the benchmark and the pre-training configs use (recorded before native resolution)"""
+    before = {(50, 1280, 0): 130016689152, (50, 1280, 1): 65723442432, (34, 2560, 1): 57598364672, (18, 16, 0): 632033024}
+    for (size, F, dt), nbytes in before.items():
+        h = L.r3m_resnet_create_dt(size, F, dt)
+        g = L.r3m_resnet_create_hw(size, F, dt, 224, 224)
+        assert h and g and L.r3m_resnet_arena_bytes(h) == L.r3m_resnet_arena_bytes(g) == nbytes
+        L.r3m_resnet_destroy(h)
+        L.r3m_resnet_destroy(g)
+
+
+@pytest.mark.parametrize("H,W", [(31, 64), (64, 31), (16, 16), (513, 256), (256, 513), (1024, 1024), (0, 224), (-5, 224)])
+def test_out_of_range_sizes_are_refused(L, H, W):
+    assert not L.r3m_resnet_create_hw(50, 2, 0, H, W)
+    msg = L.r3m_last_error().decode()
+    assert "32..512" in msg and f"{H} x {W}" in msg, msg
+
+
+def test_32bit_index_overflow_is_refused(L):
+    assert not L.r3m_resnet_create_hw(50, 600, 0, 512, 512)
+    msg = L.r3m_last_error().decode()
+    assert "32-bit" in msg and "2^31" in msg, msg
+    h = L.r3m_resnet_create_hw(50, 64, 0, 512, 512)
+    assert h, L.r3m_last_error()
+    L.r3m_resnet_destroy(h)
+
+
+def test_general_stem_lds_fits_a_cu(L):
+    f, w, d = C.c_int(), C.c_int(), C.c_int()
+    worst = [0, 0, 0]
+    for H in range(32, 513, 3):
+        for W in list(range(32, 513, 1)):
+            for F in (1, 3):
+                assert L.r3m_stem_gen_lds_bytes(F, H, W, C.byref(f), C.byref(w), C.byref(d)) == 0
+                worst = [max(a, b) for a, b in zip(worst, (f.value, w.value, d.value))]
+    assert max(worst) <= 160 * 1024, worst
+    assert L.r3m_stem_gen_lds_bytes(1, 31, 64, C.byref(f), C.byref(w), C.byref(d)) != 0
+
+
+def test_forward_crop_needs_a_224_plan(L):
+    """r3m_resnet_forward_crop refuses a plan that is not 224 x 224 before anything is launched (dummy non-null pointers)"""
+    h = L.r3m_resnet_create_hw(18, 2, 0, 128, 128)
+    try:
+        boxes = (C.c_int * 8)()
+        rc = L.r3m_resnet_forward_crop(h, 64, 1, C.addressof(boxes), 1, 240, 320, 64, 64, 64, 64, 1, None)
+        assert rc != 0 and "224" in L.r3m_last_error().decode()
+    finally:
+        L.r3m_resnet_destroy(h)
+
+
+def test_hip_resnet_refuses_out_of_range_frames_on_the_cpu():
+    from r3m_amd.encoder import HipResNet
+    with pytest.raises(ValueError, match="32..512"):
+        HipResNet.check_input_hw(31, 224)
+    HipResNet.check_input_hw(97, 131)
+
+
+# ---- every launch of the swept plans runs a kernel built for the epilogue the engine asks of it -----------------------------------
+STATS, ACCUM, MASKED_ADD, BNRED, AFFINE, RELU = 1, 2, 4, 64, 128, 16
+_GG_SWITCH = {0, STATS, ACCUM, MASKED_ADD, 8, RELU, 8 | RELU, 32, BNRED, BNRED | MASKED_ADD}       # csrc/conv.hip GG_EPI_SWITCH
+_PW = {0, STATS, ACCUM, BNRED, MASKED_ADD, BNRED | MASKED_ADD, AFFINE, AFFINE | RELU, AFFINE | ACCUM | RELU}   # conv_pw.hip pw_flags_ok
+_BF16 = {0, STATS, ACCUM, MASKED_ADD, BNRED, BNRED | MASKED_ADD, AFFINE | RELU, AFFINE | ACCUM | RELU}
+# route -> epilogue flag combinations its kernels are built with (the launchers' switches)
+BUILT = {
+    1: _GG_SWITCH | {AFFINE | RELU, AFFINE | ACCUM | RELU},     # 3x3 window kernel (LAUNCH_WIN cases + GG_EPI_SWITCH)
+    11: _PW, 12: _PW, 13: _PW,                                  # persistent kernel, three forms
+    20: _GG_SWITCH, 21: _GG_SWITCH, 22: _GG_SWITCH,             # 16-wide-K, gather, generic kernels
+    30: _BF16 | {AFFINE},                                       # bf16 gather kernel (gg16_launch)
+    31: _BF16, 32: _BF16,                                       # bf16 halo (halo_launch), kernel-row (row16_launch)
+}
+
+
+def _blocks(L, h, size):
+    """[(convs of the block in order, downsample conv or None)] from the plan's conv table (torchvision module order)"""
+    convs = _plan_convs(L, h)[1:]
+    n = 3 if size == 50 else 2
+    out, i = [], 0
+    while i < len(convs):
+        body = convs[i:i + n]
+        i += n
+        ds = None
+        if i < len(convs) and convs[i][2] == 1 and convs[i][0] == body[0][0] and convs[i][1] == body[-1][1] and \
+                (convs[i][3] == 2 or convs[i][0] != convs[i][1]):
+            ds = convs[i]
+            i += 1
+        out.append((body, ds))
+    return out
+
+
+@pytest.mark.parametrize("size", [18, 34, 50])
+@pytest.mark.parametrize("dt", [0, 1])
+def test_every_launch_has_a_kernel_built_for_its_epilogue(L, size, dt):
+    """forward (training: statistics; eval with a backward: plain), input gradients with the flags csrc/engine.hip plan_backward asks
+    (fp32 plans fuse the BatchNorm-backward partials: 64; bf16 plans do not), and fused inference (r3m_debug_conv_fuses_affine: where
+    it answers 1 the fused launch's route must build the flags; where 0 the engine runs the unfused sequence, plain forwards)."""
+    buf = (C.c_int * 8)()
+
+    def routes(F, c, dgrad, flags, bits=0):
+        Ci, Co, k, s, p, Hi, Wi = c[:7]
+        n = L.r3m_debug_conv_route(F, Hi, Wi, Ci, Co, k, s, p, dgrad, flags, bits, dt, buf, 8)
+        assert n >= 1, (c, dgrad, flags, L.r3m_last_error())
+        return list(buf[:n])
+
+    def check(F, c, dgrad, flags, bits=0):
+        for r in routes(F, c, dgrad, flags, bits):
+            assert r in BUILT and flags in BUILT[r], f"resnet{size} dt={dt} conv {c} dgrad={dgrad} flags={flags}: route {r}"
+
+    fuse_bnred = dt == 0
+    for H, W in SWEEP:
+        for F in (1, 3):
+            h = L.r3m_resnet_create_hw(size, F, dt, H, W)
+            assert h, L.r3m_last_error()
+            try:
+                blocks = _blocks(L, h, size)
+                for bi, (body, ds) in enumerate(blocks):
+                    for c in body + ([ds] if ds else []):
+                        check(F, c, 0, STATS)
+                        check(F, c, 0, 0)
+                    # input gradients (plan_backward)
+                    for j in range(len(body) - 1, 0, -1):
+                        check(F, body[j], 1, BNRED if fuse_bnred else 0)
+                    if ds:
+                        check(F, body[0], 1, 0)
+                        check(F, ds, 1, ACCUM)
+                    else:
+                        check(F, body[0], 1, MASKED_ADD | (BNRED if fuse_bnred and bi > 0 else 0), 1 if bi > 0 else 0)
+                    # inference forward (plan_forward_src, training = 2)
+                    want = [(c, AFFINE | RELU) for c in body[:-1]] + [(body[-1], AFFINE | ACCUM | RELU)] + ([(ds, AFFINE)] if ds else [])
+                    fused = all(L.r3m_debug_conv_fuses_affine(F, c[5], c[6], c[0], c[1], c[2], c[3], c[4], fl, dt) == 1 for c, fl in want)
+                    for c, fl in want:
+                        if fused:
+                            check(F, c, 0, fl)
+                        else:
+                            check(F, c, 0, 0)
+            finally:
+                L.r3m_resnet_destroy(h)
+
+
+def test_bf16_fused_inference_answers_from_the_route(L):
+    """r3m_debug_conv_fuses_affine for bf16 follows the route table (gg16_route + the epilogues each route builds), not the shape
+    alone: a 3x3 stride-1 layer fuses affine + ReLU on the halo / kernel-row route; the plain affine store goes to the gather route,
+    which builds it; a combination no bf16 kernel builds (affine + statistics) is refused even though the shape qualifies"""
+    buf = (C.c_int * 8)()
+    assert L.r3m_debug_conv_route(3, 28, 28, 128, 128, 3, 1, 1, 0, AFFINE | RELU, 0, 1, buf, 8) == 1 and buf[0] in (31, 32)
+    assert L.r3m_debug_conv_fuses_affine(3, 28, 28, 128, 128, 3, 1, 1, AFFINE | RELU, 1) == 1
+    assert L.r3m_debug_conv_route(3, 28, 28, 128, 128, 3, 1, 1, 0, AFFINE, 0, 1, buf, 8) == 1 and buf[0] == 30
+    assert L.r3m_debug_conv_fuses_affine(3, 28, 28, 128, 128, 3, 1, 1, AFFINE, 1) == 1
+    assert L.r3m_debug_conv_fuses_affine(3, 28, 28, 256, 512, 1, 2, 0, AFFINE, 1) == 1
+    assert L.r3m_debug_conv_fuses_affine(3, 28, 28, 128, 128, 3, 1, 1, AFFINE | STATS, 1) == 0
+    assert L.r3m_debug_conv_fuses_affine(3, 28, 28, 128, 128, 1, 1, 0, AFFINE | STATS, 1) == 0
