@@ -1,10 +1,13 @@
 #!/bin/bash
 # Builds libr3m_hip.so for gfx950 (MI355X). hipcc cross-compiles without a GPU. Usage: build.sh [extra hipcc flags]
+# A/B builds (tools/build_ab.sh): R3M_BUILD_SRC = root of another source tree (holding r3m_amd/csrc and include), R3M_BUILD_OUT = the
+# .so to write; with R3M_BUILD_OUT set every source is compiled afresh into a temporary directory (the flags may differ).
 set -e
-HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
-OUT="$HERE/../lib"
-mkdir -p "$OUT" "$HERE/../../build/obj"
-OBJ="$HERE/../../build/obj"
+ROOT="${R3M_BUILD_SRC:-$(cd "$(dirname "${BASH_SOURCE[0]}")/../.." && pwd)}"
+HERE="$ROOT/r3m_amd/csrc"
+LIB="${R3M_BUILD_OUT:-$ROOT/r3m_amd/lib/libr3m_hip.so}"
+if [ -n "$R3M_BUILD_OUT" ]; then OBJ="$(mktemp -d)"; trap 'rm -rf "$OBJ"' EXIT; else OBJ="$ROOT/build/obj"; fi
+mkdir -p "$(dirname "$LIB")" "$OBJ"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function $*"
 # at most MAX_JOBS (default: the CPU count, at most 16) compiles at once; a failed compile is named on stdout and stderr
@@ -17,7 +20,7 @@ for f in $SRCS; do
   [ -f "$HERE/$f.hip" ] || continue
   stale=0
   [ -f "$OBJ/$f.o" ] || stale=1
-  for dep in "$HERE/$f.hip" "$HERE"/*.h "$HERE/../../include/r3m_hip.h" "$HERE/build.sh"; do
+  for dep in "$HERE/$f.hip" "$HERE"/*.h "$ROOT/include/r3m_hip.h" "$HERE/build.sh"; do
     [ "$dep" -nt "$OBJ/$f.o" ] && stale=1
   done
   if [ $stale = 1 ]; then
@@ -44,5 +47,5 @@ if [ -n "$failed" ]; then
 fi
 objs=()
 for f in $SRCS; do [ -f "$OBJ/$f.o" ] && objs+=("$OBJ/$f.o"); done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/libr3m_hip.so" "${objs[@]}"
-echo "built $OUT/libr3m_hip.so"
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$LIB" "${objs[@]}"
+echo "built $LIB"

@@ -1,5 +1,5 @@
 // r3m_amd — extern "C" surface of libr3m_hip.so (declared in include/r3m_hip.h).
-#include "common.h"
+#include "engine.h"
 #include "augment_dev.h"
 #include "../../include/r3m_hip.h"
 #include <cstdarg>
@@ -105,74 +105,6 @@ void prof_end(hipStream_t s) {
   t_prof_open = nullptr;
 }
 
-int debug_occupancy(int* out4);
-// engine.hip
-struct Plan;
-Plan* plan_create(int size, int F, int dtype, int H, int W);
-int engine_set_generic_stem(int on);
-int plan_input_hw(Plan* P, int* H, int* W);
-int plan_num_convs(Plan* P);
-int plan_conv_info(Plan* P, int i, int* geo10);
-int plan_dtype(Plan*);
-int plan_forward(Plan& P, const float* x_nchw, const float* params, float* bufs, float* arena, float* h_out, int training,
-                 hipStream_t s);
-int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena,
-                     float* h_out, int training, hipStream_t s);
-int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
-                  int accumulate, int* gd_io, hipStream_t s, float* dx, int dx_accumulate);
-int conv_forward_launch(const float* X, const float* W, float* Y, float* stats, const float* bias, int N, int Hi, int Wi, int Ci,
-                        int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
-int conv_forward_launch_affine(const float* X, const float* W, float* out, const float* scale, const float* shift, int N, int Hi, int Wi,
-                               int Ci, int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
-bool conv_forward_affine_fusable(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt);
-int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* add0, const float* add1, const unsigned* addbits,
-                      int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
-int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, int N, int Hi, int Wi, int Ci, int Co, int k,
-                      int stride, int pad, int accumulate, int dt, hipStream_t s);
-size_t conv_wgrad_ws_floats(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dt);
-// accessors implemented in engine.hip
-int plan_out_dim(Plan*);
-long long plan_num_params(Plan*);
-long long plan_num_buffers(Plan*);
-long long plan_arena_floats(Plan*);
-int plan_num_tensors(Plan*);
-int plan_tensor_info(Plan*, int i, char* name, int cap, int* kind, long long* offset, int* ndim, int* shape4);
-int plan_stage_range(Plan*, int stage, long long* off, long long* count);
-void plan_destroy(Plan*);
-int* plan_gd(Plan*);
-int plan_set_fuse_bnred(Plan*, int on);
-int plan_set_bn_pair(Plan*, int on);
-// loss.hip / adam.hip
-size_t loss_workspace_floats(int B);
-int launch_tcn_lp_loss(const float* alle, const int* perm, const int* iperm, float* dalle, float* ws, int B, int D, int l2dist,
-                       float l2w, float l1w, float tcnw, hipStream_t s);
-int launch_lang_infonce(const float* scores, const float* mask, float* dscore, float* ws, int B, float langw, hipStream_t s);
-int launch_loss_finalize(float* ws, int B, int have_lang, float* metrics, float l2w, float l1w, float tcnw, float langw,
-                         hipStream_t s);
-int launch_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2, double eps,
-                long long step, float grad_scale, hipStream_t s);
-int launch_sgd(float* p, const float* g, float* momentum_buf, long long n, double lr, double momentum, double dampening,
-               double weight_decay, int nesterov, long long step, float grad_scale, hipStream_t s);
-// augment.hip
-int launch_crop_resize(const void* in, int in_is_u8, const int* boxes, float* out, long long N, int C, int Hi, int Wi, int Ho,
-                       int Wo, int frames_per_box, hipStream_t s);
-int launch_resize_crop(const void* in, int in_is_u8, float* out, long long N, int C, int Hi, int Wi, int full_Ho, int full_Wo,
-                       int top, int left, int Ho, int Wo, hipStream_t s);
-int launch_resize_crop_backward(const float* dout, float* din, long long N, int C, int Hi, int Wi, int full_Ho, int full_Wo, int top,
-                                int left, int Ho, int Wo, int accumulate, hipStream_t s);
-// lang.hip
-long long langrew_num_params(int D, int H, int LD);
-size_t langrew_ws_floats(int B, int D, int H, int LD);
-int langrew_forward(const float* alle, const float* feats, const int* perm, const float* params, float* scores, float* ws, int B,
-                    int D, int H, int LD, int dt, hipStream_t s);
-int langrew_backward(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, float* ws, int B, int D,
-                     int H, int LD, int accumulate, int dt, hipStream_t s);
-size_t langrew_call_ws_floats(int R, int D, int H, int LD);
-int langrew_call_forward(const float* e0, const float* eg, const float* le, const float* params, float* score, float* ws, int R,
-                         int D, int H, int LD, hipStream_t s);
-int langrew_call_backward(const float* dscore, const float* params, float* grads, float* de0, float* deg, float* dle, float* ws,
-                          int R, int D, int H, int LD, int accumulate, hipStream_t s);
-
 }  // namespace r3m
 
 using namespace r3m;
@@ -203,25 +135,26 @@ int r3m_debug_set_pw16(int mode) { return r3m::pw16_set_mode(mode); }
 int r3m_debug_set_conv3x3_bf16(int mode) { return r3m::row16_set_mode(mode); }
 int r3m_debug_set_fused_inference(int on) { return r3m::engine_set_fused_inference(on); }
 int r3m_debug_conv_fuses_affine(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int flags, int dtype) {
-  return r3m::conv_forward_affine_fusable(N, H, W, Ci, Co, k, stride, pad, flags, dtype) ? 1 : 0;
+  return r3m::conv_forward_affine_fusable({N, H, W, Ci, Co, k, stride, pad}, flags, dtype) ? 1 : 0;
 }
 int r3m_debug_conv_route(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int dgrad, int flags, int mask_bits, int dtype,
                          int* routes, int cap) {
   R3M_REQUIRE(routes && cap >= 1, "debug_conv_route: routes buffer");
   // no launch happens: the pointers only have to look like the ones the epilogue flags ask for
   const unsigned* some_bits = reinterpret_cast<const unsigned*>(static_cast<uintptr_t>(64));
+  const r3m::ConvGeom g{N, H, W, Ci, Co, k, stride, pad};
   r3m::gg_route_record_begin(routes, cap);
   int rc;
   if (!dgrad && (flags & EPI_AFFINE)) {        // inference forward: the coefficient pointers the epilogue reads must be set
     const float* coef = reinterpret_cast<const float*>(some_bits);
-    rc = r3m::conv_forward_launch_affine(nullptr, nullptr, nullptr, coef, coef, N, H, W, Ci, Co, k, stride, pad, flags, dtype, nullptr);
+    rc = r3m::conv_forward_launch_affine(nullptr, nullptr, nullptr, coef, coef, g, flags, dtype, nullptr);
   } else if (!dgrad) {
-    rc = r3m::conv_forward_launch(nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, Ci, Co, k, stride, pad, flags, dtype, nullptr);
+    rc = r3m::conv_forward_launch(nullptr, nullptr, nullptr, nullptr, nullptr, g, flags, dtype, nullptr);
   } else {
     r3m::BnRedArgs br{nullptr, mask_bits ? some_bits : nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     const bool bn = (flags & 64) != 0;      // EPI_BNRED: requested through the BnRedArgs, as the engine does
-    rc = r3m::conv_dgrad_launch_br(nullptr, nullptr, nullptr, nullptr, nullptr, (flags & 4) ? some_bits : nullptr, N, H, W, Ci, Co, k, stride, pad,
-                                   flags & ~64, dtype, bn ? &br : nullptr, nullptr);
+    rc = r3m::conv_dgrad_launch(nullptr, nullptr, nullptr, nullptr, nullptr, (flags & 4) ? some_bits : nullptr, g, flags & ~64, dtype, nullptr,
+                                bn ? &br : nullptr);
   }
   const int n = r3m::gg_route_record_end();
   return rc ? -1 : n;
@@ -307,7 +240,7 @@ int r3m_resnet_forward(r3m_resnet_t h, const float* x, const float* params, floa
                        r3m_stream_t stream) {
   R3M_REQUIRE(h && x && params && buffers && arena && h_out, "resnet_forward: null argument");
   R3M_REQUIRE(training >= 0 && training <= 2, "resnet_forward: training=%d (0 eval, 1 train, 2 inference)", training);
-  return plan_forward(*PLAN(h), x, params, buffers, static_cast<float*>(arena), h_out, training, S(stream));
+  return plan_forward(*PLAN(h), x, nullptr, params, buffers, static_cast<float*>(arena), h_out, training, S(stream));
 }
 int r3m_resnet_forward_crop(r3m_resnet_t h, const void* frames, int frames_are_u8, const int* boxes, int frames_per_box, int Hi, int Wi,
                             const float* params, float* buffers, void* arena, float* h_out, int training, r3m_stream_t stream) {
@@ -315,7 +248,7 @@ int r3m_resnet_forward_crop(r3m_resnet_t h, const void* frames, int frames_are_u
   R3M_REQUIRE(frames_per_box >= 1 && Hi >= 1 && Wi >= 1, "resnet_forward_crop: frames_per_box=%d, frames %dx%d", frames_per_box, Hi, Wi);
   R3M_REQUIRE(training >= 0 && training <= 2, "resnet_forward_crop: training=%d (0 eval, 1 train, 2 inference)", training);
   const FrameSource src{frames, frames_are_u8, boxes, frames_per_box, Hi, Wi};
-  return plan_forward_src(*PLAN(h), nullptr, &src, params, buffers, static_cast<float*>(arena), h_out, training, S(stream));
+  return plan_forward(*PLAN(h), nullptr, &src, params, buffers, static_cast<float*>(arena), h_out, training, S(stream));
 }
 int r3m_resnet_set_fused_bn_reduce(r3m_resnet_t h, int on) { return h ? plan_set_fuse_bnred(PLAN(h), on) : -1; }
 int r3m_resnet_set_bn_pair(r3m_resnet_t h, int on) { return h ? plan_set_bn_pair(PLAN(h), on) : -1; }
@@ -323,20 +256,18 @@ int r3m_resnet_backward(r3m_resnet_t h, const float* dh, const float* params, fl
                         int stage_end, int accumulate, r3m_stream_t stream) {
   R3M_REQUIRE(h && dh && params && grads && arena, "resnet_backward: null argument");
   R3M_REQUIRE(0 <= stage_begin && stage_begin <= stage_end && stage_end <= 4, "resnet_backward: stages [%d,%d)", stage_begin, stage_end);
-  return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, plan_gd(PLAN(h)),
-                       S(stream), nullptr, 0);
+  return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, S(stream), nullptr, 0);
 }
 int r3m_resnet_backward_ex(r3m_resnet_t h, const float* dh, const float* params, float* grads, void* arena, int stage_begin,
                            int stage_end, int accumulate, float* dx, int dx_accumulate, r3m_stream_t stream) {
   R3M_REQUIRE(h && dh && params && arena, "resnet_backward_ex: null argument");
   R3M_REQUIRE(0 <= stage_begin && stage_begin <= stage_end && stage_end <= 4, "resnet_backward_ex: stages [%d,%d)", stage_begin, stage_end);
-  return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, plan_gd(PLAN(h)),
-                       S(stream), dx, dx_accumulate);
+  return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, S(stream), dx,
+                       dx_accumulate);
 }
 
 int r3m_conv2d_stats_rows(int N, int Hi, int Wi, int Co, int k, int stride, int pad) {
-  const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
-  return gather_gemm_grid_m(N * Ho * Wo, Co);
+  return gather_gemm_grid_m(ConvGeom{N, Hi, Wi, 0, Co, k, stride, pad}.M(), Co);
 }
 static int check_dt(int dtype, const char* what) {
   R3M_REQUIRE(dtype == DT_F32 || dtype == DT_BF16, "%s: dtype %d (0 = fp32, 1 = bf16)", what, dtype);
@@ -351,7 +282,7 @@ int r3m_convert_bf16(const float* src, void* dst, long long n, r3m_stream_t stre
 int r3m_conv2d_fwd_dt(const void* x, const void* w, void* y, float* stats, int N, int Hi, int Wi, int Ci, int Co, int k, int stride,
                       int pad, int dtype, r3m_stream_t stream) {
   if (check_dt(dtype, "conv2d_fwd")) return 1;
-  return conv_forward_launch(FP(x), FP(w), FPM(y), stats, nullptr, N, Hi, Wi, Ci, Co, k, stride, pad, stats ? EPI_STATS : 0, dtype, S(stream));
+  return conv_forward_launch(FP(x), FP(w), FPM(y), stats, nullptr, {N, Hi, Wi, Ci, Co, k, stride, pad}, stats ? EPI_STATS : 0, dtype, S(stream));
 }
 int r3m_conv2d_fwd(const float* x, const float* w, float* y, float* stats, int N, int Hi, int Wi, int Ci, int Co, int k, int stride,
                    int pad, r3m_stream_t stream) {
@@ -365,7 +296,7 @@ int r3m_conv2d_dgrad_dt(const void* dy, const float* w, void* dx, void* ws, size
   float* Wt = static_cast<float*>(ws);
   if (dtype == DT_BF16) { if (int e = launch_transpose_w_bf16(w, Wt, Co, k * k, Ci, S(stream))) return e; }
   else if (int e = launch_transpose_w(w, Wt, Co, k * k, Ci, S(stream))) return e;
-  return conv_dgrad_launch(FP(dy), Wt, FPM(dx), nullptr, nullptr, nullptr, N, Hi, Wi, Ci, Co, k, stride, pad, 0, dtype, S(stream));
+  return conv_dgrad_launch(FP(dy), Wt, FPM(dx), nullptr, nullptr, nullptr, {N, Hi, Wi, Ci, Co, k, stride, pad}, 0, dtype, S(stream));
 }
 int r3m_conv2d_dgrad_bnred_rows(int N, int Hi, int Wi, int stride) {
   if (stride == 1) return bnred_partial_rows((long long)N * Hi * Wi);
@@ -391,15 +322,15 @@ int r3m_conv2d_dgrad_bnred_dt(const void* dy, const float* w, void* dx, void* ws
   if (dtype == DT_BF16) { if (int e = launch_transpose_w_bf16(w, Wt, Co, k * k, Ci, S(stream))) return e; }
   else if (int e = launch_transpose_w(w, Wt, Co, k * k, Ci, S(stream))) return e;
   BnRedArgs br{FP(bn_y), bn_bits, bn_scale, bn_shift, bn_mean, partials, 0};
-  return conv_dgrad_launch_br(FP(dy), Wt, FPM(dx), FP(residual_grad), nullptr, residual_bits, N, Hi, Wi, Ci, Co, k, stride, pad,
-                              residual_grad ? EPI_MASKED_ADD : 0, dtype, &br, S(stream));
+  return conv_dgrad_launch(FP(dy), Wt, FPM(dx), FP(residual_grad), nullptr, residual_bits, {N, Hi, Wi, Ci, Co, k, stride, pad},
+                           residual_grad ? EPI_MASKED_ADD : 0, dtype, S(stream), &br);
 }
 int r3m_conv2d_dgrad(const float* dy, const float* w, float* dx, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int Ci, int Co,
                      int k, int stride, int pad, r3m_stream_t stream) {
   return r3m_conv2d_dgrad_dt(dy, w, dx, ws, ws_bytes, N, Hi, Wi, Ci, Co, k, stride, pad, DT_F32, stream);
 }
 size_t r3m_conv2d_wgrad_workspace_bytes_dt(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dtype) {
-  return conv_wgrad_ws_floats(N, Hi, Wi, Ci, Co, k, stride, pad, dtype) * 4;
+  return conv_wgrad_ws_floats({N, Hi, Wi, Ci, Co, k, stride, pad}, dtype) * 4;
 }
 size_t r3m_conv2d_wgrad_workspace_bytes(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad) {
   return r3m_conv2d_wgrad_workspace_bytes_dt(N, Hi, Wi, Ci, Co, k, stride, pad, DT_F32);
@@ -408,7 +339,7 @@ int r3m_conv2d_wgrad_dt(const void* x, const void* dy, float* dw, void* ws, size
                         int k, int stride, int pad, int accumulate, int dtype, r3m_stream_t stream) {
   if (check_dt(dtype, "conv2d_wgrad")) return 1;
   R3M_REQUIRE(ws_bytes >= r3m_conv2d_wgrad_workspace_bytes_dt(N, Hi, Wi, Ci, Co, k, stride, pad, dtype), "conv2d_wgrad: workspace too small");
-  return conv_wgrad_launch(FP(x), FP(dy), dw, static_cast<float*>(ws), N, Hi, Wi, Ci, Co, k, stride, pad, accumulate, dtype, S(stream));
+  return conv_wgrad_launch(FP(x), FP(dy), dw, static_cast<float*>(ws), {N, Hi, Wi, Ci, Co, k, stride, pad}, accumulate, dtype, S(stream));
 }
 int r3m_conv2d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int Ci, int Co,
                      int k, int stride, int pad, int accumulate, r3m_stream_t stream) {
@@ -595,7 +526,7 @@ int r3m_avgpool_fwd(const float* x, float* h, int N, int HW, int C, r3m_stream_t
 int r3m_avgpool_bwd(const float* dh, float* dx, int N, int HW, int C, r3m_stream_t stream) { return launch_avgpool_bwd(dh, dx, N, HW, C, DT_F32, S(stream)); }
 
 int r3m_linear_fwd(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int relu, r3m_stream_t stream) {
-  return conv_forward_launch(x, w, y, nullptr, bias, M, 1, 1, K, N, 1, 1, 0, (bias ? EPI_BIAS : 0) | (relu ? EPI_RELU : 0), DT_F32, S(stream));
+  return conv_forward_launch(x, w, y, nullptr, bias, {M, 1, 1, K, N, 1, 1, 0}, (bias ? EPI_BIAS : 0) | (relu ? EPI_RELU : 0), DT_F32, S(stream));
 }
 
 long long r3m_langrew_num_params(int D, int hidden, int lang_dim) { return langrew_num_params(D, hidden, lang_dim); }

@@ -120,23 +120,8 @@ struct WgradParams {
   int debug;           // timing probes (probe builds, R3M_WG_DEBUG: 1 no DMA at all, 2 no X pieces, 4 no dY pieces); 0 in production
 };
 
-// EPI_BNRED request of a dgrad (engine.hip conv_dgrad_launch_br): the result is the dz of a BatchNorm whose input is Y (same
-// shape as dX); partial rows -> `partial`, count -> rows_out
-struct BnRedArgs {
-  const float* Y;
-  const unsigned* bits;      // 1-bit ReLU mask of the BatchNorm(+residual) output, or null: recompute from Y, scale, shift
-  const float* scale;
-  const float* shift;
-  const float* mean;
-  float* partial;
-  int rows_out;              // partial rows written (all launches of the dgrad)
-};
-int engine_set_fused_inference(int on);
-int conv_dgrad_launch_br(const float* dY, const float* Wt, float* dX, const float* add0, const float* add1, const unsigned* addbits,
-                         int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt, BnRedArgs* br,
-                         hipStream_t s);
-
 // ---- launchers (conv.hip) ----
+int debug_occupancy(int* out4);
 int launch_gather_gemm(const GatherGemmParams& p, hipStream_t s);
 double gather_gemm_alg_bytes(const GatherGemmParams& p, int elem_bytes);
 bool gather_gemm_fuses_affine(const GatherGemmParams& p);   // inference forward: the launch's kernel has the EPI_AFFINE epilogues
@@ -252,6 +237,39 @@ int launch_maxpool_fwd(const void* Z, void* P, unsigned char* amax, int N, int H
 int launch_maxpool_bwd(const void* dP, const unsigned char* amax, void* dZ, int N, int Hi, int Wi, int C, int dt, hipStream_t s);
 int launch_avgpool_fwd(const void* X, float* H, int N, int HW, int C, int dt, hipStream_t s);
 int launch_avgpool_bwd(const float* dH, void* dX, int N, int HW, int C, int dt, hipStream_t s);
+
+// ---- losses (loss.hip) and optimizers (adam.hip) ----
+size_t loss_workspace_floats(int B);
+int launch_tcn_lp_loss(const float* alle, const int* perm, const int* iperm, float* dalle, float* ws, int B, int D, int l2dist,
+                       float l2w, float l1w, float tcnw, hipStream_t s);
+int launch_lang_infonce(const float* scores, const float* mask, float* dscore, float* ws, int B, float langw, hipStream_t s);
+int launch_loss_finalize(float* ws, int B, int have_lang, float* metrics, float l2w, float l1w, float tcnw, float langw,
+                         hipStream_t s);
+int launch_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2, double eps,
+                long long step, float grad_scale, hipStream_t s);
+int launch_sgd(float* p, const float* g, float* momentum_buf, long long n, double lr, double momentum, double dampening,
+               double weight_decay, int nesterov, long long step, float grad_scale, hipStream_t s);
+
+// ---- augmentation (augment.hip) ----
+int launch_crop_resize(const void* in, int in_is_u8, const int* boxes, float* out, long long N, int C, int Hi, int Wi, int Ho,
+                       int Wo, int frames_per_box, hipStream_t s);
+int launch_resize_crop(const void* in, int in_is_u8, float* out, long long N, int C, int Hi, int Wi, int full_Ho, int full_Wo,
+                       int top, int left, int Ho, int Wo, hipStream_t s);
+int launch_resize_crop_backward(const float* dout, float* din, long long N, int C, int Hi, int Wi, int full_Ho, int full_Wo, int top,
+                                int left, int Ho, int Wo, int accumulate, hipStream_t s);
+
+// ---- language-reward head (lang.hip) ----
+long long langrew_num_params(int D, int H, int LD);
+size_t langrew_ws_floats(int B, int D, int H, int LD);
+int langrew_forward(const float* alle, const float* feats, const int* perm, const float* params, float* scores, float* ws, int B,
+                    int D, int H, int LD, int dt, hipStream_t s);
+int langrew_backward(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, float* ws, int B, int D,
+                     int H, int LD, int accumulate, int dt, hipStream_t s);
+size_t langrew_call_ws_floats(int R, int D, int H, int LD);
+int langrew_call_forward(const float* e0, const float* eg, const float* le, const float* params, float* score, float* ws, int R,
+                         int D, int H, int LD, hipStream_t s);
+int langrew_call_backward(const float* dscore, const float* params, float* grads, float* de0, float* deg, float* dle, float* ws,
+                          int R, int D, int H, int LD, int accumulate, hipStream_t s);
 
 // ---- optional per-kernel-class HIP-event timing (bench.py roofline; off by default, zero cost when off) ----
 enum { KC_GEMM_WIDE = 0, KC_GEMM_NARROW = 1, KC_WGRAD_WIDE = 2, KC_WGRAD_NARROW = 3, KC_COUNT = 4 };

@@ -1,0 +1,80 @@
+// r3m_amd — internal interface of the encoder engine (engine.hip): the plan, its forward / backward, and the convolution launch
+// helpers that the C ABI (capi.hip) and the language head (lang.hip) call directly. Not installed; include/r3m_hip.h is the
+// public surface.
+#pragma once
+#include "common.h"
+
+namespace r3m {
+
+// torchvision's output size of a k x k / stride / pad layer, per dimension
+static inline int out_dim(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
+
+// One convolution over N images: input [N,Hi,Wi,Ci] NHWC, weights [Co][k][k][Ci], output [N,Ho(),Wo(),Co]
+struct ConvGeom {
+  int N, Hi, Wi, Ci, Co, k, stride, pad;
+  int Ho() const { return out_dim(Hi, k, stride, pad); }
+  int Wo() const { return out_dim(Wi, k, stride, pad); }
+  int M() const { return N * Ho() * Wo(); }                                  // rows of the forward GEMM
+  long long w_elems() const { return (long long)Co * k * k * Ci; }
+  int simple_rows() const { return (k == 1 && stride == 1 && pad == 0) ? 1 : 0; }
+};
+
+// EPI_BNRED request of a dgrad (conv_dgrad_launch): the result is the dz of a BatchNorm whose input is Y (same shape as dX);
+// partial rows -> `partial`, count -> rows_out
+struct BnRedArgs {
+  const float* Y;
+  const unsigned* bits;      // 1-bit ReLU mask of the BatchNorm(+residual) output, or null: recompute from Y, scale, shift
+  const float* scale;
+  const float* shift;
+  const float* mean;
+  float* partial;
+  int rows_out;              // partial rows written (all launches of the dgrad)
+};
+
+// ---- convolution launches ----
+// X / W / Y (and dY / Wt / dX / add0 / add1) are fp32 tensors, or bf16 tensors behind float-typed pointers when dt == DT_BF16
+int conv_forward_launch(const float* X, const float* W, float* Y, float* stats, const float* bias, const ConvGeom& c, int flags, int dt,
+                        hipStream_t s);
+// Inference forward (round 6): the convolution stores [relu]( acc * scale[co] + shift[co] [+ what `out` already holds] ) — eval-mode
+// BatchNorm, the residual join and the ReLU in the conv's own store (flags: EPI_AFFINE [| EPI_ACCUM] [| EPI_RELU]).
+int conv_forward_launch_affine(const float* X, const float* W, float* out, const float* scale, const float* shift, const ConvGeom& c,
+                               int flags, int dt, hipStream_t s);
+bool conv_forward_affine_fusable(const ConvGeom& c, int flags, int dt);   // whether that launch's kernel has these epilogues
+// dX[N,Hi,Wi,Ci] = dgrad of the convolution given dY[N,Ho,Wo,Co] and Wt[Ci][k*k][Co]; br: also the EPI_BNRED partials
+int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* add0, const float* add1, const unsigned* addbits,
+                      const ConvGeom& c, int flags, int dt, hipStream_t s, BnRedArgs* br = nullptr);
+int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, const ConvGeom& c, int accumulate, int dt,
+                      hipStream_t s);
+size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt);
+
+// ---- the plan ----
+struct Plan;
+struct FrameSource;   // augment_dev.h: raw clips + crop boxes
+Plan* plan_create(int size, int F, int dtype, int H, int W);
+void plan_destroy(Plan* P);
+// frames come either as [F,3,H,W] fp32 0..255 (x_nchw, crop == nullptr) or as raw clips + crop boxes (crop: rc / rctraj resampled
+// inside the stem pre-pass; 224 x 224 plans only)
+int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena, float* h_out,
+                 int training, hipStream_t s);
+int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
+                  int accumulate, hipStream_t s, float* dx, int dx_accumulate);
+int plan_out_dim(Plan* P);
+int plan_input_hw(Plan* P, int* H, int* W);
+int plan_num_convs(Plan* P);
+int plan_conv_info(Plan* P, int i, int* geo10);
+int plan_dtype(Plan* P);
+long long plan_num_params(Plan* P);
+long long plan_num_buffers(Plan* P);
+long long plan_arena_floats(Plan* P);
+int plan_num_tensors(Plan* P);
+int plan_tensor_info(Plan* P, int i, char* name, int cap, int* kind, long long* offset, int* ndim, int* shape4);
+int plan_stage_range(Plan* P, int stage, long long* off, long long* count);
+// per-plan options; each returns the old value
+int plan_set_bn_pair(Plan* P, int on);      // the two tail BatchNorms of a downsample block share their backward passes
+int plan_set_fuse_bnred(Plan* P, int on);   // 1 = BatchNorm-backward partials from the dgrad epilogues (EPI_BNRED), 0 = stand-alone reduce passes
+
+// ---- process-wide diagnostic switches (r3m_debug_set_*); each returns the old value ----
+int engine_set_generic_stem(int on);      // 1 = 224 x 224 frames run the general stem kernels too (tests, A/B)
+int engine_set_fused_inference(int on);   // 0 = inference forwards run the unfused eval sequence (A/B, tests)
+
+}  // namespace r3m

@@ -9,7 +9,11 @@
 // HBM layout: activations NHWC fp32 in ONE arena owned by the caller (offsets fixed at plan creation, sized for the
 // frame count F); parameters and gradients are two flat fp32 buffers in torchvision parameter order with conv weights
 // stored OHWI (= logical OIHW tensors with channels_last strides, so state-dict interchange needs no copy kernels).
-#include "common.h"
+//
+// File order: the layer table and Plan (layout, options, RunState) -> plan_create -> the convolution launch helpers of engine.h ->
+// Ctx (one call's view of plan + buffers) and the tile-counter guard -> forward (stem_forward, block_forward, block_forward_fused,
+// plan_forward) -> backward (BatchNorm / dgrad / wgrad helpers, SideStream, block_backward, stem_backward, plan_backward) -> accessors.
+#include "engine.h"
 #include "augment_dev.h"
 #ifndef R3M_BN_PAIR_DEFAULT
 #define R3M_BN_PAIR_DEFAULT 1     // A/B builds: tools/build_ab.sh none variant nopair -DR3M_BN_PAIR_DEFAULT=0
@@ -35,6 +39,7 @@ struct ConvSpec {
   long long coef_off;                     // arena: mean, invstd, scale, shift, c1, c2  (6*Co floats)
   int stats_rows;                         // row blocks of the forward GEMM (BatchNorm partials)
   long long wt_off = 0;                   // dgrad weight image [Ci][k*k][Co] inside the plan's Wt region (elements of the activation type)
+  ConvGeom geom(int F) const { return {F, Hi, Wi, Ci, Co, k, stride, pad}; }
 };
 
 struct BlockSpec {
@@ -56,12 +61,58 @@ struct TensorInfo {
   int ndim;
 };
 
+struct Ctx;
+
+// The opt-in side stream of a backward: wgrad(L) only needs dY_L and the saved activations, and nothing on the critical path needs its
+// result before the optimizer. It runs on a side stream, ordered by events so that it overlaps ONLY with the HBM-bound
+// BatchNorm-backward passes of the next layer down (reduce / apply: ~6 TB/s, no MFMA) and never with the MFMA-bound dgrad:
+//     main:  bn_bwd(L) -> [wait wgrad(L+1)] -> dgrad(L) -> bn_bwd(L-1) -> [wait wgrad(L)] -> dgrad(L-1) -> ...
+//     side:                                    wgrad(L)  (starts when dgrad(L) has finished)
+// A bandwidth-bound and a matrix-bound kernel share the CUs without stealing each other's bottleneck resource, and the
+// per-launch timings of the dominant kernel class (gather-GEMM on the main stream) stay unperturbed. Each stage ends with
+// a join. Off by default (probe builds: R3M_SIDE_STREAM=1 enables it, 2 = wgrad(L) runs beside dgrad(L)): measured neutral, see init().
+// Every method does nothing (wgrad_async: launches on the main stream) while it is off.
+struct SideStream {
+  int init();                                   // reads the mode once; creates the stream and events when it is on
+  void begin(hipStream_t s, bool have_grads) { main = s; on = mode && side && have_grads; }   // per plan_backward call
+  void restart() { pending[0] = pending[1] = false; }                                         // stage 0: nothing in flight
+  int mark_dy();                                // the side stream waits for what the main stream has enqueued so far (dY_L)
+  int wgrad_async(Ctx& c, const ConvSpec& L, const float* X, const float* dY, int ai);   // right AFTER dgrad(L) was enqueued; dY is A[ai]
+  int acquire(int ai);                          // before the main stream overwrites A[ai], the wgrad that last read it must be done
+  int wait_wgrads();                            // before an MFMA-bound kernel goes to the main stream: every wgrad in flight must have finished
+  int join();                                   // the main stream waits for everything on the side stream
+  void destroy();
+ private:
+  int mode = -1;
+  bool on = false;
+  hipStream_t main = nullptr, side = nullptr;
+  hipEvent_t ev_dy = nullptr, ev_wg[2] = {nullptr, nullptr}, ev_join = nullptr;
+  bool pending[2] = {false, false};             // a wgrad reading A0 / A1 is in flight
+};
+
+// What forward and backward change on a plan. Backward stages carry state from one r3m_resnet_backward call to the next (buffer
+// roles, the running output gradient and — with EPI_BNRED — BatchNorm partials waiting in the shared partial buffer for the NEXT
+// block). They are only valid in the order 0,1,2,3 after ONE forward.
+struct RunState {
+  int last_training = 1;
+  int last_crop = 0;        // the last forward read raw clips through crop boxes (r3m_resnet_forward_crop): no frames to differentiate
+  int stem_gen = 0;         // the last forward ran the general stem (stem_gen.hip): its backward must too (the normalised image layout)
+  int next_stage = -1;      // what the following backward call must begin with (0 = a backward may (re)start, -1 = no forward has run yet)
+  int roles[5] = {0, 1, 2, 3, 4};   // which G buffer is D (block output grad), A0 / A1 (dY, alternating), B, C: rotated per block
+  int a_next = 0;           // which of A0/A1 the next dY goes to
+  int dout_fused_rows = 0;  // > 0: the dgrad that wrote the running output gradient also wrote the BatchNorm-backward partials of the
+                            // block that consumes it next (EPI_BNRED): that many partial rows wait in the partial buffer
+  WtEntry* d_wt_tab = nullptr;      // device copies of wt_tab / wt_tile0, made at the first backward (plan creation needs no GPU)
+  int* d_wt_tile0 = nullptr;
+  SideStream side;
+};
+
+// Layout (set by plan_create; forward and backward see it const), two options, and the run state.
 struct Plan {
   int size, F, D;
   int H = 224, W = 224;   // input frames [F,3,H,W]
   int H1 = 112, W1 = 112; // stem output (conv1), the maxpool's input
   int Hp = 56, Wp = 56;   // maxpool output, layer1's input
-  int stem_gen = 0;       // the last forward ran the general stem (stem_gen.hip): its backward must too (the normalised image layout)
   int dtype = DT_F32;     // activation storage: fp32, or bf16 (bf16 conv operands, fp32 accumulation / statistics / gradients of weights)
   long long w16_off = 0;  // arena: bf16 image of the flat parameter buffer (DT_BF16 only)
   std::vector<ConvSpec> convs;
@@ -71,39 +122,21 @@ struct Plan {
   long long stage_param_begin[5];  // params of stem+layer1 | layer2 | layer3 | layer4 boundaries (see stage_range)
   // arena offsets (floats)
   long long col_off, P0_off, amax_off, partial_off, acc_off, wt_off, wgp_off;
-  long long ctr_off = 0;    // [convs][8] + [convs][4][8] unsigned: per-XCD tile queues of the persistent kernel — the forward launch of each conv, and the (up to four: stride-2 parity classes) backward launches
+  long long ctr_off = 0;    // per-XCD tile queues of the persistent kernel (TileCounters)
   long long G_off[5];     // gradient ping-pong buffers: D (block output grad), A0/A1 (dY, alternating), B, C
   long long E_off = -1;   // dY of a downsample block's downsample BatchNorm: written with the block's last BatchNorm backward (one pass
                           // for both, bn_backward_pair), read by the downsample dgrad / wgrad at the END of the block (-1: no such block)
   long long arena_floats = 0;
   long long gmax = 0;
-  int last_training = 1;
-  int last_crop = 0;      // the last forward read raw clips through crop boxes (r3m_resnet_forward_crop): no frames to differentiate
   long long gsc_off = 0;  // arena: [2][2048] BatchNorm parameter-gradient sums of a backward without parameter gradients (grads == NULL)
-  int gd = 0;             // which G buffer holds the running output-gradient between backward stages
-  // side stream: wgrad(L) runs concurrently with dgrad(L) (both only need dY_L), filling each other's tile-quantisation tails
-  hipStream_t side = nullptr;
-  hipEvent_t ev_dy = nullptr, ev_wg[2] = {nullptr, nullptr}, ev_join = nullptr;
-  bool wg_pending[2] = {false, false};
-  int a_next = 0;         // which of A0/A1 the next dY goes to
-  int roles[5] = {0, 1, 2, 3, 4};
-  bool bnred_init = false;
-  int fuse_bnred = 1;       // BatchNorm-backward partials from the producing dgrad's epilogue (EPI_BNRED); 0: stand-alone reduce pass
-  int dout_fused_rows = 0;  // > 0: the dgrad that wrote the running output gradient also wrote the BatchNorm-backward partials of the
-                            // block that consumes it next (EPI_BNRED): that many partial rows wait in the partial buffer
-  int use_side = -1;
-  int bn_pair = R3M_BN_PAIR_DEFAULT;   // the two tail BatchNorms of a downsample block share their backward passes (bn_backward_pair); 0: separate passes
-  // Backward stages carry state from one r3m_resnet_backward call to the next (buffer roles, the running output gradient and — with
-  // EPI_BNRED — BatchNorm partials waiting in the shared partial buffer for the NEXT block). They are only valid in the order
-  // 0,1,2,3 after ONE forward: next_stage is what the following call must begin with (0 = a backward may (re)start, -1 = no
-  // forward has run yet).
-  int next_stage = -1;
   // dgrad weight images of all layers, rebuilt by ONE launch at the start of each backward (launch_transpose_w_all)
   std::vector<WtEntry> wt_tab;
   std::vector<int> wt_tile0;
   long long wt_elems = 0;
-  WtEntry* d_wt_tab = nullptr;             // device copies, made at the first backward (plan creation needs no GPU)
-  int* d_wt_tile0 = nullptr;
+  // options (plan_set_*)
+  int fuse_bnred = 1;       // BatchNorm-backward partials from the producing dgrad's epilogue (EPI_BNRED); 0: stand-alone reduce pass
+  int bn_pair = R3M_BN_PAIR_DEFAULT;   // the two tail BatchNorms of a downsample block share their backward passes (bn_backward_pair); 0: separate passes
+  RunState run;
 };
 
 static long long align64(long long x) { return (x + 63) / 64 * 64; }
@@ -113,8 +146,8 @@ static int add_conv(Plan& P, const std::string& name, const std::string& bn, int
   ConvSpec c;
   c.name = name; c.bn_name = bn;
   c.Ci = Ci; c.Co = Co; c.k = k; c.stride = stride; c.pad = pad; c.Hi = Hi; c.Wi = Wi;
-  c.Ho = (Hi + 2 * pad - k) / stride + 1;
-  c.Wo = (Wi + 2 * pad - k) / stride + 1;
+  c.Ho = out_dim(Hi, k, stride, pad);
+  c.Wo = out_dim(Wi, k, stride, pad);
   c.w_off = P.n_params;
   P.n_params += (long long)Co * Ci * k * k;
   c.gamma_off = P.n_params; P.n_params += Co;
@@ -136,11 +169,10 @@ static int add_conv(Plan& P, const std::string& name, const std::string& bn, int
   return (int)P.convs.size() - 1;
 }
 
-static int g_generic_stem = 0;   // r3m_debug_set_generic_stem: 1 = 224 x 224 frames run the general stem kernels too (tests, A/B)
+static int g_generic_stem = 0;      // r3m_debug_set_generic_stem
 int engine_set_generic_stem(int on) { const int old = g_generic_stem; g_generic_stem = on ? 1 : 0; return old; }
-
-// torchvision's output size of a k x k / stride / pad layer, per dimension
-static int out_dim(int n, int k, int stride, int pad) { return (n + 2 * pad - k) / stride + 1; }
+static int g_fused_inference = 1;   // r3m_debug_set_fused_inference
+int engine_set_fused_inference(int on) { const int old = g_fused_inference; g_fused_inference = on ? 1 : 0; return old; }
 
 Plan* plan_create(int size, int F, int dtype, int H, int W) {
   if (size != 18 && size != 34 && size != 50) { set_last_error("resnet: unsupported size %d (18, 34, 50)", size); return nullptr; }
@@ -159,7 +191,11 @@ Plan* plan_create(int size, int F, int dtype, int H, int W) {
   P.H1 = out_dim(H, 7, 2, 3); P.W1 = out_dim(W, 7, 2, 3);
   P.Hp = out_dim(P.H1, 3, 2, 1); P.Wp = out_dim(P.W1, 3, 2, 1);
   const bool is224 = H == 224 && W == 224;
-  P.fuse_bnred = dtype == DT_F32 ? 1 : 0;   // see side_init(): measured gain for fp32 plans, measured loss for bf16 plans
+  // fp32 plans only: there the dgrad is MFMA-bound and the extra epilogue loads ride under other blocks' matrix work (A/B on one
+  // box, probe build: 343.0 / 341.7 ms -> 338.5 / 339.0 ms per ResNet-50 step). bf16 plans are HBM/epilogue-bound already and
+  // measured slightly SLOWER with it (ResNet-50 95.6 -> 96.2 ms, ResNet-34 97.0 -> 97.9 ms), so they keep the stand-alone reduce.
+  P.fuse_bnred = dtype == DT_F32 ? 1 : 0;
+  if (const int v = R3M_ENV_INT("R3M_BNRED", 1); v != 1) P.fuse_bnred = v == 2;   // probe builds: 0 = off everywhere, 2 = on for bf16 too
   const bool bottleneck = (size == 50);
   const int expansion = bottleneck ? 4 : 1;
   const int nblk[4] = {size == 18 ? 2 : 3, size == 18 ? 2 : 4, size == 18 ? 2 : 6, size == 18 ? 2 : 3};
@@ -310,23 +346,6 @@ Plan* plan_create(int size, int F, int dtype, int H, int W) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-struct Ctx {
-  Plan& P;
-  const float* params;
-  float* grads;
-  float* bufs;
-  float* arena;
-  hipStream_t s;
-  int training;
-  int accumulate;
-  int dt;
-  // where BatchNorm backward puts d gamma / d beta of layer L: the flat gradient buffer, or plan scratch when no parameter gradient
-  // is wanted (the sums themselves are still formed: train-mode dz needs c1 / c2 from the same pass)
-  float* dgamma(const ConvSpec& L) const { return grads ? grads + L.gamma_off : arena + P.gsc_off; }
-  float* dbeta(const ConvSpec& L) const { return grads ? grads + L.beta_off : arena + P.gsc_off + 2048; }
-  int bn_accumulate() const { return grads ? accumulate : 0; }
-};
-
 static void fill_taps_fwd(GatherGemmParams& g, int k, int pad) {
   int t = 0;
   for (int kh = 0; kh < k; ++kh)
@@ -336,64 +355,45 @@ static void fill_taps_fwd(GatherGemmParams& g, int k, int pad) {
   g.ntaps = t;
 }
 
-// X / W / Y (and dY / Wt / dX / add0 / add1, X / dY below) are fp32 tensors, or bf16 tensors behind float-typed pointers when dt == DT_BF16
-int conv_forward_launch(const float* X, const float* W, float* Y, float* stats, const float* bias, int N, int Hi, int Wi, int Ci,
-                        int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s) {
-  GatherGemmParams g;
+// the forward launch of convolution c; the caller adds the pointers its epilogue flags read (stats / bias, or bn_scale / bn_shift)
+static void fill_forward_params(GatherGemmParams& g, const float* X, const float* W, float* out, const ConvGeom& c, int flags, int dt) {
   memset(&g, 0, sizeof g);
   g.dtype = dt;
-  const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
-  g.A = X; g.B = W; g.out = Y; g.stats = stats; g.bias = bias;
-  g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ci = Ci;
-  g.Hg = Ho; g.Wg = Wo; g.Ho = Ho; g.Wo = Wo; g.Nc = Co;
-  g.is = stride; g.os = 1; g.ooy = 0; g.oox = 0;
-  g.M = N * Ho * Wo;
-  g.T = k * k;
-  fill_taps_fwd(g, k, pad);
+  g.A = X; g.B = W; g.out = out;
+  g.N = c.N; g.Hi = c.Hi; g.Wi = c.Wi; g.Ci = c.Ci;
+  g.Hg = c.Ho(); g.Wg = c.Wo(); g.Ho = c.Ho(); g.Wo = c.Wo(); g.Nc = c.Co;
+  g.is = c.stride; g.os = 1; g.ooy = 0; g.oox = 0;
+  g.M = c.M();
+  g.T = c.k * c.k;
+  fill_taps_fwd(g, c.k, c.pad);
   g.flags = flags;
-  g.simple_rows = (k == 1 && stride == 1 && pad == 0) ? 1 : 0;
+  g.simple_rows = c.simple_rows();
+}
+int conv_forward_launch(const float* X, const float* W, float* Y, float* stats, const float* bias, const ConvGeom& c, int flags, int dt,
+                        hipStream_t s) {
+  GatherGemmParams g;
+  fill_forward_params(g, X, W, Y, c, flags, dt);
+  g.stats = stats; g.bias = bias;
   return launch_gather_gemm(g, s);
 }
-
-// Inference forward (round 6): the convolution stores [relu]( acc * scale[co] + shift[co] [+ what `out` already holds] ) — eval-mode
-// BatchNorm, the residual join and the ReLU in the conv's own store (flags: EPI_AFFINE [| EPI_ACCUM] [| EPI_RELU]).
-static void fill_forward_params(GatherGemmParams& g, const float* X, const float* W, float* out, const float* scale, const float* shift,
-                                int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt) {
-  memset(&g, 0, sizeof g);
-  g.dtype = dt;
-  const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
-  g.A = X; g.B = W; g.out = out; g.bn_scale = scale; g.bn_shift = shift;
-  g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ci = Ci;
-  g.Hg = Ho; g.Wg = Wo; g.Ho = Ho; g.Wo = Wo; g.Nc = Co;
-  g.is = stride; g.os = 1; g.ooy = 0; g.oox = 0;
-  g.M = N * Ho * Wo;
-  g.T = k * k;
-  fill_taps_fwd(g, k, pad);
-  g.flags = flags;
-  g.simple_rows = (k == 1 && stride == 1 && pad == 0) ? 1 : 0;
+int conv_forward_launch_affine(const float* X, const float* W, float* out, const float* scale, const float* shift, const ConvGeom& c,
+                               int flags, int dt, hipStream_t s) {
+  GatherGemmParams g;
+  fill_forward_params(g, X, W, out, c, flags, dt);
+  g.bn_scale = scale; g.bn_shift = shift;
+  return launch_gather_gemm(g, s);
 }
-bool conv_forward_affine_fusable(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt) {
+bool conv_forward_affine_fusable(const ConvGeom& c, int flags, int dt) {
   GatherGemmParams g;
   static const float one = 1.f;   // (the query looks at shapes, flags and whether the coefficient pointers are set — never dereferenced)
-  fill_forward_params(g, nullptr, nullptr, nullptr, &one, &one, N, Hi, Wi, Ci, Co, k, stride, pad, flags, dt);
+  fill_forward_params(g, nullptr, nullptr, nullptr, c, flags, dt);
+  g.bn_scale = g.bn_shift = &one;
   return gather_gemm_fuses_affine(g);
 }
-int conv_forward_launch_affine(const float* X, const float* W, float* out, const float* scale, const float* shift, int N, int Hi, int Wi,
-                               int Ci, int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s) {
-  GatherGemmParams g;
-  fill_forward_params(g, X, W, out, scale, shift, N, Hi, Wi, Ci, Co, k, stride, pad, flags, dt);
-  return launch_gather_gemm(g, s);
-}
 
-// dX[N,Hi,Wi,Ci] = dgrad of conv(k, stride, pad) given dY[N,Ho,Wo,Co] and Wt[Ci][k*k][Co]
 int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* add0, const float* add1, const unsigned* addbits,
-                      int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s) {
-  return conv_dgrad_launch_br(dY, Wt, dX, add0, add1, addbits, N, Hi, Wi, Ci, Co, k, stride, pad, flags, dt, nullptr, s);
-}
-int conv_dgrad_launch_br(const float* dY, const float* Wt, float* dX, const float* add0, const float* add1,
-                         const unsigned* addbits, int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags,
-                         int dt, BnRedArgs* br, hipStream_t s) {
-  const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
+                      const ConvGeom& c, int flags, int dt, hipStream_t s, BnRedArgs* br) {
+  const int N = c.N, Hi = c.Hi, Wi = c.Wi, k = c.k, stride = c.stride, pad = c.pad;
   R3M_REQUIRE(stride == 1 || stride == 2, "dgrad: stride %d", stride);
   GatherGemmParams g;
   memset(&g, 0, sizeof g);
@@ -405,8 +405,8 @@ int conv_dgrad_launch_br(const float* dY, const float* Wt, float* dX, const floa
     br->rows_out = 0;
   }
   g.A = dY; g.B = Wt; g.out = dX; g.add0 = add0; g.add1 = add1; g.addbits = addbits;
-  g.N = N; g.Hi = Ho; g.Wi = Wo; g.Ci = Co;   // the GEMM "input" is dY
-  g.Ho = Hi; g.Wo = Wi; g.Nc = Ci;
+  g.N = N; g.Hi = c.Ho(); g.Wi = c.Wo(); g.Ci = c.Co;   // the GEMM "input" is dY
+  g.Ho = Hi; g.Wo = Wi; g.Nc = c.Ci;
   g.is = 1; g.T = k * k; g.flags = flags;
   if (stride == 1) {
     g.Hg = Hi; g.Wg = Wi; g.os = 1; g.ooy = g.oox = 0;
@@ -424,307 +424,282 @@ int conv_dgrad_launch_br(const float* dY, const float* Wt, float* dX, const floa
   // stride 2: one launch per output parity class; class (py,px) only sees taps with (py+pad-kh), (px+pad-kw) even
   for (int py = 0; py < 2; ++py)
     for (int px = 0; px < 2; ++px) {
-      GatherGemmParams c = g;
-      c.Hg = (Hi - py + 1) / 2; c.Wg = (Wi - px + 1) / 2;
-      if (c.Hg <= 0 || c.Wg <= 0) continue;
-      c.os = 2; c.ooy = py; c.oox = px;
-      c.M = N * c.Hg * c.Wg;
+      GatherGemmParams q = g;
+      q.Hg = (Hi - py + 1) / 2; q.Wg = (Wi - px + 1) / 2;
+      if (q.Hg <= 0 || q.Wg <= 0) continue;
+      q.os = 2; q.ooy = py; q.oox = px;
+      q.M = N * q.Hg * q.Wg;
       int t = 0;
       for (int kh = 0; kh < k; ++kh) {
         if ((py + pad - kh) & 1) continue;
         for (int kw = 0; kw < k; ++kw) {
           if ((px + pad - kw) & 1) continue;
-          c.dy[t] = (signed char)((py + pad - kh) / 2); c.dx[t] = (signed char)((px + pad - kw) / 2);
-          c.wt[t] = (unsigned char)(kh * k + kw); ++t;
+          q.dy[t] = (signed char)((py + pad - kh) / 2); q.dx[t] = (signed char)((px + pad - kw) / 2);
+          q.wt[t] = (unsigned char)(kh * k + kw); ++t;
         }
       }
-      c.ntaps = t;
-      c.simple_rows = 0;
+      q.ntaps = t;
+      q.simple_rows = 0;
       R3M_REQUIRE(!(br && t == 0), "dgrad: EPI_BNRED on a parity class without taps (1x1 stride-2) is not supported");
       if (t == 0 && (flags & EPI_ACCUM) && !(flags & EPI_MASKED_ADD)) continue;  // nothing to add
       if (br) {                                          // every parity class appends its own partial rows
-        c.stats = br->partial + (long long)br->rows_out * 2 * c.Nc;
-        br->rows_out += bnred_partial_rows(c.M);
+        q.stats = br->partial + (long long)br->rows_out * 2 * q.Nc;
+        br->rows_out += bnred_partial_rows(q.M);
       }
-      if (int e = launch_gather_gemm(c, s)) return e;
+      if (int e = launch_gather_gemm(q, s)) return e;
     }
   return 0;
 }
 
-int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, int N, int Hi, int Wi, int Ci, int Co, int k,
-                      int stride, int pad, int accumulate, int dt, hipStream_t s) {
+static int wgrad_split(const ConvGeom& c, int dt) {
+  return dt == DT_BF16 ? wgrad_bf16_pick_split(c.M(), c.Co, c.Ci, c.k * c.k) : wgrad_pick_split(c.M(), c.Co, c.Ci, c.k * c.k);
+}
+int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, const ConvGeom& c, int accumulate, int dt,
+                      hipStream_t s) {
   WgradParams w;
   memset(&w, 0, sizeof w);
   w.dtype = dt;
-  w.Ho = (Hi + 2 * pad - k) / stride + 1; w.Wo = (Wi + 2 * pad - k) / stride + 1;
+  w.Ho = c.Ho(); w.Wo = c.Wo();
   w.dY = dY; w.X = X; w.out = partial_ws;
-  w.N = N; w.Hi = Hi; w.Wi = Wi; w.Ci = Ci; w.Co = Co;
-  w.KH = w.KW = k; w.stride = stride; w.pad = pad;
-  w.M = N * w.Ho * w.Wo;
-  w.simple_rows = (k == 1 && stride == 1 && pad == 0) ? 1 : 0;
-  if (dt == DT_BF16) {
-    const int split = wgrad_bf16_pick_split(w.M, Co, Ci, k * k);
-    if (int e = launch_wgrad_bf16(w, split, s)) return e;
-    return launch_wgrad_reduce(partial_ws, dW, (long long)Co * k * k * Ci, split, accumulate, s);
-  }
-  const int split = wgrad_pick_split(w.M, Co, Ci, k * k);
-  if (int e = launch_wgrad(w, split, s)) return e;
-  return launch_wgrad_reduce(partial_ws, dW, (long long)Co * k * k * Ci, split, accumulate, s);
+  w.N = c.N; w.Hi = c.Hi; w.Wi = c.Wi; w.Ci = c.Ci; w.Co = c.Co;
+  w.KH = w.KW = c.k; w.stride = c.stride; w.pad = c.pad;
+  w.M = c.M();
+  w.simple_rows = c.simple_rows();
+  const int split = wgrad_split(c, dt);
+  if (int e = dt == DT_BF16 ? launch_wgrad_bf16(w, split, s) : launch_wgrad(w, split, s)) return e;
+  return launch_wgrad_reduce(partial_ws, dW, c.w_elems(), split, accumulate, s);
 }
+size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt) { return (size_t)wgrad_split(c, dt) * c.Co * c.k * c.k * c.Ci; }
 
-size_t conv_wgrad_ws_floats(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dt) {
-  const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
-  const int split = dt == DT_BF16 ? wgrad_bf16_pick_split(N * Ho * Wo, Co, Ci, k * k) : wgrad_pick_split(N * Ho * Wo, Co, Ci, k * k);
-  return (size_t)split * Co * k * k * Ci;
-}
-
-static int g_fused_inference = 1;   // r3m_debug_set_fused_inference: 0 = inference forwards run the unfused eval sequence (A/B, tests)
-int engine_set_fused_inference(int on) { const int old = g_fused_inference; g_fused_inference = on ? 1 : 0; return old; }
-
+// ---------------------------------------------------------------------------------------------------------
 #define TRY(x)              \
   do {                      \
     if (int e_ = (x)) return e_; \
   } while (0)
 
-static float* coef(Ctx& c, const ConvSpec& L, int which) { return c.arena + L.coef_off + (long long)which * L.Co; }
+// one forward or backward call: the plan's layout (read-only), its run state, and the caller's buffers
+struct Ctx {
+  const Plan& P;
+  RunState& R;
+  const float* params;
+  float* grads;
+  float* bufs;
+  float* arena;
+  hipStream_t s;
+  int training;
+  int accumulate;
+  int dt;
+  // where BatchNorm backward puts d gamma / d beta of layer L: the flat gradient buffer, or plan scratch when no parameter gradient
+  // is wanted (the sums themselves are still formed: train-mode dz needs c1 / c2 from the same pass)
+  float* dgamma(const ConvSpec& L) const { return grads ? grads + L.gamma_off : arena + P.gsc_off; }
+  float* dbeta(const ConvSpec& L) const { return grads ? grads + L.beta_off : arena + P.gsc_off + 2048; }
+  int bn_accumulate() const { return grads ? accumulate : 0; }
+  float* partial() const { return arena + P.partial_off; }
+  double* acc() const { return reinterpret_cast<double*>(arena + P.acc_off); }
+  float* coef(const ConvSpec& L, int which) const { return arena + L.coef_off + (long long)which * L.Co; }
+  // gradient buffer in role r (0 = D, 1 / 2 = A0 / A1, 3 = B, 4 = C), and the A buffer the next dY goes to
+  float* G(int r) const { return arena + P.G_off[R.roles[r]]; }
+  float* next_A(int* ai) const { *ai = R.a_next; R.a_next ^= 1; return G(1 + *ai); }
+};
 
-// conv -> (training: batch statistics -> coefficients | eval: running statistics -> coefficients)
-static int conv_bn_coeffs(Ctx& c, const ConvSpec& L, const float* X, const float* W, int Ci_eff, int k_eff, int stride_eff,
-                          int pad_eff, int Hi_eff, int Wi_eff, int N_eff) {
-  Plan& P = c.P;
-  float* Y = c.arena + L.Y_off;
-  float* partial = c.arena + P.partial_off;
-  double* acc = reinterpret_cast<double*>(c.arena + P.acc_off);
-  gg_set_tile_counters(reinterpret_cast<unsigned*>(c.arena + P.ctr_off) + (&L - P.convs.data()) * 8);
-  {
-    // the counters are handed to "the next launch of this thread": if the launcher returns before it reaches launch_gather_gemm
-    // (a failed requirement), nothing later on this thread may inherit them
-    struct DropCounters { ~DropCounters() { gg_set_tile_counters(nullptr, 0); } } drop;
-    TRY(conv_forward_launch(X, W, Y, partial, nullptr, N_eff, Hi_eff, Wi_eff, Ci_eff, L.Co, k_eff, stride_eff, pad_eff,
-                            c.training ? EPI_STATS : 0, c.dt, c.s));
+// Tile queues of the persistent kernel (conv_pw.hip) for the launches of layer L: the arena holds [convs][8] counters for the forward
+// launch of each conv, then [convs][4][8] for its (up to four: stride-2 parity classes) backward launches; each set serves one launch
+// and is zeroed at the top of its pass. The counters are handed to "the next launch of this thread": if the launcher returns before it
+// reaches launch_gather_gemm (a failed requirement), nothing later on this thread may inherit them, so the guard takes them back (sets
+// a layer did not use stay unused).
+struct TileCounters {
+  enum Pass { FORWARD = 0, BACKWARD = 1 };
+  static unsigned* slot(const Ctx& c, Pass pass, size_t layer) {
+    return reinterpret_cast<unsigned*>(c.arena + c.P.ctr_off) + (pass == FORWARD ? layer : c.P.convs.size() + 4 * layer) * 8;
   }
-  const float* gamma = c.params + L.gamma_off;
-  const float* beta = c.params + L.beta_off;
-  if (c.training) {
-    const long long count = (long long)P.F * L.Ho * L.Wo;
-    TRY(launch_bn_stats_reduce(partial, L.stats_rows, L.Co, acc, c.s));
-    TRY(launch_bn_finalize_rows(acc, L.stats_rows, count, gamma, beta, c.bufs + L.rm_off, c.bufs + L.rv_off, 0.1f, 1e-5f,
-                                coef(c, L, 0), coef(c, L, 1), coef(c, L, 2), coef(c, L, 3), L.Co, c.s));
-  } else {
-    TRY(launch_bn_eval_coeffs(gamma, beta, c.bufs + L.rm_off, c.bufs + L.rv_off, 1e-5f, coef(c, L, 0), coef(c, L, 1),
-                              coef(c, L, 2), coef(c, L, 3), L.Co, c.s));
+  static int reset(const Ctx& c, Pass pass) {
+    if (hipMemsetAsync(slot(c, pass, 0), 0, (pass == FORWARD ? 1 : 4) * c.P.convs.size() * 8 * sizeof(unsigned), c.s) != hipSuccess) {
+      set_last_error("resnet_%s: cannot reset the tile queues", pass == FORWARD ? "forward" : "backward");
+      return 1;
+    }
+    return 0;
   }
-  return 0;
-}
+  TileCounters(const Ctx& c, Pass pass, const ConvSpec& L) { gg_set_tile_counters(slot(c, pass, &L - c.P.convs.data()), pass == FORWARD ? 1 : 4); }
+  ~TileCounters() { gg_set_tile_counters(nullptr, 0); }
+};
 
+// ---- forward ------------------------------------------------------------------------------------------------
 // forward weight operand of layer L: the fp32 master, or its slice of the bf16 image made at the top of plan_forward
 static const float* fwd_weights(Ctx& c, const ConvSpec& L) {
   if (c.dt != DT_BF16) return c.params + L.w_off;
   return reinterpret_cast<const float*>(reinterpret_cast<const char*>(c.arena + c.P.w16_off) + L.w_off * 2);
 }
 
+// training: the statistics partials a forward launch left (L.stats_rows rows) -> batch coefficients (+ running-statistics update);
+// eval / inference: running statistics -> coefficients
+static int bn_forward_coeffs(Ctx& c, const ConvSpec& L) {
+  const float* gamma = c.params + L.gamma_off;
+  const float* beta = c.params + L.beta_off;
+  if (!c.training)
+    return launch_bn_eval_coeffs(gamma, beta, c.bufs + L.rm_off, c.bufs + L.rv_off, 1e-5f, c.coef(L, 0), c.coef(L, 1), c.coef(L, 2),
+                                 c.coef(L, 3), L.Co, c.s);
+  TRY(launch_bn_stats_reduce(c.partial(), L.stats_rows, L.Co, c.acc(), c.s));
+  return launch_bn_finalize_rows(c.acc(), L.stats_rows, (long long)c.P.F * L.Ho * L.Wo, gamma, beta, c.bufs + L.rm_off, c.bufs + L.rv_off,
+                                 0.1f, 1e-5f, c.coef(L, 0), c.coef(L, 1), c.coef(L, 2), c.coef(L, 3), L.Co, c.s);
+}
+
+// conv -> BatchNorm coefficients (the raw output stays in Y)
 static int conv_bn(Ctx& c, const ConvSpec& L, const float* X) {
-  return conv_bn_coeffs(c, L, X, fwd_weights(c, L), L.Ci, L.k, L.stride, L.pad, L.Hi, L.Wi, c.P.F);
+  {
+    TileCounters tc(c, TileCounters::FORWARD, L);
+    TRY(conv_forward_launch(X, fwd_weights(c, L), c.arena + L.Y_off, c.partial(), nullptr, L.geom(c.P.F), c.training ? EPI_STATS : 0, c.dt,
+                            c.s));
+  }
+  return bn_forward_coeffs(c, L);
 }
 
-int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena,
-                     float* h_out, int training, hipStream_t s);
-int plan_forward(Plan& P, const float* x_nchw, const float* params, float* bufs, float* arena, float* h_out, int training,
-                 hipStream_t s) {
-  return plan_forward_src(P, x_nchw, nullptr, params, bufs, arena, h_out, training, s);
+// x/255 -> Normalize -> conv1 7x7/2 straight from the NCHW frames (csrc/conv.hip stem_fwd_kernel) -> BatchNorm + ReLU + MaxPool
+static int stem_forward(Ctx& c, const float* x_nchw, const FrameSource* crop) {
+  const Plan& P = c.P;
+  const int F = P.F, dt = c.dt;
+  const ConvSpec& L0 = P.convs[0];
+  // frames other than 224 x 224 (and 224 under r3m_debug_set_generic_stem) run the general stem kernels (stem_gen.hip)
+  const bool gen = !crop && (P.H != 224 || P.W != 224 || g_generic_stem);
+  c.R.stem_gen = gen ? 1 : 0;
+  // normalised, channel-interleaved copy of the frames (0.6 MB/frame): read by the stem forward now and by its weight
+  // gradient in backward (the caller's tensor may be gone by then)
+  float* xn = c.arena + P.col_off;
+  if (gen) {
+    TRY(launch_stem_prep_gen(x_nchw, xn, F, P.H, P.W, dt, c.s));
+  } else if (crop) {
+    if (dt == DT_BF16) TRY(launch_stem_prep16_crop(*crop, xn, F, c.s));
+    else TRY(launch_stem_prep_crop(*crop, xn, F, c.s));
+  } else if (dt == DT_BF16) {
+    TRY(launch_stem_prep16(x_nchw, xn, F, c.s));
+  } else {
+    TRY(launch_stem_prep(x_nchw, xn, F, c.s));
+  }
+  const float* w = c.params + L0.w_off;
+  float* Y = c.arena + L0.Y_off;
+  float* stats = c.training ? c.partial() : nullptr;
+  if (gen) TRY(launch_stem_fwd_gen(xn, w, Y, stats, F, P.H, P.W, dt, c.s));
+  else if (dt == DT_BF16) TRY(launch_stem_fwd16(xn, w, Y, stats, F, c.s));
+  else TRY(launch_stem_fwd(xn, w, Y, stats, F, dt, c.s));
+  TRY(bn_forward_coeffs(c, L0));
+  // BatchNorm + ReLU + MaxPool in one pass over Y0
+  return launch_bn_relu_maxpool_fwd(Y, c.coef(L0, 2), c.coef(L0, 3), c.arena + P.P0_off, reinterpret_cast<unsigned char*>(c.arena + P.amax_off),
+                                    F, P.H1, P.W1, 64, dt, c.s);
 }
 
-// frames come either as [F,3,224,224] fp32 0..255 (x_nchw) or as raw clips + crop boxes (crop: rc / rctraj resampled inside the
-// stem pre-pass)
-int plan_forward_src(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena,
-                     float* h_out, int training, hipStream_t s) {
+// One residual block, unfused: every conv leaves its raw output and coefficients, bn_act_fwd makes the activations and the block
+// output (+ its [z > 0] bits for backward when mask != null). Writes B's output buffer.
+static int block_forward(Ctx& c, const BlockSpec& B, const float* Xin, unsigned* mask) {
+  const Plan& P = c.P;
+  const float* cur = Xin;
+  for (int j = 0; j < B.nconv; ++j) {
+    const ConvSpec& L = P.convs[B.conv[j]];
+    TRY(conv_bn(c, L, cur));
+    if (j < B.nconv - 1) {
+      TRY(launch_bn_act_fwd(c.arena + L.Y_off, c.coef(L, 2), c.coef(L, 3), nullptr, nullptr, nullptr, c.arena + L.Z_off,
+                            (long long)P.F * L.Ho * L.Wo, L.Co, 1, nullptr, c.dt, c.s));
+      cur = c.arena + L.Z_off;
+    }
+  }
+  const ConvSpec& LL = P.convs[B.conv[B.nconv - 1]];
+  const long long rows = (long long)P.F * B.Ho * B.Wo;
+  if (B.ds < 0)
+    return launch_bn_act_fwd(c.arena + LL.Y_off, c.coef(LL, 2), c.coef(LL, 3), Xin, nullptr, nullptr, c.arena + B.out_off, rows, B.Co, 1,
+                             mask, c.dt, c.s);
+  const ConvSpec& Ld = P.convs[B.ds];
+  TRY(conv_bn(c, Ld, Xin));
+  return launch_bn_act_fwd(c.arena + LL.Y_off, c.coef(LL, 2), c.coef(LL, 3), c.arena + Ld.Y_off, c.coef(Ld, 2), c.coef(Ld, 3),
+                           c.arena + B.out_off, rows, B.Co, 1, mask, c.dt, c.s);
+}
+
+// Inference: every convolution of the block stores its activated output itself — inner convs relu(bn(conv)), the downsample conv
+// bn(conv), the last conv relu(bn(conv) + residual) accumulating ONTO the residual (the block input, in place, or the downsample
+// result): no raw conv output, no bn_act_fwd pass, no mask bits. A block any of whose launches runs a kernel without these
+// epilogues (odd shapes; never a ResNet layer) takes the unfused sequence instead.
+static bool block_fusable(Ctx& c, const BlockSpec& B) {
+  bool fus = true;
+  for (int j = 0; j < B.nconv; ++j)
+    fus = fus && conv_forward_affine_fusable(c.P.convs[B.conv[j]].geom(c.P.F),
+                                             j < B.nconv - 1 ? (EPI_AFFINE | EPI_RELU) : (EPI_AFFINE | EPI_ACCUM | EPI_RELU), c.dt);
+  if (B.ds >= 0) fus = fus && conv_forward_affine_fusable(c.P.convs[B.ds].geom(c.P.F), EPI_AFFINE, c.dt);
+  return fus;
+}
+static int conv_bn_fused(Ctx& c, const ConvSpec& L, const float* X, float* out, int flags) {
+  TRY(bn_forward_coeffs(c, L));
+  TileCounters tc(c, TileCounters::FORWARD, L);
+  return conv_forward_launch_affine(X, fwd_weights(c, L), out, c.coef(L, 2), c.coef(L, 3), L.geom(c.P.F), flags, c.dt, c.s);
+}
+// *out: where the block's output is (the block input, or the downsample conv's Y)
+static int block_forward_fused(Ctx& c, const BlockSpec& B, float* Xin, float** out) {
+  const Plan& P = c.P;
+  const float* cur = Xin;
+  for (int j = 0; j < B.nconv - 1; ++j) {
+    const ConvSpec& L = P.convs[B.conv[j]];
+    TRY(conv_bn_fused(c, L, cur, c.arena + L.Z_off, EPI_AFFINE | EPI_RELU));
+    cur = c.arena + L.Z_off;
+  }
+  float* res = Xin;       // identity block: the sum replaces the block input
+  if (B.ds >= 0) {
+    const ConvSpec& Ld = P.convs[B.ds];
+    res = c.arena + Ld.Y_off;
+    TRY(conv_bn_fused(c, Ld, Xin, res, EPI_AFFINE));
+  }
+  *out = res;
+  return conv_bn_fused(c, P.convs[B.conv[B.nconv - 1]], cur, res, EPI_AFFINE | EPI_ACCUM | EPI_RELU);
+}
+
+int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena, float* h_out,
+                 int training, hipStream_t s) {
   // training: 1 = batch statistics (+ running-statistics update), 0 = running statistics with everything a backward needs kept,
   // 2 = INFERENCE (round 6): running statistics, nothing kept — BatchNorm, residual join and ReLU ride in the convolutions' stores
   const bool infer = training == 2;
   if (infer) training = 0;
-  Ctx c{P, params, nullptr, bufs, arena, s, training, 0, P.dtype};
+  Ctx c{P, P.run, params, nullptr, bufs, arena, s, training, 0, P.dtype};
   R3M_REQUIRE(!crop || (P.H == 224 && P.W == 224), "resnet_forward_crop: the crops are 224 x 224 but this plan takes %d x %d frames "
               "(create it for 224 x 224)", P.H, P.W);
-  P.last_training = training;
-  P.last_crop = crop ? 1 : 0;
-  P.next_stage = infer ? -3 : 0;   // a new forward invalidates whatever an unfinished backward left behind (-3: nothing to differentiate)
-  P.dout_fused_rows = 0;
-  const int F = P.F;
-  const int dt = P.dtype;
-  // tile queues of this pass's persistent-kernel launches (conv_pw.hip): 8 counters per conv, zeroed here, each used by one launch
-  if (hipMemsetAsync(arena + P.ctr_off, 0, P.convs.size() * 8 * sizeof(unsigned), s) != hipSuccess) {
-    set_last_error("resnet_forward: cannot reset the tile queues");
-    return 1;
-  }
-  if (dt == DT_BF16) TRY(launch_convert_bf16(params, arena + P.w16_off, P.n_params, s));   // bf16 image of every weight (45 MB for ResNet-50)
-  // ---- stem: x/255 -> Normalize -> conv1 7x7/2 straight from the NCHW frames (csrc/conv.hip stem_fwd_kernel) ----
-  const ConvSpec& L0 = P.convs[0];
-  // frames other than 224 x 224 (and 224 under r3m_debug_set_generic_stem) run the general stem kernels (stem_gen.hip)
-  const bool gen = !crop && (P.H != 224 || P.W != 224 || g_generic_stem);
-  P.stem_gen = gen ? 1 : 0;
-  // normalised, channel-interleaved copy of the frames (0.6 MB/frame): read by the stem forward now and by its weight
-  // gradient in backward (the caller's tensor may be gone by then)
-  if (gen) {
-    TRY(launch_stem_prep_gen(x_nchw, arena + P.col_off, F, P.H, P.W, dt, s));
-  } else if (crop) {
-    if (dt == DT_BF16) TRY(launch_stem_prep16_crop(*crop, arena + P.col_off, F, s));
-    else TRY(launch_stem_prep_crop(*crop, arena + P.col_off, F, s));
-  } else if (dt == DT_BF16) {
-    TRY(launch_stem_prep16(x_nchw, arena + P.col_off, F, s));
-  } else {
-    TRY(launch_stem_prep(x_nchw, arena + P.col_off, F, s));
-  }
-  {
-    float* partial = arena + P.partial_off;
-    double* acc = reinterpret_cast<double*>(arena + P.acc_off);
-    if (gen) TRY(launch_stem_fwd_gen(arena + P.col_off, params + L0.w_off, arena + L0.Y_off, training ? partial : nullptr, F, P.H, P.W, dt, s));
-    else if (dt == DT_BF16) TRY(launch_stem_fwd16(arena + P.col_off, params + L0.w_off, arena + L0.Y_off, training ? partial : nullptr, F, s));
-    else TRY(launch_stem_fwd(arena + P.col_off, params + L0.w_off, arena + L0.Y_off, training ? partial : nullptr, F, dt, s));
-    if (training) {
-      TRY(launch_bn_stats_reduce(partial, L0.stats_rows, 64, acc, s));
-      TRY(launch_bn_finalize_rows(acc, L0.stats_rows, (long long)F * L0.Ho * L0.Wo, params + L0.gamma_off, params + L0.beta_off,
-                                  bufs + L0.rm_off, bufs + L0.rv_off, 0.1f, 1e-5f, coef(c, L0, 0), coef(c, L0, 1), coef(c, L0, 2),
-                                  coef(c, L0, 3), 64, s));
-    } else {
-      TRY(launch_bn_eval_coeffs(params + L0.gamma_off, params + L0.beta_off, bufs + L0.rm_off, bufs + L0.rv_off, 1e-5f,
-                                coef(c, L0, 0), coef(c, L0, 1), coef(c, L0, 2), coef(c, L0, 3), 64, s));
-    }
-  }
-  // BatchNorm + ReLU + MaxPool in one pass over Y0
-  TRY(launch_bn_relu_maxpool_fwd(arena + L0.Y_off, coef(c, L0, 2), coef(c, L0, 3), arena + P.P0_off,
-                                 reinterpret_cast<unsigned char*>(arena + P.amax_off), F, P.H1, P.W1, 64, dt, s));
-  // ---- residual stages ----
-  if (infer && g_fused_inference) {
-    // Inference: per block, every convolution stores its activated output itself — inner convs relu(bn(conv)), the downsample conv
-    // bn(conv), the last conv relu(bn(conv) + residual) accumulating ONTO the residual (the block input, in place, or the downsample
-    // result): no raw conv output, no bn_act_fwd pass, no mask bits. A block any of whose launches runs a kernel without these
-    // epilogues (odd shapes; never a ResNet layer) takes the unfused sequence below instead.
-    const float* cur_in = arena + P.blocks[0].in_off;
-    for (const BlockSpec& B : P.blocks) {
-      const int nlast = B.conv[B.nconv - 1];
-      bool fus = true;
-      for (int j = 0; j < B.nconv; ++j) {
-        const ConvSpec& L = P.convs[B.conv[j]];
-        const int fl = j < B.nconv - 1 ? (EPI_AFFINE | EPI_RELU) : (EPI_AFFINE | EPI_ACCUM | EPI_RELU);
-        fus = fus && conv_forward_affine_fusable(F, L.Hi, L.Wi, L.Ci, L.Co, L.k, L.stride, L.pad, fl, dt);
-      }
-      if (B.ds >= 0) {
-        const ConvSpec& Ld = P.convs[B.ds];
-        fus = fus && conv_forward_affine_fusable(F, Ld.Hi, Ld.Wi, Ld.Ci, Ld.Co, Ld.k, Ld.stride, Ld.pad, EPI_AFFINE, dt);
-      }
-      auto coeffs = [&](const ConvSpec& L) {
-        return launch_bn_eval_coeffs(params + L.gamma_off, params + L.beta_off, bufs + L.rm_off, bufs + L.rv_off, 1e-5f, coef(c, L, 0),
-                                     coef(c, L, 1), coef(c, L, 2), coef(c, L, 3), L.Co, s);
-      };
-      auto fused = [&](const ConvSpec& L, const float* X, float* out, int flags) {
-        gg_set_tile_counters(reinterpret_cast<unsigned*>(arena + P.ctr_off) + (&L - P.convs.data()) * 8);
-        struct DropCounters { ~DropCounters() { gg_set_tile_counters(nullptr, 0); } } drop;
-        return conv_forward_launch_affine(X, fwd_weights(c, L), out, coef(c, L, 2), coef(c, L, 3), F, L.Hi, L.Wi, L.Ci, L.Co, L.k,
-                                          L.stride, L.pad, flags, dt, s);
-      };
-      if (fus) {
-        const float* cur = cur_in;
-        for (int j = 0; j < B.nconv - 1; ++j) {
-          const ConvSpec& L = P.convs[B.conv[j]];
-          TRY(coeffs(L));
-          TRY(fused(L, cur, arena + L.Z_off, EPI_AFFINE | EPI_RELU));
-          cur = arena + L.Z_off;
-        }
-        float* res = const_cast<float*>(cur_in);       // identity block: the sum replaces the block input
-        if (B.ds >= 0) {
-          const ConvSpec& Ld = P.convs[B.ds];
-          TRY(coeffs(Ld));
-          res = arena + Ld.Y_off;
-          TRY(fused(Ld, cur_in, res, EPI_AFFINE));
-        }
-        const ConvSpec& LL = P.convs[nlast];
-        TRY(coeffs(LL));
-        TRY(fused(LL, cur, res, EPI_AFFINE | EPI_ACCUM | EPI_RELU));
-        cur_in = res;
-      } else {
-        const float* cur = cur_in;
-        for (int j = 0; j < B.nconv; ++j) {
-          const ConvSpec& L = P.convs[B.conv[j]];
-          TRY(conv_bn(c, L, cur));
-          if (j < B.nconv - 1) {
-            TRY(launch_bn_act_fwd(arena + L.Y_off, coef(c, L, 2), coef(c, L, 3), nullptr, nullptr, nullptr, arena + L.Z_off,
-                                  (long long)F * L.Ho * L.Wo, L.Co, 1, nullptr, dt, s));
-            cur = arena + L.Z_off;
-          }
-        }
-        const ConvSpec& LL = P.convs[nlast];
-        const long long rows = (long long)F * B.Ho * B.Wo;
-        if (B.ds >= 0) {
-          const ConvSpec& Ld = P.convs[B.ds];
-          TRY(conv_bn(c, Ld, cur_in));
-          TRY(launch_bn_act_fwd(arena + LL.Y_off, coef(c, LL, 2), coef(c, LL, 3), arena + Ld.Y_off, coef(c, Ld, 2), coef(c, Ld, 3),
-                                arena + B.out_off, rows, B.Co, 1, nullptr, dt, s));
-        } else {
-          TRY(launch_bn_act_fwd(arena + LL.Y_off, coef(c, LL, 2), coef(c, LL, 3), cur_in, nullptr, nullptr, arena + B.out_off, rows,
-                                B.Co, 1, nullptr, dt, s));
-        }
-        cur_in = arena + B.out_off;
-      }
-    }
-    const BlockSpec& lastb = P.blocks.back();
-    TRY(launch_avgpool_fwd(cur_in, h_out, F, lastb.Ho * lastb.Wo, lastb.Co, dt, s));
-    return 0;
-  }
+  c.R.last_training = training;
+  c.R.last_crop = crop ? 1 : 0;
+  c.R.next_stage = infer ? -3 : 0;   // a new forward invalidates whatever an unfinished backward left behind (-3: nothing to differentiate)
+  c.R.dout_fused_rows = 0;
+  TRY(TileCounters::reset(c, TileCounters::FORWARD));
+  if (c.dt == DT_BF16) TRY(launch_convert_bf16(params, arena + P.w16_off, P.n_params, s));   // bf16 image of every weight (45 MB for ResNet-50)
+  TRY(stem_forward(c, x_nchw, crop));
+  const bool fused = infer && g_fused_inference;
+  float* cur = arena + P.blocks[0].in_off;
   for (const BlockSpec& B : P.blocks) {
-    const float* Xin = arena + B.in_off;
-    const float* cur = Xin;
-    for (int j = 0; j < B.nconv; ++j) {
-      const ConvSpec& L = P.convs[B.conv[j]];
-      TRY(conv_bn(c, L, cur));
-      if (j < B.nconv - 1) {
-        const long long rows = (long long)F * L.Ho * L.Wo;
-        TRY(launch_bn_act_fwd(arena + L.Y_off, coef(c, L, 2), coef(c, L, 3), nullptr, nullptr, nullptr, arena + L.Z_off, rows,
-                              L.Co, 1, nullptr, dt, s));
-        cur = arena + L.Z_off;
-      }
-    }
-    const ConvSpec& LL = P.convs[B.conv[B.nconv - 1]];
-    const long long rows = (long long)F * B.Ho * B.Wo;
-    unsigned* mask = reinterpret_cast<unsigned*>(arena + B.mask_off);   // [z > 0] bits of the block output, for backward
-    if (B.ds >= 0) {
-      const ConvSpec& Ld = P.convs[B.ds];
-      TRY(conv_bn(c, Ld, Xin));
-      TRY(launch_bn_act_fwd(arena + LL.Y_off, coef(c, LL, 2), coef(c, LL, 3), arena + Ld.Y_off, coef(c, Ld, 2), coef(c, Ld, 3),
-                            arena + B.out_off, rows, B.Co, 1, mask, dt, s));
+    if (fused && block_fusable(c, B)) {
+      TRY(block_forward_fused(c, B, cur, &cur));
     } else {
-      TRY(launch_bn_act_fwd(arena + LL.Y_off, coef(c, LL, 2), coef(c, LL, 3), Xin, nullptr, nullptr, arena + B.out_off, rows,
-                            B.Co, 1, mask, dt, s));
+      TRY(block_forward(c, B, cur, fused ? nullptr : reinterpret_cast<unsigned*>(arena + B.mask_off)));
+      cur = arena + B.out_off;
     }
   }
   const BlockSpec& last = P.blocks.back();
-  TRY(launch_avgpool_fwd(arena + last.out_off, h_out, F, last.Ho * last.Wo, last.Co, dt, s));
-  return 0;
+  return launch_avgpool_fwd(cur, h_out, P.F, last.Ho * last.Wo, last.Co, c.dt, s);
 }
 
+// ---- backward -----------------------------------------------------------------------------------------------
+// partial rows -> the parameter gradients and the two per-channel coefficients c1 / c2 the second pass needs.
+// from_dgrad: the partials are a dgrad epilogue's (EPI_BNRED): sum(g) and sum(g (y - mean)) per 64 rows
+static int bn_backward_combine(Ctx& c, const ConvSpec& L, const float* partial, int prow, bool from_dgrad = false) {
+  TRY(launch_bn_stats_reduce(partial, prow, L.Co, c.acc(), c.s));
+  return launch_bn_bwd_finalize_rows(c.acc(), prow, (long long)c.P.F * L.Ho * L.Wo, c.R.last_training, c.dgamma(L), c.dbeta(L), c.coef(L, 4),
+                                     c.coef(L, 5), c.bn_accumulate(), L.Co, c.s, from_dgrad ? c.coef(L, 1) : nullptr);
+}
 // BatchNorm(+ReLU / residual mask) backward of layer L: dZ -> dY, parameter gradients into the flat gradient buffer
-// fused_rows > 0: the dgrad that produced dZ already wrote this BatchNorm's backward partials (EPI_BNRED, sum(g) and
-// sum(g (y - mean)) per 64 rows) into the partial buffer: the stand-alone first pass is skipped
-// first pass + combine: the parameter gradients and the two per-channel coefficients c1 / c2 the second pass needs
+// fused_rows > 0: the dgrad that produced dZ already wrote this BatchNorm's backward partials (EPI_BNRED) into the partial buffer:
+// the stand-alone first pass is skipped
 static int bn_backward_sums(Ctx& c, const ConvSpec& L, const float* dZ, const unsigned* Zbits, int fused_rows) {
-  Plan& P = c.P;
-  const long long rows = (long long)P.F * L.Ho * L.Wo;
-  float* partial = c.arena + P.partial_off;
-  double* acc = reinterpret_cast<double*>(c.arena + P.acc_off);
-  const float* Y = c.arena + L.Y_off;
-  int prow = fused_rows;
-  if (!fused_rows) {
-    TRY(launch_bn_bwd_reduce(dZ, nullptr, Zbits, Y, coef(c, L, 2), coef(c, L, 3), coef(c, L, 0), coef(c, L, 1), partial, rows, L.Co, c.dt, c.s));
-    prow = bn_bwd_partial_rows(rows, L.Co, c.dt);
-  }
-  TRY(launch_bn_stats_reduce(partial, prow, L.Co, acc, c.s));
-  return launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.dgamma(L), c.dbeta(L), coef(c, L, 4),
-                                     coef(c, L, 5), c.bn_accumulate(), L.Co, c.s, fused_rows ? coef(c, L, 1) : nullptr);
+  if (fused_rows) return bn_backward_combine(c, L, c.partial(), fused_rows, true);
+  const long long rows = (long long)c.P.F * L.Ho * L.Wo;
+  TRY(launch_bn_bwd_reduce(dZ, nullptr, Zbits, c.arena + L.Y_off, c.coef(L, 2), c.coef(L, 3), c.coef(L, 0), c.coef(L, 1), c.partial(), rows,
+                           L.Co, c.dt, c.s));
+  return bn_backward_combine(c, L, c.partial(), bn_bwd_partial_rows(rows, L.Co, c.dt));
 }
 static int bn_backward(Ctx& c, const ConvSpec& L, const float* dZ, const unsigned* Zbits, float* dY, int fused_rows = 0) {
   TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
   const long long rows = (long long)c.P.F * L.Ho * L.Wo;
-  return launch_bn_bwd_apply(dZ, nullptr, Zbits, c.arena + L.Y_off, coef(c, L, 2), coef(c, L, 3), coef(c, L, 0), coef(c, L, 1), coef(c, L, 4),
-                             coef(c, L, 5), dY, rows, L.Co, c.dt, c.s);
+  return launch_bn_bwd_apply(dZ, nullptr, Zbits, c.arena + L.Y_off, c.coef(L, 2), c.coef(L, 3), c.coef(L, 0), c.coef(L, 1), c.coef(L, 4),
+                             c.coef(L, 5), dY, rows, L.Co, c.dt, c.s);
 }
 // The two BatchNorms that feed a downsample block's add + ReLU (its last convolution's and the downsample convolution's) see the SAME
 // masked output gradient: their second passes run as ONE launch that reads dOut and the mask bits once (bn.hip, bn_bwd_apply2).
@@ -735,20 +710,12 @@ static int bn_backward_pair(Ctx& c, const ConvSpec& L, const ConvSpec& Ld, const
   const long long rows = (long long)c.P.F * L.Ho * L.Wo;
   if (!fused_rows && bn_bwd_reduce2_available(L.Co, c.dt)) {
     // both first passes are stand-alone (bf16 plans): one launch, two partial sets, then the two combines one after the other
-    Plan& P = c.P;
-    float* partial = c.arena + P.partial_off;
-    double* acc = reinterpret_cast<double*>(c.arena + P.acc_off);
     const int prow = bn_bwd_partial_rows(rows, L.Co, c.dt);
     const long long set = (long long)prow * 2 * L.Co;
-    TRY(launch_bn_bwd_reduce2(dZ, Zbits, c.arena + L.Y_off, c.arena + L.coef_off, c.arena + Ld.Y_off, c.arena + Ld.coef_off, partial, set,
+    TRY(launch_bn_bwd_reduce2(dZ, Zbits, c.arena + L.Y_off, c.arena + L.coef_off, c.arena + Ld.Y_off, c.arena + Ld.coef_off, c.partial(), set,
                               rows, L.Co, c.dt, c.s));
-    const ConvSpec* two[2] = {&L, &Ld};
-    for (int k = 0; k < 2; ++k) {
-      const ConvSpec& Q = *two[k];
-      TRY(launch_bn_stats_reduce(partial + k * set, prow, Q.Co, acc, c.s));
-      TRY(launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.dgamma(Q), c.dbeta(Q), coef(c, Q, 4),
-                                      coef(c, Q, 5), c.bn_accumulate(), Q.Co, c.s, nullptr));
-    }
+    TRY(bn_backward_combine(c, L, c.partial(), prow));
+    TRY(bn_backward_combine(c, Ld, c.partial() + set, prow));
   } else {
     TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
     TRY(bn_backward_sums(c, Ld, dZ, Zbits, 0));
@@ -758,8 +725,7 @@ static int bn_backward_pair(Ctx& c, const ConvSpec& L, const ConvSpec& Ld, const
 }
 
 static int wgrad(Ctx& c, const ConvSpec& L, const float* X, const float* dY) {
-  return conv_wgrad_launch(X, dY, c.grads + L.w_off, c.arena + c.P.wgp_off, c.P.F, L.Hi, L.Wi, L.Ci, L.Co, L.k, L.stride, L.pad,
-                           c.accumulate, c.dt, c.s);
+  return conv_wgrad_launch(X, dY, c.grads + L.w_off, c.arena + c.P.wgp_off, L.geom(c.P.F), c.accumulate, c.dt, c.s);
 }
 
 // bn_of: the conv layer whose BatchNorm consumes dX as its dz (its Y has dX's shape), bn_bits: that BatchNorm's output mask bits
@@ -770,16 +736,201 @@ static int dgrad(Ctx& c, const ConvSpec& L, const float* dY, float* dX, int flag
   float* Wt = c.dt == DT_BF16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(c.arena + c.P.wt_off) + L.wt_off)
                               : c.arena + c.P.wt_off + L.wt_off;
   if (fused_rows_out) *fused_rows_out = 0;
-  gg_set_tile_counters(reinterpret_cast<unsigned*>(c.arena + c.P.ctr_off) + (c.P.convs.size() + 4 * (&L - c.P.convs.data())) * 8, 4);   // backward part
+  TileCounters tc(c, TileCounters::BACKWARD, L);
   // 1x1 stride-2 dgrads leave three of four parity classes without taps (plain zero / no-op launches): not fused
   const bool fuse = bn_of && fused_rows_out && c.P.fuse_bnred && !(L.stride == 2 && L.k == 1);
-  struct DropCounters { ~DropCounters() { gg_set_tile_counters(nullptr, 0); } } drop;   // sets this layer did not use stay unused
-  if (!fuse)
-    return conv_dgrad_launch(dY, Wt, dX, add0, nullptr, addbits, c.P.F, L.Hi, L.Wi, L.Ci, L.Co, L.k, L.stride, L.pad, flags, c.dt, c.s);
-  BnRedArgs br{c.arena + bn_of->Y_off, bn_bits, c.arena + bn_of->coef_off + 2LL * bn_of->Co, c.arena + bn_of->coef_off + 3LL * bn_of->Co,
-               c.arena + bn_of->coef_off, c.arena + c.P.partial_off, 0};
-  TRY(conv_dgrad_launch_br(dY, Wt, dX, add0, nullptr, addbits, c.P.F, L.Hi, L.Wi, L.Ci, L.Co, L.k, L.stride, L.pad, flags, c.dt, &br, c.s));
+  if (!fuse) return conv_dgrad_launch(dY, Wt, dX, add0, nullptr, addbits, L.geom(c.P.F), flags, c.dt, c.s);
+  BnRedArgs br{c.arena + bn_of->Y_off, bn_bits, c.coef(*bn_of, 2), c.coef(*bn_of, 3), c.coef(*bn_of, 0), c.partial(), 0};
+  TRY(conv_dgrad_launch(dY, Wt, dX, add0, nullptr, addbits, L.geom(c.P.F), flags, c.dt, c.s, &br));
   *fused_rows_out = br.rows_out;
+  return 0;
+}
+
+// ---- the opt-in side stream (declared with RunState above) ----
+int SideStream::init() {
+  // Opt-in. Measured on ResNet-50 F=1280 (profiles/r01 notes in DESIGN.md): co-running wgrad with the BatchNorm-backward
+  // passes lengthens the wgrad launches by about the BatchNorm time (the two do not overlap usefully on gfx950 even
+  // though one is HBM-bound and the other MFMA-bound) -> step time unchanged (364.9 vs 364.5 ms). Kept for experiments.
+  // 2 (round 5 experiment): wgrad(L) starts TOGETHER with dgrad(L) (both wait for dY_L only) and nothing on the main stream waits
+  // for it before its dY buffer is rewritten: the two GEMMs fill each other's tile-quantisation tails (every launch of the
+  // 1280-frame step has 490 k tiles for 512 slots).
+  if (mode < 0) mode = R3M_ENV_INT("R3M_SIDE_STREAM", 0);
+  if (!mode || side) return 0;
+  if (hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) { set_last_error("side stream: create failed"); return 1; }
+  for (hipEvent_t* ev : {&ev_dy, &ev_wg[0], &ev_wg[1], &ev_join})
+    if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { set_last_error("side stream: event create failed"); return 1; }
+  return 0;
+}
+void SideStream::destroy() {
+  if (!side) return;
+  (void)hipStreamDestroy(side);
+  for (hipEvent_t ev : {ev_dy, ev_wg[0], ev_wg[1], ev_join})
+    if (ev) (void)hipEventDestroy(ev);
+}
+int SideStream::mark_dy() {
+  if (hipEventRecord(ev_dy, main) != hipSuccess || hipStreamWaitEvent(side, ev_dy, 0) != hipSuccess) {
+    set_last_error("side stream: event ordering failed");
+    return 1;
+  }
+  return 0;
+}
+int SideStream::wgrad_async(Ctx& c, const ConvSpec& L, const float* X, const float* dY, int ai) {
+  if (!c.grads) return 0;                  // frozen encoder: no weight gradient
+  if (!on) return wgrad(c, L, X, dY);
+  if (mode != 2) TRY(mark_dy());           // mode 1: wgrad(L) starts once the dgrad(L) just enqueued is done
+  Ctx cs = c;                              // context whose launches go to the side stream
+  cs.s = side;
+  TRY(wgrad(cs, L, X, dY));
+  if (hipEventRecord(ev_wg[ai], side) != hipSuccess) { set_last_error("side stream: record failed"); return 1; }
+  pending[ai] = true;
+  return 0;
+}
+int SideStream::acquire(int ai) {
+  if (on && pending[ai]) {
+    if (hipStreamWaitEvent(main, ev_wg[ai], 0) != hipSuccess) { set_last_error("side stream: wait failed"); return 1; }
+    pending[ai] = false;
+  }
+  return 0;
+}
+int SideStream::wait_wgrads() {
+  if (on && mode == 2) return mark_dy();      // mode 2: no wait; the dY just written is what the side stream waits for
+  TRY(acquire(0));
+  return acquire(1);
+}
+int SideStream::join() {
+  if (!on) return 0;
+  if (hipEventRecord(ev_join, side) != hipSuccess || hipStreamWaitEvent(main, ev_join, 0) != hipSuccess) {
+    set_last_error("side stream: join failed");
+    return 1;
+  }
+  pending[0] = pending[1] = false;
+  return 0;
+}
+
+// the weights are final since the last optimizer step: all dgrad weight images in one launch, at the start of each backward
+static int build_weight_images(Ctx& c) {
+  const Plan& P = c.P;
+  if (!c.R.d_wt_tab) {
+    // failure-atomic: the plan's pointers are set only after both allocations and both uploads succeeded (a half-initialised
+    // pair would make the next backward skip this block and launch transpose_w_all on a null / uninitialised table)
+    const size_t tb = P.wt_tab.size() * sizeof(WtEntry), ib = P.wt_tile0.size() * sizeof(int);
+    WtEntry* d_tab = nullptr;
+    int* d_tile0 = nullptr;
+    const bool ok = hipMalloc(reinterpret_cast<void**>(&d_tab), tb) == hipSuccess &&
+                    hipMalloc(reinterpret_cast<void**>(&d_tile0), ib) == hipSuccess &&
+                    hipMemcpy(d_tab, P.wt_tab.data(), tb, hipMemcpyHostToDevice) == hipSuccess &&
+                    hipMemcpy(d_tile0, P.wt_tile0.data(), ib, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      if (d_tab) (void)hipFree(d_tab);
+      if (d_tile0) (void)hipFree(d_tile0);
+      set_last_error("resnet_backward: cannot allocate / upload the weight-image table (%zu + %zu bytes)", tb, ib);
+      return 1;
+    }
+    c.R.d_wt_tab = d_tab;
+    c.R.d_wt_tile0 = d_tile0;
+  }
+  return launch_transpose_w_all(c.params, c.arena + P.wt_off, c.R.d_wt_tab, c.R.d_wt_tile0, (int)P.wt_tab.size(), P.wt_tile0.back(), P.dtype,
+                                c.s);
+}
+
+// Block bi: the gradient of its output (role D) -> parameter gradients and the gradient of its input (role C, then swapped into D)
+static int block_backward(Ctx& c, int bi) {
+  const Plan& P = c.P;
+  SideStream& side = c.R.side;
+  float* arena = c.arena;
+  const BlockSpec& B = P.blocks[bi];
+  const float* dOut = c.G(0);
+  const unsigned* Out = reinterpret_cast<const unsigned*>(arena + B.mask_off);   // [out > 0] bits
+  const float* Xin = arena + B.in_off;
+  float* Gb = c.G(3);
+  float* Gc = c.G(4);
+  // last conv of the block: its BatchNorm output joined the residual add, mask comes from the block output
+  const float* dz = dOut;
+  const unsigned* zmask = Out;
+  // partials of the BatchNorm that consumes dz, written by the dgrad that produced dz (EPI_BNRED) — 0: none
+  int dz_fused = c.R.dout_fused_rows;
+  c.R.dout_fused_rows = 0;
+  // the block whose output gradient this block's last dgrad completes, and the BatchNorm (its last conv's) that will read it
+  const BlockSpec* Bprev = bi > 0 ? &P.blocks[bi - 1] : nullptr;
+  const ConvSpec* Lprev_last = Bprev ? &P.convs[Bprev->conv[Bprev->nconv - 1]] : nullptr;
+  const unsigned* prev_bits = Bprev ? reinterpret_cast<const unsigned*>(arena + Bprev->mask_off) : nullptr;
+  int ai;
+  // downsample block: both tail BatchNorms in one second pass, the downsample one's dY parked in E until the end of the block
+  // (R3M_BN_PAIR=0 in probe builds: two separate passes, for A/B)
+  const bool pair = B.ds >= 0 && P.E_off >= 0 && B.nconv >= 2 && P.bn_pair && R3M_ENV_INT("R3M_BN_PAIR", 1) != 0 && P.convs[B.ds].Co >= 8;
+  float* const dYd_pair = pair ? arena + P.E_off : nullptr;
+  for (int j = B.nconv - 1; j >= 1; --j) {
+    const ConvSpec& L = P.convs[B.conv[j]];
+    const ConvSpec& Lprev = P.convs[B.conv[j - 1]];
+    float* dY = c.next_A(&ai);
+    TRY(side.acquire(ai));
+    if (pair && j == B.nconv - 1) TRY(bn_backward_pair(c, L, P.convs[B.ds], dz, zmask, dY, dYd_pair, dz_fused));
+    else TRY(bn_backward(c, L, dz, zmask, dY, dz_fused));     // HBM-bound: overlaps the previous layer's wgrad
+    TRY(side.wait_wgrads());
+    TRY(dgrad(c, L, dY, Gb, 0, nullptr, nullptr, &Lprev, nullptr, &dz_fused));   // Gb = dz of Lprev's BatchNorm + its partials
+    TRY(side.wgrad_async(c, L, arena + Lprev.Z_off, dY, ai));
+    dz = Gb; zmask = nullptr;   // Gb is consumed by the next bn_backward before a later dgrad rewrites it
+  }
+  const ConvSpec& L1 = P.convs[B.conv[0]];
+  float* dY1 = c.next_A(&ai);
+  TRY(side.acquire(ai));
+  TRY(bn_backward(c, L1, dz, zmask, dY1, dz_fused));
+  TRY(side.wait_wgrads());
+  if (B.ds >= 0) {
+    const ConvSpec& Ld = P.convs[B.ds];
+    TRY(dgrad(c, L1, dY1, Gc, 0, nullptr, nullptr));
+    TRY(side.wgrad_async(c, L1, Xin, dY1, ai));
+    if (pair) {                                     // dY of the downsample BatchNorm has been waiting in E since the block's first pass
+      TRY(dgrad(c, Ld, dYd_pair, Gc, EPI_ACCUM, nullptr, nullptr));
+      TRY(side.wgrad_async(c, Ld, Xin, dYd_pair, ai));      // (side stream: ordered behind conv1's wgrad, same event slot)
+    } else {
+      int ad;
+      float* dYd = c.next_A(&ad);
+      TRY(side.acquire(ad));
+      TRY(bn_backward(c, Ld, dOut, Out, dYd));        // overlaps wgrad(conv1); always the stand-alone reduce (second consumer of dOut)
+      TRY(side.wait_wgrads());
+      TRY(dgrad(c, Ld, dYd, Gc, EPI_ACCUM, nullptr, nullptr));
+      TRY(side.wgrad_async(c, Ld, Xin, dYd, ad));
+    }
+  } else {
+    // Gc = dgrad + masked residual gradient = the previous block's COMPLETE output gradient: also emit the partials of the
+    // BatchNorm that will consume it (the previous block's last one, masked by that block's output bits)
+    TRY(dgrad(c, L1, dY1, Gc, EPI_MASKED_ADD, dOut, Out, Lprev_last, prev_bits, &c.R.dout_fused_rows));
+    TRY(side.wgrad_async(c, L1, Xin, dY1, ai));
+  }
+  // C becomes the gradient of the previous block's output; the old D is free (only the main stream ever read it)
+  std::swap(c.R.roles[0], c.R.roles[4]);
+  return 0;
+}
+
+// stem: maxpool + BN/ReLU backward (fused) -> conv1 weight gradient [-> input gradient]
+static int stem_backward(Ctx& c, float* dx, int dx_accumulate) {
+  const Plan& P = c.P;
+  const int F = P.F, dt = c.dt;
+  const ConvSpec& L0 = P.convs[0];
+  float* Gc = c.G(4);
+  const float* Y = c.arena + L0.Y_off;
+  // MaxPool backward gathered inside both BatchNorm-backward passes (no dZ0 tensor)
+  const unsigned char* am = reinterpret_cast<const unsigned char*>(c.arena + P.amax_off);
+  TRY(launch_bn_bwd_reduce_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.partial(), F, P.H1, P.W1, 64, dt,
+                                c.s));
+  TRY(bn_backward_combine(c, L0, c.partial(), bn_bwd_pool_partial_rows(F, P.H1, P.W1, 64)));
+  TRY(launch_bn_bwd_apply_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.coef(L0, 4), c.coef(L0, 5), Gc, F,
+                               P.H1, P.W1, 64, dt, c.s));
+  TRY(c.R.side.join());   // the stem wgrad shares the split-K scratch with the side stream's wgrads
+  const float* xn = c.arena + P.col_off;
+  float* ws = c.arena + P.wgp_off;
+  if (c.grads) {
+    if (c.R.stem_gen) TRY(launch_stem_wgrad_gen(xn, Gc, c.grads + L0.w_off, ws, F, P.H, P.W, c.accumulate, dt, c.s));
+    else if (dt == DT_BF16) TRY(launch_stem_wgrad16(xn, Gc, c.grads + L0.w_off, ws, F, c.accumulate, c.s));
+    else TRY(launch_stem_wgrad(xn, Gc, c.grads + L0.w_off, ws, F, c.accumulate, dt, c.s));
+  }
+  // Gc = conv1's output gradient; the bf16 rounding of the normalised frames is taken as identity (as autocast does)
+  if (dx) {
+    if (c.R.stem_gen) TRY(launch_stem_input_grad_gen(Gc, dt, c.params + L0.w_off, dx, F, P.H, P.W, dx_accumulate, c.s));
+    else TRY(launch_stem_input_grad(Gc, dt, c.params + L0.w_off, dx, F, dx_accumulate, c.s));
+  }
   return 0;
 }
 
@@ -788,261 +939,47 @@ static int dgrad(Ctx& c, const ConvSpec& L, const float* dY, float* dX, int flag
 // carried across calls so stages can be issued one by one (the data-parallel wrapper launches the RCCL all-reduce of a
 // finished stage's gradient slice in between).
 //
-// Streams: wgrad(L) only needs dY_L and the saved activations, and nothing on the critical path needs its result before
-// the optimizer. It runs on a side stream, ordered by events so that it overlaps ONLY with the HBM-bound BatchNorm-backward
-// passes of the next layer down (reduce / apply: ~6 TB/s, no MFMA) and never with the MFMA-bound dgrad:
-//     main:  bn_bwd(L) -> [wait wgrad(L+1)] -> dgrad(L) -> bn_bwd(L-1) -> [wait wgrad(L)] -> dgrad(L-1) -> ...
-//     side:                                    wgrad(L)  (starts when dgrad(L) has finished)
-// A bandwidth-bound and a matrix-bound kernel share the CUs without stealing each other's bottleneck resource, and the
-// per-launch timings of the dominant kernel class (gather-GEMM on the main stream) stay unperturbed. Each stage ends with
-// a join. Off by default (R3M_SIDE_STREAM=1 enables it): measured neutral, see side_init().
-static int side_init(Plan& P) {
-  if (P.use_side < 0) {
-    // Opt-in. Measured on ResNet-50 F=1280 (profiles/r01 notes in DESIGN.md): co-running wgrad with the BatchNorm-backward
-    // passes lengthens the wgrad launches by about the BatchNorm time (the two do not overlap usefully on gfx950 even
-    // though one is HBM-bound and the other MFMA-bound) -> step time unchanged (364.9 vs 364.5 ms). Kept for experiments.
-    // 2 (round 5 experiment): wgrad(L) starts TOGETHER with dgrad(L) (both wait for dY_L only) and nothing on the main stream waits
-    // for it before its dY buffer is rewritten: the two GEMMs fill each other's tile-quantisation tails (every launch of the
-    // 1280-frame step has 490 k tiles for 512 slots).
-    P.use_side = R3M_ENV_INT("R3M_SIDE_STREAM", 0);
-  }
-  if (!P.bnred_init) {
-    P.bnred_init = true;
-    // fp32 plans only: there the dgrad is MFMA-bound and the extra epilogue loads ride under other blocks' matrix work (A/B on one
-    // box, probe build: 343.0 / 341.7 ms -> 338.5 / 339.0 ms per ResNet-50 step). bf16 plans are HBM/epilogue-bound already and
-    // measured slightly SLOWER with it (ResNet-50 95.6 -> 96.2 ms, ResNet-34 97.0 -> 97.9 ms), so they keep the stand-alone reduce.
-    // R3M_BNRED (probe builds): 0 = off everywhere, 2 = on for bf16 too.
-    {
-      const int v = R3M_ENV_INT("R3M_BNRED", 1);
-      if (v != 1) P.fuse_bnred = v == 2;       // probe builds: 0 = off everywhere, 2 = on for bf16 too; 1 = the plan's own setting
-    }
-  }
-  if (!P.use_side || P.side) return 0;
-  if (hipStreamCreateWithFlags(&P.side, hipStreamNonBlocking) != hipSuccess) { set_last_error("side stream: create failed"); return 1; }
-  hipEvent_t* evs[4] = {&P.ev_dy, &P.ev_wg[0], &P.ev_wg[1], &P.ev_join};
-  for (auto ev : evs)
-    if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { set_last_error("side stream: event create failed"); return 1; }
-  return 0;
-}
-
 // grads == nullptr: no parameter gradient (frozen encoder) — no weight-gradient launch is enqueued, the side stream stays idle and
 // the BatchNorm parameter sums go to plan scratch. dx != nullptr (only with stage 3 in range): d/d(frames) [F,3,H,W] fp32 NCHW
 // of the frames of the last forward (stem_dgrad.hip), written (dx_accumulate = 0) or added.
 int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
-                  int accumulate, int* gd_io, hipStream_t s, float* dx, int dx_accumulate) {
-  Ctx c{P, params, grads, nullptr, arena, s, P.last_training, accumulate, P.dtype};
-  const int dt = P.dtype;
+                  int accumulate, hipStream_t s, float* dx, int dx_accumulate) {
+  RunState& R = P.run;
+  Ctx c{P, R, params, grads, nullptr, arena, s, R.last_training, accumulate, P.dtype};
   R3M_REQUIRE(stage_begin >= 0 && stage_end <= 4 && stage_begin < stage_end, "resnet_backward: stages [%d, %d) outside [0, 4)", stage_begin, stage_end);
-  R3M_REQUIRE(P.next_stage != -3, "resnet_backward: the last forward on this plan ran in inference mode (training = 2): nothing was kept for a backward");
+  R3M_REQUIRE(R.next_stage != -3, "resnet_backward: the last forward on this plan ran in inference mode (training = 2): nothing was kept for a backward");
   R3M_REQUIRE(!dx || stage_end == 4, "resnet_backward: dx (the input gradient) is formed by the stem, in stage 3; stages [%d, %d) do not "
               "include it", stage_begin, stage_end);
-  R3M_REQUIRE(!dx || !P.last_crop, "resnet_backward: no input gradient after r3m_resnet_forward_crop (the frames were resampled from raw "
+  R3M_REQUIRE(!dx || !R.last_crop, "resnet_backward: no input gradient after r3m_resnet_forward_crop (the frames were resampled from raw "
               "clips inside the stem pre-pass; pass dx = NULL)");
-  R3M_REQUIRE(P.next_stage != -1, "resnet_backward: no forward has run on this plan");
+  R3M_REQUIRE(R.next_stage != -1, "resnet_backward: no forward has run on this plan");
   // stage 0 may always (re)start a backward over the saved activations (retain_graph); any other stage must continue the
   // sequence the previous call left off at — its inputs (running output gradient, pending EPI_BNRED partials) live in the plan
-  R3M_REQUIRE(stage_begin == 0 || stage_begin == P.next_stage,
+  R3M_REQUIRE(stage_begin == 0 || stage_begin == R.next_stage,
               "resnet_backward: stage %d requested but the plan expects stage %d (stages run 0..3 in order after each forward; "
-              "stage 0 restarts)", stage_begin, P.next_stage);
-  P.next_stage = -2;           // poisoned while in flight: after a failed call only stage 0 (a restart) is accepted
-  TRY(side_init(P));
-  if (stage_begin == 0) {       // the weights are final since the last optimizer step: all dgrad weight images in one launch
-    if (hipMemsetAsync(arena + P.ctr_off + P.convs.size() * 8, 0, 4 * P.convs.size() * 8 * sizeof(unsigned), s) != hipSuccess) {
-      set_last_error("resnet_backward: cannot reset the tile queues");
-      return 1;
-    }
-    if (!P.d_wt_tab) {
-      // failure-atomic: the plan's pointers are set only after both allocations and both uploads succeeded (a half-initialised
-      // pair would make the next backward skip this block and launch transpose_w_all on a null / uninitialised table)
-      const size_t tb = P.wt_tab.size() * sizeof(WtEntry), ib = P.wt_tile0.size() * sizeof(int);
-      WtEntry* d_tab = nullptr;
-      int* d_tile0 = nullptr;
-      const bool ok = hipMalloc(reinterpret_cast<void**>(&d_tab), tb) == hipSuccess &&
-                      hipMalloc(reinterpret_cast<void**>(&d_tile0), ib) == hipSuccess &&
-                      hipMemcpy(d_tab, P.wt_tab.data(), tb, hipMemcpyHostToDevice) == hipSuccess &&
-                      hipMemcpy(d_tile0, P.wt_tile0.data(), ib, hipMemcpyHostToDevice) == hipSuccess;
-      if (!ok) {
-        (void)hipGetLastError();
-        if (d_tab) (void)hipFree(d_tab);
-        if (d_tile0) (void)hipFree(d_tile0);
-        set_last_error("resnet_backward: cannot allocate / upload the weight-image table (%zu + %zu bytes)", tb, ib);
-        return 1;
-      }
-      P.d_wt_tab = d_tab;
-      P.d_wt_tile0 = d_tile0;
-    }
-    TRY(launch_transpose_w_all(params, arena + P.wt_off, P.d_wt_tab, P.d_wt_tile0, (int)P.wt_tab.size(), P.wt_tile0.back(), P.dtype, s));
+              "stage 0 restarts)", stage_begin, R.next_stage);
+  R.next_stage = -2;           // poisoned while in flight: after a failed call only stage 0 (a restart) is accepted
+  TRY(R.side.init());
+  R.side.begin(s, grads != nullptr);
+  if (stage_begin == 0) {
+    TRY(TileCounters::reset(c, TileCounters::BACKWARD));
+    TRY(build_weight_images(c));
   }
-  const bool side_on = P.use_side && P.side && grads;
-  Ctx cs = c;                       // context whose launches go to the side stream
-  cs.s = side_on ? P.side : s;
-  const int F = P.F;
-  // buffer roles: role[0]=D, role[1]=A0, role[2]=A1, role[3]=B, role[4]=C  (indices into G_off), rotated per block
-  int* role = P.roles;
-  auto Gp = [&](int r) { return arena + P.G_off[role[r]]; };
-
-  const bool side_co = side_on && P.use_side == 2;   // wgrad(L) runs beside dgrad(L)
-  // mode 2: call right BEFORE dgrad(L) is enqueued — the side stream may start wgrad(L) as soon as dY_L is complete
-  auto mark_dy = [&]() -> int {
-    if (!side_co) return 0;
-    if (hipEventRecord(P.ev_dy, s) != hipSuccess || hipStreamWaitEvent(P.side, P.ev_dy, 0) != hipSuccess) {
-      set_last_error("side stream: event ordering failed");
-      return 1;
-    }
-    return 0;
-  };
-  // call right AFTER dgrad(L) was enqueued on the main stream: wgrad(L) starts on the side stream once that dgrad is done (mode 1)
-  auto wgrad_async = [&](const ConvSpec& L, const float* X, const float* dY, int ai) -> int {
-    if (!grads) return 0;                  // frozen encoder: no weight gradient
-    if (!side_on) return wgrad(c, L, X, dY);
-    if (!side_co && (hipEventRecord(P.ev_dy, s) != hipSuccess || hipStreamWaitEvent(P.side, P.ev_dy, 0) != hipSuccess)) {
-      set_last_error("side stream: event ordering failed");
-      return 1;
-    }
-    TRY(wgrad(cs, L, X, dY));
-    if (hipEventRecord(P.ev_wg[ai], P.side) != hipSuccess) { set_last_error("side stream: record failed"); return 1; }
-    P.wg_pending[ai] = true;
-    return 0;
-  };
-  // before the main stream overwrites A[ai], the wgrad that last read it must be done
-  auto acquire_A = [&](int ai) -> int {
-    if (side_on && P.wg_pending[ai]) {
-      if (hipStreamWaitEvent(s, P.ev_wg[ai], 0) != hipSuccess) { set_last_error("side stream: wait failed"); return 1; }
-      P.wg_pending[ai] = false;
-    }
-    return 0;
-  };
-  // before an MFMA-bound kernel goes to the main stream: every wgrad in flight must have finished
-  auto wait_wgrads = [&]() -> int {
-    if (side_co) return mark_dy();      // mode 2: no wait; the dY just written is what the side stream waits for
-    TRY(acquire_A(0));
-    return acquire_A(1);
-  };
-  auto join_side = [&]() -> int {
-    if (!side_on) return 0;
-    if (hipEventRecord(P.ev_join, P.side) != hipSuccess || hipStreamWaitEvent(s, P.ev_join, 0) != hipSuccess) {
-      set_last_error("side stream: join failed");
-      return 1;
-    }
-    P.wg_pending[0] = P.wg_pending[1] = false;
-    return 0;
-  };
-  auto next_A = [&](int* ai) -> float* {
-    *ai = P.a_next;
-    P.a_next ^= 1;
-    return Gp(1 + *ai);
-  };
-
   for (int st = stage_begin; st < stage_end; ++st) {
-    const int layer = 3 - st;
     if (st == 0) {
       const BlockSpec& last = P.blocks.back();
-      for (int r = 0; r < 5; ++r) role[r] = r;
-      P.a_next = 0;
-      P.wg_pending[0] = P.wg_pending[1] = false;
-      P.dout_fused_rows = 0;     // the last block's output gradient comes from the pool: its BatchNorm runs the stand-alone reduce
-      TRY(launch_avgpool_bwd(dh, Gp(0), F, last.Ho * last.Wo, last.Co, dt, s));
+      for (int r = 0; r < 5; ++r) R.roles[r] = r;
+      R.a_next = 0;
+      R.side.restart();
+      R.dout_fused_rows = 0;     // the last block's output gradient comes from the pool: its BatchNorm runs the stand-alone reduce
+      TRY(launch_avgpool_bwd(dh, c.G(0), P.F, last.Ho * last.Wo, last.Co, c.dt, s));
     }
-    for (int bi = (int)P.blocks.size() - 1; bi >= 0; --bi) {
-      const BlockSpec& B = P.blocks[bi];
-      if (B.stage != layer) continue;
-      const float* dOut = Gp(0);
-      const unsigned* Out = reinterpret_cast<const unsigned*>(arena + B.mask_off);   // [out > 0] bits
-      const float* Xin = arena + B.in_off;
-      float* Gb = Gp(3);
-      float* Gc = Gp(4);
-      // last conv of the block: its BatchNorm output joined the residual add, mask comes from the block output
-      const float* dz = dOut;
-      const unsigned* zmask = Out;
-      // partials of the BatchNorm that consumes dz, written by the dgrad that produced dz (EPI_BNRED) — 0: none
-      int dz_fused = P.dout_fused_rows;
-      P.dout_fused_rows = 0;
-      // the block whose output gradient this block's last dgrad completes, and the BatchNorm (its last conv's) that will read it
-      const BlockSpec* Bprev = bi > 0 ? &P.blocks[bi - 1] : nullptr;
-      const ConvSpec* Lprev_last = Bprev ? &P.convs[Bprev->conv[Bprev->nconv - 1]] : nullptr;
-      const unsigned* prev_bits = Bprev ? reinterpret_cast<const unsigned*>(arena + Bprev->mask_off) : nullptr;
-      int ai;
-      // downsample block: both tail BatchNorms in one second pass, the downsample one's dY parked in E until the end of the block
-      // (R3M_BN_PAIR=0 in probe builds: two separate passes, for A/B)
-      const bool pair = B.ds >= 0 && P.E_off >= 0 && B.nconv >= 2 && P.bn_pair && R3M_ENV_INT("R3M_BN_PAIR", 1) != 0 && P.convs[B.ds].Co >= 8;
-      float* const dYd_pair = pair ? arena + P.E_off : nullptr;
-      for (int j = B.nconv - 1; j >= 1; --j) {
-        const ConvSpec& L = P.convs[B.conv[j]];
-        const ConvSpec& Lprev = P.convs[B.conv[j - 1]];
-        float* dY = next_A(&ai);
-        TRY(acquire_A(ai));
-        if (pair && j == B.nconv - 1) TRY(bn_backward_pair(c, L, P.convs[B.ds], dz, zmask, dY, dYd_pair, dz_fused));
-        else
-        TRY(bn_backward(c, L, dz, zmask, dY, dz_fused));     // HBM-bound: overlaps the previous layer's wgrad
-        TRY(wait_wgrads());
-        TRY(dgrad(c, L, dY, Gb, 0, nullptr, nullptr, &Lprev, nullptr, &dz_fused));   // Gb = dz of Lprev's BatchNorm + its partials
-        TRY(wgrad_async(L, arena + Lprev.Z_off, dY, ai));
-        dz = Gb; zmask = nullptr;   // Gb is consumed by the next bn_backward before a later dgrad rewrites it
-      }
-      const ConvSpec& L1 = P.convs[B.conv[0]];
-      float* dY1 = next_A(&ai);
-      TRY(acquire_A(ai));
-      TRY(bn_backward(c, L1, dz, zmask, dY1, dz_fused));
-      TRY(wait_wgrads());
-      if (B.ds >= 0) {
-        const ConvSpec& Ld = P.convs[B.ds];
-        TRY(dgrad(c, L1, dY1, Gc, 0, nullptr, nullptr));
-        TRY(wgrad_async(L1, Xin, dY1, ai));
-        if (pair) {                                     // dY of the downsample BatchNorm has been waiting in E since the block's first pass
-          TRY(dgrad(c, Ld, dYd_pair, Gc, EPI_ACCUM, nullptr, nullptr));
-          TRY(wgrad_async(Ld, Xin, dYd_pair, ai));      // (side stream: ordered behind conv1's wgrad, same event slot)
-        } else {
-          int ad;
-          float* dYd = next_A(&ad);
-          TRY(acquire_A(ad));
-          TRY(bn_backward(c, Ld, dOut, Out, dYd));        // overlaps wgrad(conv1); always the stand-alone reduce (second consumer of dOut)
-          TRY(wait_wgrads());
-          TRY(dgrad(c, Ld, dYd, Gc, EPI_ACCUM, nullptr, nullptr));
-          TRY(wgrad_async(Ld, Xin, dYd, ad));
-        }
-      } else {
-        // Gc = dgrad + masked residual gradient = the previous block's COMPLETE output gradient: also emit the partials of the
-        // BatchNorm that will consume it (the previous block's last one, masked by that block's output bits)
-        TRY(dgrad(c, L1, dY1, Gc, EPI_MASKED_ADD, dOut, Out, Lprev_last, prev_bits, &P.dout_fused_rows));
-        TRY(wgrad_async(L1, Xin, dY1, ai));
-      }
-      // C becomes the gradient of the previous block's output; the old D is free (only the main stream ever read it)
-      const int t = role[0]; role[0] = role[4]; role[4] = t;
-    }
-    if (st == 3) {
-      // stem: maxpool + BN/ReLU backward (fused) -> conv1 weight gradient [-> input gradient]
-      const ConvSpec& L0 = P.convs[0];
-      float* Gc = Gp(4);
-      {   // MaxPool backward gathered inside both BatchNorm-backward passes (no dZ0 tensor)
-        const unsigned char* am = reinterpret_cast<const unsigned char*>(arena + P.amax_off);
-        const long long rows = (long long)F * P.H1 * P.W1;
-        float* partial = arena + P.partial_off;
-        double* acc = reinterpret_cast<double*>(arena + P.acc_off);
-        TRY(launch_bn_bwd_reduce_pool(Gp(0), am, arena + L0.Y_off, coef(c, L0, 2), coef(c, L0, 3), coef(c, L0, 0), coef(c, L0, 1), partial,
-                                      F, P.H1, P.W1, 64, dt, s));
-        const int prow = bn_bwd_pool_partial_rows(F, P.H1, P.W1, 64);
-        TRY(launch_bn_stats_reduce(partial, prow, 64, acc, s));
-        TRY(launch_bn_bwd_finalize_rows(acc, prow, rows, P.last_training, c.dgamma(L0), c.dbeta(L0), coef(c, L0, 4),
-                                        coef(c, L0, 5), c.bn_accumulate(), 64, s));
-        TRY(launch_bn_bwd_apply_pool(Gp(0), am, arena + L0.Y_off, coef(c, L0, 2), coef(c, L0, 3), coef(c, L0, 0), coef(c, L0, 1),
-                                     coef(c, L0, 4), coef(c, L0, 5), Gc, F, P.H1, P.W1, 64, dt, s));
-      }
-      TRY(join_side());   // the stem wgrad shares the split-K scratch with the side stream's wgrads
-      if (grads) {
-        if (P.stem_gen) TRY(launch_stem_wgrad_gen(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, P.H, P.W, accumulate, dt, s));
-        else if (dt == DT_BF16) TRY(launch_stem_wgrad16(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, s));
-        else TRY(launch_stem_wgrad(arena + P.col_off, Gc, grads + L0.w_off, arena + P.wgp_off, F, accumulate, dt, s));
-      }
-      // Gc = conv1's output gradient; the bf16 rounding of the normalised frames is taken as identity (as autocast does)
-      if (dx) {
-        if (P.stem_gen) TRY(launch_stem_input_grad_gen(Gc, dt, params + L0.w_off, dx, F, P.H, P.W, dx_accumulate, s));
-        else TRY(launch_stem_input_grad(Gc, dt, params + L0.w_off, dx, F, dx_accumulate, s));
-      }
-    }
-    TRY(join_side());     // a finished stage's gradients are complete on the main stream (all-reduce hook, Adam)
+    for (int bi = (int)P.blocks.size() - 1; bi >= 0; --bi)
+      if (P.blocks[bi].stage == 3 - st) TRY(block_backward(c, bi));
+    if (st == 3) TRY(stem_backward(c, dx, dx_accumulate));
+    TRY(R.side.join());     // a finished stage's gradients are complete on the main stream (all-reduce hook, Adam)
   }
-  *gd_io = role[0];
-  P.next_stage = stage_end == 4 ? 0 : stage_end;
+  R.next_stage = stage_end == 4 ? 0 : stage_end;
   return 0;
 }
 
@@ -1086,17 +1023,11 @@ int plan_stage_range(Plan* P, int stage, long long* off, long long* count) {
   return 0;
 }
 void plan_destroy(Plan* P) {
-  if (P->side) {
-    (void)hipStreamDestroy(P->side);
-    for (hipEvent_t ev : {P->ev_dy, P->ev_wg[0], P->ev_wg[1], P->ev_join})
-      if (ev) (void)hipEventDestroy(ev);
-  }
-  if (P->d_wt_tab) (void)hipFree(P->d_wt_tab);
-  if (P->d_wt_tile0) (void)hipFree(P->d_wt_tile0);
+  P->run.side.destroy();
+  if (P->run.d_wt_tab) (void)hipFree(P->run.d_wt_tab);
+  if (P->run.d_wt_tile0) (void)hipFree(P->run.d_wt_tile0);
   delete P;
 }
-int* plan_gd(Plan* P) { return &P->gd; }
-// per-plan option: 1 = BatchNorm-backward partials from the dgrad epilogues (EPI_BNRED), 0 = stand-alone reduce passes
 int plan_set_bn_pair(Plan* P, int on) { const int old = P->bn_pair; P->bn_pair = on ? 1 : 0; return old; }
 int plan_set_fuse_bnred(Plan* P, int on) { const int old = P->fuse_bnred; P->fuse_bnred = on ? 1 : 0; return old; }
 

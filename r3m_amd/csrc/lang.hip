@@ -8,18 +8,13 @@
 //   q0 (e0,eg) q1 (e0,es1) q2 (e0,es2) | q3 (e0,e0) q4 (e0,es0) q5 (e0,es1) | q6+3k+j: (e0[pi], other_j[pi]), pi = perm[3k+j],
 //   other_j = (eg, es1, es2)[j]
 // Parameter layout (flat, = state-dict order pred.{0,2,4,6,8}.{weight,bias}): W1[H][K1] b1[H] W2[H][H] b2 W3 b3 W4 b4 w5[H] b5[1]
-#include "common.h"
+#include "engine.h"
 #include "conv_dev.h"
 
 namespace r3m {
 
-int conv_forward_launch(const float* X, const float* W, float* Y, float* stats, const float* bias, int N, int Hi, int Wi, int Ci,
-                        int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
-int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, int N, int Hi, int Wi, int Ci, int Co, int k,
-                      int stride, int pad, int accumulate, int dt, hipStream_t s);
-size_t conv_wgrad_ws_floats(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dt);
-int launch_convert_bf16(const float* src, void* dst, long long n, hipStream_t s);
-int launch_transpose_w_bf16(const float* W, void* Wt, int Co, int T, int Ci, hipStream_t s);
+// a Linear(K -> H) over R rows is the 1x1 convolution of R one-pixel images
+static ConvGeom linear_geom(int R, int K, int H) { return {R, 1, 1, K, H, 1, 1, 0}; }
 
 __device__ __forceinline__ f32x4 ld4g(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
@@ -198,7 +193,7 @@ static LangDims lang_dims_rows(int R, int B, int D, int H, int LD) {
   long long wg = 0;
   for (int dt : {DT_F32, DT_BF16})
     for (int K : {d.K1, H}) {
-      const long long v = (long long)conv_wgrad_ws_floats(d.R, 1, 1, K, H, 1, 1, 0, dt);
+      const long long v = (long long)conv_wgrad_ws_floats(linear_geom(d.R, K, H), dt);
       if (v > wg) wg = v;
     }
   d.wgp = take(wg);
@@ -266,13 +261,13 @@ static int mlp_forward(const LangDims& d, const float* params, float* scores, fl
     if (dt == DT_BF16) {
       bf16_t* w16 = as16(ws + d.w16) + d.w[l];
       if (int e = launch_convert_bf16(params + d.w[l], w16, (long long)K * H, s)) return e;
-      if (int e = conv_forward_launch(in, reinterpret_cast<const float*>(w16), ws + d.Hh[l], nullptr, nullptr, d.R, 1, 1, K, H, 1, 1, 0, 0,
+      if (int e = conv_forward_launch(in, reinterpret_cast<const float*>(w16), ws + d.Hh[l], nullptr, nullptr, linear_geom(d.R, K, H), 0,
                                       DT_BF16, s))
         return e;
       const long long n8 = (long long)d.R * H / 8;
       hipLaunchKernelGGL(bias_relu16_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, s, as16(ws + d.Hh[l]), params + d.b[l], n8, H / 8);
       if (int e = check_launch("lang_bias_relu16")) return e;
-    } else if (int e = conv_forward_launch(in, params + d.w[l], ws + d.Hh[l], nullptr, params + d.b[l], d.R, 1, 1, K, H, 1, 1, 0,
+    } else if (int e = conv_forward_launch(in, params + d.w[l], ws + d.Hh[l], nullptr, params + d.b[l], linear_geom(d.R, K, H),
                                            EPI_BIAS | EPI_RELU, DT_F32, s))
       return e;
     in = ws + d.Hh[l];
@@ -297,10 +292,6 @@ int langrew_forward(const float* alle, const float* feats, const int* perm, cons
   if (int e = check_launch("lang_gather")) return e;
   return mlp_forward(d, params, scores, ws, dt, s);
 }
-
-int launch_transpose_w(const float* W, float* Wt, int Co, int T, int Ci, hipStream_t s);
-int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* add0, const float* add1, const unsigned* addbits,
-                      int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int dt, hipStream_t s);
 
 // Needs the workspace left by the forward (X and the four hidden activations).
 // dscore [R] -> parameter gradients (= or +=); returns the buffer holding dX [R, K1] (inside ws) through *dx_out
@@ -332,13 +323,13 @@ static int mlp_backward(const LangDims& d, const float* dscore, const float* par
   for (int l = 3; l >= 0; --l) {
     const float* in = l == 0 ? ws + d.X : ws + d.Hh[l - 1];
     const int K = l == 0 ? d.K1 : H;
-    if (int e = conv_wgrad_launch(in, dz, grads + d.w[l], wgp, d.R, 1, 1, K, H, 1, 1, 0, accumulate, dt, s)) return e;
+    if (int e = conv_wgrad_launch(in, dz, grads + d.w[l], wgp, linear_geom(d.R, K, H), accumulate, dt, s)) return e;
     if (int e = h16 ? launch_colsum(reinterpret_cast<const bf16_t*>(dz), nullptr, grads + d.b[l], ws + d.cs, d.R, H, accumulate, s)
                     : launch_colsum(dz, nullptr, grads + d.b[l], ws + d.cs, d.R, H, accumulate, s))
       return e;
     if (h16) {
       if (int e = launch_transpose_w_bf16(params + d.w[l], Wt, H, 1, K, s)) return e;
-      if (int e = conv_dgrad_launch(dz, Wt, nxt, nullptr, nullptr, nullptr, d.R, 1, 1, K, H, 1, 1, 0, 0, DT_BF16, s)) return e;
+      if (int e = conv_dgrad_launch(dz, Wt, nxt, nullptr, nullptr, nullptr, linear_geom(d.R, K, H), 0, DT_BF16, s)) return e;
       if (l > 0) {
         const long long n8 = (long long)d.R * H / 8;
         hipLaunchKernelGGL(relu_mask16_kernel, dim3(ceil_div(n8, 256)), dim3(256), 0, s, as16(nxt), reinterpret_cast<const bf16_t*>(in), n8);
@@ -346,7 +337,7 @@ static int mlp_backward(const LangDims& d, const float* dscore, const float* par
       }
     } else {
       if (int e = launch_transpose_w(params + d.w[l], Wt, H, 1, K, s)) return e;
-      if (int e = conv_dgrad_launch(dz, Wt, nxt, nullptr, l == 0 ? nullptr : in, nullptr, d.R, 1, 1, K, H, 1, 1, 0, l == 0 ? 0 : EPI_MASK_OUT, DT_F32, s))
+      if (int e = conv_dgrad_launch(dz, Wt, nxt, nullptr, l == 0 ? nullptr : in, nullptr, linear_geom(d.R, K, H), l == 0 ? 0 : EPI_MASK_OUT, DT_F32, s))
         return e;
     }
     float* t = dz; dz = nxt; nxt = t;

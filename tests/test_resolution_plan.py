@@ -234,3 +234,140 @@ def test_bf16_fused_inference_answers_from_the_route(L):
     assert L.r3m_debug_conv_fuses_affine(3, 28, 28, 256, 512, 1, 2, 0, AFFINE, 1) == 1
     assert L.r3m_debug_conv_fuses_affine(3, 28, 28, 128, 128, 3, 1, 1, AFFINE | STATS, 1) == 0
     assert L.r3m_debug_conv_fuses_affine(3, 28, 28, 128, 128, 1, 1, 0, AFFINE | STATS, 1) == 0
+
+
+# ---- the plan layout is pinned ---------------------------------------------------------------------------------------------------
+def _plan_fingerprint(L, size, dt, F, H, W):
+    """(arena bytes, hash of everything else the host-only queries tell), or ("refused", first five words of the message)"""
+    import hashlib
+    h = L.r3m_resnet_create_hw(size, F, dt, H, W)
+    if not h:
+        return ("refused", " ".join(L.r3m_last_error().decode().split()[:5]))
+    try:
+        rest = [L.r3m_resnet_num_params(h), L.r3m_resnet_num_buffers(h), _plan_convs(L, h)]
+        name = C.create_string_buffer(128)
+        kind, ndim, off = C.c_int(), C.c_int(), C.c_longlong()
+        shape = (C.c_int * 4)()
+        for i in range(L.r3m_resnet_num_tensors(h)):
+            assert L.r3m_resnet_tensor_info(h, i, name, 128, C.byref(kind), C.byref(off), C.byref(ndim), shape) == 0
+            rest.append((name.value.decode(), kind.value, off.value, ndim.value, tuple(shape)))
+        cnt = C.c_longlong()
+        for stage in range(4):
+            assert L.r3m_resnet_stage_range(h, stage, C.byref(off), C.byref(cnt)) == 0
+            rest.append((stage, off.value, cnt.value))
+        return (L.r3m_resnet_arena_bytes(h), hashlib.sha256(repr(rest).encode()).hexdigest()[:16])
+    finally:
+        L.r3m_resnet_destroy(h)
+
+
+_LAYOUT_HW = [(224, 224), (32, 32), (97, 161), (512, 512)]
+_LAYOUT_F = [1, 5, 80, 1280]
+# (size, dtype, F, H, W) -> _plan_fingerprint, recorded from the library built at the parent commit of the engine refactor
+PLAN_LAYOUT = {
+    (18, 0, 1, 224, 224): (102091008, 'db79de152c25154a'),
+    (18, 0, 1, 32, 32): (68591872, '629a58ddb2775a4b'),
+    (18, 0, 1, 97, 161): (79204352, 'bfda50e348010cf7'),
+    (18, 0, 1, 512, 512): (246626048, '78720a51cbbead6b'),
+    (18, 0, 5, 224, 224): (238946048, 'db79de152c25154a'),
+    (18, 0, 5, 32, 32): (71376640, '629a58ddb2775a4b'),
+    (18, 0, 5, 97, 161): (124506880, 'bfda50e348010cf7'),
+    (18, 0, 5, 512, 512): (987797248, '78720a51cbbead6b'),
+    (18, 0, 80, 224, 224): (2934959872, 'db79de152c25154a'),
+    (18, 0, 80, 32, 32): (123735808, '629a58ddb2775a4b'),
+    (18, 0, 80, 97, 161): (1028413184, 'bfda50e348010cf7'),
+    (18, 0, 80, 512, 512): (14545000192, '78720a51cbbead6b'),
+    (18, 0, 1280, 224, 224): (44041606912, 'db79de152c25154a'),
+    (18, 0, 1280, 32, 32): (987797248, '629a58ddb2775a4b'),
+    (18, 0, 1280, 97, 161): (14741859072, 'bfda50e348010cf7'),
+    (18, 0, 1280, 512, 512): ('refused', 'resnet: 1280 frames of 512'),
+    (18, 1, 1, 224, 224): (108330496, 'db79de152c25154a'),
+    (18, 1, 1, 32, 32): (68284928, '629a58ddb2775a4b'),
+    (18, 1, 1, 97, 161): (73646848, 'bfda50e348010cf7'),
+    (18, 1, 1, 512, 512): (158321664, '78720a51cbbead6b'),
+    (18, 1, 5, 224, 224): (177650688, 'db79de152c25154a'),
+    (18, 1, 5, 32, 32): (69689344, '629a58ddb2775a4b'),
+    (18, 1, 5, 97, 161): (96559104, 'bfda50e348010cf7'),
+    (18, 1, 5, 512, 512): (546122752, '78720a51cbbead6b'),
+    (18, 1, 80, 224, 224): (1533576192, 'db79de152c25154a'),
+    (18, 1, 80, 32, 32): (96166912, '629a58ddb2775a4b'),
+    (18, 1, 80, 97, 161): (580645376, 'bfda50e348010cf7'),
+    (18, 1, 80, 512, 512): (7379725312, '78720a51cbbead6b'),
+    (18, 1, 1280, 224, 224): (22329633792, 'db79de152c25154a'),
+    (18, 1, 1280, 32, 32): (546122752, '629a58ddb2775a4b'),
+    (18, 1, 1280, 97, 161): (7479091712, 'bfda50e348010cf7'),
+    (18, 1, 1280, 512, 512): ('refused', 'resnet: 1280 frames of 512'),
+    (34, 0, 1, 224, 224): (152699904, '3d65c5ab50d5a2c3'),
+    (34, 0, 1, 32, 32): (109293568, 'b801d792f71b0ebc'),
+    (34, 0, 1, 97, 161): (123354368, 'c4f89324cb5e2b76'),
+    (34, 0, 1, 512, 512): (339959040, '81adb14a5a2a4a50'),
+    (34, 0, 5, 224, 224): (330009344, '3d65c5ab50d5a2c3'),
+    (34, 0, 5, 32, 32): (112903936, 'b801d792f71b0ebc'),
+    (34, 0, 5, 97, 161): (183274496, 'c4f89324cb5e2b76'),
+    (34, 0, 5, 512, 512): (1292483840, '81adb14a5a2a4a50'),
+    (34, 0, 80, 224, 224): (3784542464, '3d65c5ab50d5a2c3'),
+    (34, 0, 80, 32, 32): (180742400, 'b801d792f71b0ebc'),
+    (34, 0, 80, 97, 161): (1361252864, 'c4f89324cb5e2b76'),
+    (34, 0, 80, 512, 512): (18812566784, '81adb14a5a2a4a50'),
+    (34, 0, 1280, 224, 224): (57027509504, '3d65c5ab50d5a2c3'),
+    (34, 0, 1280, 32, 32): (1292483840, 'b801d792f71b0ebc'),
+    (34, 0, 1280, 97, 161): (19459873024, 'c4f89324cb5e2b76'),
+    (34, 0, 1280, 512, 512): ('refused', 'resnet: 1280 frames of 512'),
+    (34, 1, 1, 224, 224): (153936640, '3d65c5ab50d5a2c3'),
+    (34, 1, 1, 32, 32): (108899072, 'b801d792f71b0ebc'),
+    (34, 1, 1, 97, 161): (115999232, 'c4f89324cb5e2b76'),
+    (34, 1, 1, 512, 512): (225455104, '81adb14a5a2a4a50'),
+    (34, 1, 5, 224, 224): (243640832, '3d65c5ab50d5a2c3'),
+    (34, 1, 5, 32, 32): (110719488, 'b801d792f71b0ebc'),
+    (34, 1, 5, 97, 161): (146277120, 'c4f89324cb5e2b76'),
+    (34, 1, 5, 512, 512): (719752192, '81adb14a5a2a4a50'),
+    (34, 1, 80, 224, 224): (1981765632, '3d65c5ab50d5a2c3'),
+    (34, 1, 80, 32, 32): (144996352, 'b801d792f71b0ebc'),
+    (34, 1, 80, 97, 161): (768460544, 'c4f89324cb5e2b76'),
+    (34, 1, 80, 512, 512): (9550154752, '81adb14a5a2a4a50'),
+    (34, 1, 1280, 224, 224): (28893023232, '3d65c5ab50d5a2c3'),
+    (34, 1, 1280, 32, 32): (719752192, 'b801d792f71b0ebc'),
+    (34, 1, 1280, 97, 161): (9876490752, 'c4f89324cb5e2b76'),
+    (34, 1, 1280, 512, 512): ('refused', 'resnet: 1280 frames of 512'),
+    (50, 0, 1, 224, 224): (218911488, '40ac808507dd3b5a'),
+    (50, 0, 1, 32, 32): (119702272, 'a3790ff1911ae5a9'),
+    (50, 0, 1, 97, 161): (152825088, '7bedf10d7a98a333'),
+    (50, 0, 1, 512, 512): (647027712, '774c9b1c63c7d9af'),
+    (50, 0, 5, 224, 224): (624277248, '40ac808507dd3b5a'),
+    (50, 0, 5, 32, 32): (127966976, 'a3790ff1911ae5a9'),
+    (50, 0, 5, 97, 161): (293701120, '7bedf10d7a98a333'),
+    (50, 0, 5, 512, 512): (2791062528, '774c9b1c63c7d9af'),
+    (50, 0, 80, 224, 224): (8354982912, '40ac808507dd3b5a'),
+    (50, 0, 80, 32, 32): (283020288, 'a3790ff1911ae5a9'),
+    (50, 0, 80, 97, 161): (2990109184, '7bedf10d7a98a333'),
+    (50, 0, 80, 512, 512): (42651958272, '774c9b1c63c7d9af'),
+    (50, 0, 1280, 224, 224): (130016689152, '40ac808507dd3b5a'),
+    (50, 0, 1280, 32, 32): (2791062528, 'a3790ff1911ae5a9'),
+    (50, 0, 1280, 97, 161): (45383710720, '7bedf10d7a98a333'),
+    (50, 0, 1280, 512, 512): ('refused', 'resnet: 1280 frames of 512'),
+    (50, 1, 1, 224, 224): (191965184, '40ac808507dd3b5a'),
+    (50, 1, 1, 32, 32): (118803456, 'a3790ff1911ae5a9'),
+    (50, 1, 1, 97, 161): (135514624, '7bedf10d7a98a333'),
+    (50, 1, 1, 512, 512): (385008896, '774c9b1c63c7d9af'),
+    (50, 1, 5, 224, 224): (396735488, '40ac808507dd3b5a'),
+    (50, 1, 5, 32, 32): (122972160, 'a3790ff1911ae5a9'),
+    (50, 1, 5, 97, 161): (206601984, '7bedf10d7a98a333'),
+    (50, 1, 5, 512, 512): (1480467712, '774c9b1c63c7d9af'),
+    (50, 1, 80, 224, 224): (4292351232, '40ac808507dd3b5a'),
+    (50, 1, 80, 32, 32): (201225472, 'a3790ff1911ae5a9'),
+    (50, 1, 80, 97, 161): (1594710272, '7bedf10d7a98a333'),
+    (50, 1, 80, 512, 512): (21582652672, '774c9b1c63c7d9af'),
+    (50, 1, 1280, 224, 224): (65723442432, '40ac808507dd3b5a'),
+    (50, 1, 1280, 32, 32): (1480467712, 'a3790ff1911ae5a9'),
+    (50, 1, 1280, 97, 161): (22957523712, '7bedf10d7a98a333'),
+    (50, 1, 1280, 512, 512): ('refused', 'resnet: 1280 frames of 512'),
+}
+
+
+def test_plan_layout_is_unchanged(L):
+    """Arena bytes, parameter / buffer counts, the conv table, the tensor table and the stage ranges of ResNet-18/34/50 x fp32/bf16 x
+    F in {1, 5, 80, 1280} x four frame sizes equal what the library gave before the engine was refactored (and a combination it
+    refused is still refused with the same opening words). PLAN_LAYOUT holds recorded results of that earlier library, not of the
+    code under test."""
+    assert len(PLAN_LAYOUT) == 3 * 2 * len(_LAYOUT_F) * len(_LAYOUT_HW)
+    for (size, dt, F, H, W), want in PLAN_LAYOUT.items():
+        assert _plan_fingerprint(L, size, dt, F, H, W) == want, (size, dt, F, H, W)

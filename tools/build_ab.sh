@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B builds for same-box comparisons (gitignored *.so; they travel with gpurun):
+# A/B builds for same-box comparisons (gitignored *.so):
 #   r3m_amd/lib/libr3m_hip_base.so   = csrc/ of a git ref (default HEAD)             -> R3M_HIP_LIB=... python bench.py
 #   r3m_amd/lib/libr3m_hip_probes.so = the working tree with -DR3M_PROBES (environment switches live)
 #   r3m_amd/lib/libr3m_hip_<name>.so = the working tree with extra compiler flags (compile-time experiment switches)
@@ -7,20 +7,9 @@
 set -e
 ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 REF="${1:-HEAD}"
-HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"
-build_tree() {   # $1 = source root holding r3m_amd/csrc + include, $2 = output .so, $3.. = extra flags
+build_tree() {   # $1 = source root holding r3m_amd/csrc + include, $2 = output .so, $3.. = extra flags (one source list: csrc/build.sh)
   local src="$1" out="$2"; shift 2
-  local obj; obj="$(mktemp -d)"
-  local pids=()
-  for f in conv conv_pw wgrad_win conv_bf16 conv_row16 conv_pw16 stem_bf16 bn loss adam lang augment engine capi; do
-    [ -f "$src/r3m_amd/csrc/$f.hip" ] || continue
-    local extra=""; [ "$f" = conv_pw16 ] && extra="-mllvm -amdgpu-atomic-optimizer-strategy=None"
-    $HIPCC $FLAGS $extra "$@" -c "$src/r3m_amd/csrc/$f.hip" -o "$obj/$f.o" & pids+=($!)
-  done
-  for p in "${pids[@]}"; do wait "$p"; done
-  $HIPCC --offload-arch=gfx950 -shared -fPIC -o "$out" "$obj"/*.o
-  rm -rf "$obj"; echo "built $out"
+  R3M_BUILD_SRC="$src" R3M_BUILD_OUT="$out" bash "$ROOT/r3m_amd/csrc/build.sh" "$@"
 }
 if [ "$REF" != "none" ]; then
   T="$(mktemp -d)"; (cd "$ROOT" && git archive "$REF" r3m_amd/csrc include | tar -x -C "$T")
