@@ -8,7 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from util import nchw, nhwc, rel_err, rnd
+from util import check_conv_bf16, nchw, nhwc, rel_err, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -47,53 +47,7 @@ def _ids(c):
 @pytest.mark.parametrize("case", CONV_CASES, ids=_ids)
 def test_conv_bf16_fwd_dgrad_wgrad(hip, case):
     N, H, Ci, Co, k, s, p = case
-    x = q(rnd((N, Ci, H, H), 1))
-    w = q(rnd((Co, Ci, k, k), 2, -0.2, 0.2))
-    xr = x.double().requires_grad_(True)
-    wr = w.double().requires_grad_(True)
-    y_ref = F.conv2d(xr, wr, stride=s, padding=p)
-    Ho = y_ref.shape[2]
-    dy = q(rnd(tuple(y_ref.shape), 3))
-    y_ref.backward(dy.double())
-
-    xd = nhwc(x).to(DEV).to(torch.bfloat16)
-    w32 = w.permute(0, 2, 3, 1).contiguous().to(DEV)              # fp32 master, OHWI
-    wd = torch.empty((Co, k, k, Ci), dtype=torch.bfloat16, device=DEV)
-    assert hip.r3m_convert_bf16(w32.data_ptr(), wd.data_ptr(), w32.numel(), st()) == 0, hip.r3m_last_error()
-    torch.testing.assert_close(wd.float().cpu(), w.permute(0, 2, 3, 1), rtol=0, atol=0)
-    yd = torch.full((N, Ho, Ho, Co), float("nan"), dtype=torch.bfloat16, device=DEV)
-    rows = hip.r3m_conv2d_stats_rows(N, H, H, Co, k, s, p)
-    stats = torch.zeros((rows, 2, Co), device=DEV)
-    rc = hip.r3m_conv2d_fwd_dt(xd.data_ptr(), wd.data_ptr(), yd.data_ptr(), stats.data_ptr(), N, H, H, Ci, Co, k, s, p, BF16, st())
-    assert rc == 0, hip.r3m_last_error()
-    yr = y_ref.detach()
-    e_max, e_l2 = rel_err(nchw(yd.float().cpu()).numpy(), yr.numpy())
-    assert e_max < EPS_BF16 and e_l2 < EPS_BF16 / 2, f"conv fwd bf16 max-rel {e_max} l2 {e_l2}"
-    # BatchNorm partials come from the fp32 accumulators (before the bf16 rounding of y)
-    np.testing.assert_allclose(stats[:, 0].double().sum(0).cpu().numpy(), yr.sum((0, 2, 3)).numpy(), rtol=1e-4,
-                               atol=1e-3 * float(yr.abs().max()))
-    np.testing.assert_allclose(stats[:, 1].double().sum(0).cpu().numpy(), (yr * yr).sum((0, 2, 3)).numpy(), rtol=1e-4)
-
-    # dgrad
-    dyd = nhwc(dy).to(DEV).to(torch.bfloat16)
-    dxd = torch.full((N, H, H, Ci), float("nan"), dtype=torch.bfloat16, device=DEV)
-    wsb = hip.r3m_conv2d_dgrad_workspace_bytes(Ci, Co, k)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-    rc = hip.r3m_conv2d_dgrad_dt(dyd.data_ptr(), w32.data_ptr(), dxd.data_ptr(), ws.data_ptr(), wsb, N, H, H, Ci, Co, k, s, p, BF16, st())
-    assert rc == 0, hip.r3m_last_error()
-    e_max, e_l2 = rel_err(nchw(dxd.float().cpu()).numpy(), xr.grad.numpy())
-    assert e_max < EPS_BF16 and e_l2 < EPS_BF16 / 2, f"conv dgrad bf16 max-rel {e_max} l2 {e_l2}"
-
-    # wgrad: fp32 output (+ accumulate)
-    dwd = torch.full((Co, k, k, Ci), float("nan"), device=DEV)
-    wsb = hip.r3m_conv2d_wgrad_workspace_bytes_dt(N, H, H, Ci, Co, k, s, p, BF16)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-    for acc in (0, 1):
-        rc = hip.r3m_conv2d_wgrad_dt(xd.data_ptr(), dyd.data_ptr(), dwd.data_ptr(), ws.data_ptr(), wsb, N, H, H, Ci, Co, k, s, p, acc,
-                                     BF16, st())
-        assert rc == 0, hip.r3m_last_error()
-        e_max, _ = rel_err(dwd.cpu().permute(0, 3, 1, 2).numpy(), (acc + 1) * wr.grad.numpy())
-        assert e_max < 5e-5, f"conv wgrad bf16 (acc={acc}) max-rel {e_max}"
+    check_conv_bf16(hip, (N, H, H, Ci, Co, k, s, p))      # body shared with tests/test_gpu_ops_hw.py (Hi != Wi)
 
 
 def test_conv_bf16_is_transpose_safe(hip):

@@ -6,6 +6,9 @@ import ctypes as C
 import pytest
 import torch
 
+import route_sig
+from route_sig import ACCUM, AFFINE, BNRED, MASKED_ADD, RELU, STATS
+
 SWEEP = [(s, s) for s in (32, 33, 47, 84, 96, 127, 128, 160, 223, 225, 256, 320, 511, 512)] + [(96, 160), (97, 131), (160, 96),
                                                                                               (33, 512), (512, 47)]
 
@@ -36,13 +39,7 @@ def _torch_convs(size, H, W):
     return out
 
 
-def _plan_convs(L, h):
-    v = [C.c_int() for _ in range(9)]
-    out = []
-    for i in range(L.r3m_resnet_num_convs(h)):
-        assert L.r3m_resnet_conv_info(h, i, *[C.byref(x) for x in v]) == 0, L.r3m_last_error()
-        out.append(tuple(x.value for x in v))
-    return out
+_plan_convs = route_sig.plan_convs          # [(Ci, Co, k, stride, pad, Hi, Wi, Ho, Wo)], conv1 first (shared with tests/test_dispatch.py)
 
 
 @pytest.mark.parametrize("size", [18, 34, 50])
@@ -142,7 +139,6 @@ def test_hip_resnet_refuses_out_of_range_frames_on_the_cpu():
 
 
 # ---- every launch of the swept plans runs a kernel built for the epilogue the engine asks of it -----------------------------------
-STATS, ACCUM, MASKED_ADD, BNRED, AFFINE, RELU = 1, 2, 4, 64, 128, 16
 _GG_SWITCH = {0, STATS, ACCUM, MASKED_ADD, 8, RELU, 8 | RELU, 32, BNRED, BNRED | MASKED_ADD}       # csrc/conv.hip GG_EPI_SWITCH
 _PW = {0, STATS, ACCUM, BNRED, MASKED_ADD, BNRED | MASKED_ADD, AFFINE, AFFINE | RELU, AFFINE | ACCUM | RELU}   # conv_pw.hip pw_flags_ok
 _BF16 = {0, STATS, ACCUM, MASKED_ADD, BNRED, BNRED | MASKED_ADD, AFFINE | RELU, AFFINE | ACCUM | RELU}
@@ -156,70 +152,20 @@ BUILT = {
 }
 
 
-def _blocks(L, h, size):
-    """[(convs of the block in order, downsample conv or None)] from the plan's conv table (torchvision module order)"""
-    convs = _plan_convs(L, h)[1:]
-    n = 3 if size == 50 else 2
-    out, i = [], 0
-    while i < len(convs):
-        body = convs[i:i + n]
-        i += n
-        ds = None
-        if i < len(convs) and convs[i][2] == 1 and convs[i][0] == body[0][0] and convs[i][1] == body[-1][1] and \
-                (convs[i][3] == 2 or convs[i][0] != convs[i][1]):
-            ds = convs[i]
-            i += 1
-        out.append((body, ds))
-    return out
-
-
 @pytest.mark.parametrize("size", [18, 34, 50])
 @pytest.mark.parametrize("dt", [0, 1])
 def test_every_launch_has_a_kernel_built_for_its_epilogue(L, size, dt):
     """forward (training: statistics; eval with a backward: plain), input gradients with the flags csrc/engine.hip plan_backward asks
     (fp32 plans fuse the BatchNorm-backward partials: 64; bf16 plans do not), and fused inference (r3m_debug_conv_fuses_affine: where
     it answers 1 the fused launch's route must build the flags; where 0 the engine runs the unfused sequence, plain forwards)."""
-    buf = (C.c_int * 8)()
-
-    def routes(F, c, dgrad, flags, bits=0):
-        Ci, Co, k, s, p, Hi, Wi = c[:7]
-        n = L.r3m_debug_conv_route(F, Hi, Wi, Ci, Co, k, s, p, dgrad, flags, bits, dt, buf, 8)
-        assert n >= 1, (c, dgrad, flags, L.r3m_last_error())
-        return list(buf[:n])
-
-    def check(F, c, dgrad, flags, bits=0):
-        for r in routes(F, c, dgrad, flags, bits):
-            assert r in BUILT and flags in BUILT[r], f"resnet{size} dt={dt} conv {c} dgrad={dgrad} flags={flags}: route {r}"
-
-    fuse_bnred = dt == 0
     for H, W in SWEEP:
         for F in (1, 3):
-            h = L.r3m_resnet_create_hw(size, F, dt, H, W)
-            assert h, L.r3m_last_error()
-            try:
-                blocks = _blocks(L, h, size)
-                for bi, (body, ds) in enumerate(blocks):
-                    for c in body + ([ds] if ds else []):
-                        check(F, c, 0, STATS)
-                        check(F, c, 0, 0)
-                    # input gradients (plan_backward)
-                    for j in range(len(body) - 1, 0, -1):
-                        check(F, body[j], 1, BNRED if fuse_bnred else 0)
-                    if ds:
-                        check(F, body[0], 1, 0)
-                        check(F, ds, 1, ACCUM)
-                    else:
-                        check(F, body[0], 1, MASKED_ADD | (BNRED if fuse_bnred and bi > 0 else 0), 1 if bi > 0 else 0)
-                    # inference forward (plan_forward_src, training = 2)
-                    want = [(c, AFFINE | RELU) for c in body[:-1]] + [(body[-1], AFFINE | ACCUM | RELU)] + ([(ds, AFFINE)] if ds else [])
-                    fused = all(L.r3m_debug_conv_fuses_affine(F, c[5], c[6], c[0], c[1], c[2], c[3], c[4], fl, dt) == 1 for c, fl in want)
-                    for c, fl in want:
-                        if fused:
-                            check(F, c, 0, fl)
-                        else:
-                            check(F, c, 0, 0)
-            finally:
-                L.r3m_resnet_destroy(h)
+            # the launches and their flags: route_sig.engine_launches (one derivation, shared with the coverage test of test_dispatch.py)
+            for (case, dgrad, flags, bits) in route_sig.engine_launches(L, size, dt, F, H, W):
+                rs = route_sig.routes(L, case, dgrad, flags, bits, dt)
+                assert len(rs) >= 1, (case, dgrad, flags, L.r3m_last_error())
+                for r in rs:
+                    assert r in BUILT and flags in BUILT[r], f"resnet{size} dt={dt} conv {case} dgrad={dgrad} flags={flags}: route {r}"
 
 
 def test_bf16_fused_inference_answers_from_the_route(L):
