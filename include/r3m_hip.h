@@ -58,6 +58,18 @@ int r3m_debug_conv_route(int N, int H, int W, int Ci, int Co, int k, int stride,
    output from the convolution itself; 0 when the engine runs that block's unfused sequence instead. r3m_debug_conv_route with the same
    flags (dgrad = 0) reports the route the fused launch takes. */
 int r3m_debug_conv_fuses_affine(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int flags, int dtype);
+/* Diagnostic, runs without a GPU: the launch geometry the BatchNorm passes of csrc/bn.hip pick for a [rows][C] tensor of `dtype` (C a
+   power of two >= 4) -- computed by the helpers the launchers themselves call, nothing is launched. out[0..13]:
+     0-2   forward apply (r3m_bn_act_fwd_dt): elements per lane (4 | 8), items per block (span: 256 | 1024), blocks
+     3-7   backward reduce (first pass of r3m_bn_bwd_dt): elements per lane, rows per block, rows per pass (rpp: the rows a block reads at
+           once), column blocks (2 for fp32 at C = 2048), blocks = partial rows
+     8-10  backward apply (second pass, also the paired one): elements per lane, span, blocks
+     11    slices of the fp64 reduce over the backward's partial rows (out[7])
+     12    slices of that reduce when `rows` itself is a partial-row count (r3m_bn_train_coeffs with stats_rows = rows,
+           r3m_bn_bwd_from_partials_dt with partial_rows = rows)
+     13    the cap on the slice count for this C (256 at C = 64 ... 64 at C = 2048)
+   Returns the number of ints written (14), -1 on error (cap < 14, bad rows / C / dtype). */
+int r3m_debug_bn_geometry(long long rows, int C, int dtype, int* out, int cap);
 void r3m_profile_enable(int on);
 /* which kernel classes are bracketed while profiling is on: bit k = class k (0 conv fwd/dgrad 128-wide, 1 64-wide, 2 / 3 the weight
    gradients); default all. Each bracket costs the stream two event records. Returns the old mask. */
@@ -157,6 +169,12 @@ int r3m_stem_input_grad(const void* dz, int dz_dtype, const float* w_ohwi, float
 /* BatchNorm2d(eps, momentum) train/eval + ReLU + residual add (torchvision BasicBlock/Bottleneck).
  * coef: [4][C] = mean, invstd, scale = gamma*invstd, shift = beta - mean*scale. */
 size_t r3m_bn_workspace_bytes(long long rows, int C);
+/* stats: [stats_rows][2][C] fp32 partial sums / sums of squares of y over any blocking of the rows (a conv epilogue's); they are added up
+ * in fp64: mean = sum / count, var = max(sumsq / count - mean^2, 0) (biased), coef from their fp32 values. running_mean / running_var
+ * (both or neither; NULL: not updated) move by `momentum` towards mean and var * count / (count - 1).
+ * count = 1 (one frame at 32 x 32 reaches it in layer4; torch refuses it in training mode): defined here as the variance of the single
+ * value -- 0 up to the rounding of the partials, never negative -- with the unbiased factor taken as 1 instead of 1 / 0, so invstd is
+ * at most 1 / sqrt(eps) and every output, the running statistics included, stays finite. */
 int r3m_bn_train_coeffs(const float* stats, int stats_rows, long long count, const float* gamma, const float* beta,
                         float* running_mean, float* running_var, float momentum, float eps, float* coef, void* workspace,
                         size_t workspace_bytes, int C, r3m_stream_t stream);
@@ -264,6 +282,24 @@ int r3m_bn_act_fwd_dt(const void* y, const float* coef, const void* r, const voi
 int r3m_bn_bwd_dt(const void* dz, const void* zmask, const unsigned* zbits, const void* y, const float* coef, float* dgamma,
                   float* dbeta, void* dy, void* workspace, size_t workspace_bytes, long long rows, int C, int use_batch_stats,
                   int accumulate, int dtype, r3m_stream_t stream);
+/* The backward of the TWO BatchNorms that feed a downsample block's add + ReLU, out = relu(bn_a(y_a) + bn_b(y_b)), as the engine runs it
+ * with r3m_resnet_set_bn_pair on (tests): both see g = dz * [zbits] (mask bits of the block output, required). The first passes run as
+ * one launch where the library has one (bf16, C a multiple of 8), else one after the other; the second passes always run as one launch
+ * that reads dz and the bits once. coef_a / coef_b: [6][C] -- rows 0-3 as r3m_bn_*_coeffs write them, rows 4 and 5 RECEIVE c1 = mean(g)
+ * and c2 = mean(g yhat) (0 with use_batch_stats = 0), the engine's coefficient block. dy_a / dy_b equal two r3m_bn_bwd_dt calls bit for
+ * bit; dgamma / dbeta equal them bit for bit where the first passes ran one after the other, to rounding where the joint one ran.
+ * workspace = r3m_bn_pair_workspace_bytes(rows, C). C >= 8. */
+size_t r3m_bn_pair_workspace_bytes(long long rows, int C);
+int r3m_bn_bwd_pair_dt(const void* dz, const unsigned* zbits, const void* y_a, float* coef_a, const void* y_b, float* coef_b,
+                       float* dgamma_a, float* dbeta_a, void* dy_a, float* dgamma_b, float* dbeta_b, void* dy_b, void* workspace,
+                       size_t workspace_bytes, long long rows, int C, int use_batch_stats, int accumulate, int dtype, r3m_stream_t stream);
+/* BatchNorm backward whose first pass a dgrad epilogue already ran (the fp32 plans' default schedule, tests): partials
+ * [partial_rows][2][C] as r3m_conv2d_dgrad_bnred_dt writes them -- sum(g) and sum(g (y - mean)) over any blocking of the rows -- are
+ * added up in fp64, the second sum times invstd gives sum(g yhat); then dgamma / dbeta (accumulate: 0 writes, 1 adds) and the second
+ * pass dy, as r3m_bn_bwd_dt. The mask comes as zbits or, when NULL, is recomputed from y. workspace = r3m_bn_workspace_bytes(rows, C). */
+int r3m_bn_bwd_from_partials_dt(const void* dz, const unsigned* zbits, const void* y, const float* coef, const float* partials,
+                                int partial_rows, float* dgamma, float* dbeta, void* dy, void* workspace, size_t workspace_bytes,
+                                long long rows, int C, int use_batch_stats, int accumulate, int dtype, r3m_stream_t stream);
 /* Stem tail fused (what the engine runs after conv1): z = relu(bn(y)) is pooled on the fly — the activated tensor and its
  * gradient, the two largest tensors of the network, are never written. Same arithmetic as r3m_bn_act_fwd + r3m_maxpool_fwd and
  * r3m_maxpool_bwd + r3m_bn_bwd (mask recomputed from y); workspace = r3m_bn_workspace_bytes(N*Hi*Wi, C). */

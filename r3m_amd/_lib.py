@@ -30,6 +30,7 @@ SIGNATURES = {
     "r3m_debug_set_fused_inference": (c_i, [c_i]),
     "r3m_debug_conv_route": (c_i, [c_i] * 12 + [C.POINTER(c_i), c_i]),
     "r3m_debug_conv_fuses_affine": (c_i, [c_i] * 10),
+    "r3m_debug_bn_geometry": (c_i, [c_ll, c_i, c_i, C.POINTER(c_i), c_i]),
     "r3m_profile_enable": (None, [c_i]),
     "r3m_profile_classes": (C.c_uint, [C.c_uint]),
     "r3m_profile_collect": (c_i, [C.POINTER(c_d), C.POINTER(c_ll), C.POINTER(c_d)]),
@@ -102,6 +103,9 @@ SIGNATURES = {
     "r3m_stem_conv_wgrad_bf16": (c_i, [c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_f]),
     "r3m_bn_act_fwd_dt": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_ll, c_i, c_i, c_f, c_i, c_f]),
     "r3m_bn_bwd_dt": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_ll, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_bn_pair_workspace_bytes": (c_sz, [c_ll, c_i]),
+    "r3m_bn_bwd_pair_dt": (c_i, [c_f] * 13 + [c_sz, c_ll, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_bn_bwd_from_partials_dt": (c_i, [c_f] * 5 + [c_i] + [c_f] * 4 + [c_sz, c_ll, c_i, c_i, c_i, c_i, c_f]),
     "r3m_bn_relu_maxpool_fwd_dt": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_bn_maxpool_bwd_dt": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_maxpool_fwd_dt": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f]),

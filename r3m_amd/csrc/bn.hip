@@ -100,11 +100,15 @@ __global__ __launch_bounds__(256) void bn_stats_reduce_kernel(const float* __res
 // Slices of the partial-row reduce: enough blocks for narrow layers with MANY rows (64 channels at 56 x 56 x 1280 frames: 62 720
 // EPI_BNRED rows, one column block — 64 slices left 192 CUs idle and a 245-row serial walk per thread), within the accumulator
 // buffer of 64 x 2 x 2048 doubles (S * C <= 131072).
-static inline int reduce_slices(int rows, int C) {
-  int s = (rows + 15) / 16;
+static inline int slice_cap(int C) {
   int cap = 131072 / (C > 0 ? C : 1);
   if (cap > 256) cap = 256;
   if (cap < 64) cap = 64;
+  return cap;
+}
+static inline int reduce_slices(int rows, int C) {
+  int s = (rows + 15) / 16;
+  const int cap = slice_cap(C);
   if (s > cap) s = cap;
   if (s < 1) s = 1;
   return s;
@@ -112,10 +116,7 @@ static inline int reduce_slices(int rows, int C) {
 
 // bytes of the fp64 slice accumulator for C channels (the largest slice count reduce_slices can pick for that C)
 size_t bn_acc_bytes(int C) {
-  int cap = 131072 / (C > 0 ? C : 1);
-  if (cap > 256) cap = 256;
-  if (cap < 64) cap = 64;
-  return (size_t)cap * 2 * C * 8;
+  return (size_t)slice_cap(C) * 2 * C * 8;
 }
 
 // acc must hold 131072 * 2 doubles (64 slices x 2 x 2048 channels, or more slices of fewer channels); the slice count is a pure function of the partial-row count (reduce_slices), so
@@ -345,22 +346,30 @@ static inline int bn_span(int cv, int items) {
   if (cv > 256 || 256 % cv != 0) items = 1;
   return 256 * items;
 }
+// The span each elementwise launch picks, in one place: the launchers below and bn_debug_geometry (r3m_debug_bn_geometry) call these.
+// v8: the 8-wide bf16 kernels (C a multiple of 8), else the 4-wide ones.
+static inline bool fwd_v8(int dt, int C) { return dt == DT_BF16 && C >= 8; }
+static inline int fwd_span(int dt, int C) { return fwd_v8(dt, C) ? bn_span(C / 8, C >= 2048 ? 4 : 1) : bn_span(C / 4, 1); }
+static inline int apply_span(bool v8, int C) { return v8 ? bn_span(C / 8, 4) : bn_span(C / 4, C >= 512 ? 4 : 1); }
+static inline int span_grid(long long items, int span) { return ceil_div(items, span); }   // blocks of a span-wide elementwise launch
+static inline long long bn_items(long long rows, int C, int vec) { return rows * C / vec; }  // 16-byte items (vec elements each) of [rows][C]
+static inline int col_blocks(int C, int vec, int cpb) { return ceil_div(C / vec, cpb); }      // gridDim.y of the backward reduce launches
 
 int launch_bn_act_fwd(const void* Yv, const float* scale, const float* shift, const void* Rv, const float* scale2,
                       const float* shift2, void* Zv, long long rows, int C, int relu, unsigned* maskbits, int dt, hipStream_t s) {
   R3M_REQUIRE(is_pow2(C) && C >= 4, "bn_act_fwd: C=%d must be a power of two >= 4", C);
   R3M_REQUIRE(!maskbits || (rows * C / 4) % 8 == 0, "bn_act_fwd: bit mask needs rows*C to be a multiple of 32");
-  const long long n4 = rows * C / 4;
+  const long long n4 = bn_items(rows, C, 4);
   const int c4mask = C / 4 - 1;
-  const int span = bn_span(C / 4, 1);
-  const int grid = ceil_div(n4, span);
-  if (dt == DT_BF16 && C >= 8) {
+  const int span = fwd_span(dt, C);
+  const int grid = span_grid(n4, span);
+  if (fwd_v8(dt, C)) {
     const bf16_t* Y = static_cast<const bf16_t*>(Yv);
     const bf16_t* R = static_cast<const bf16_t*>(Rv);
     bf16_t* Z = static_cast<bf16_t*>(Zv);
-    const long long n8 = rows * C / 8;
-    const int span8 = bn_span(C / 8, C >= 2048 ? 4 : 1);
-    const int g8 = ceil_div(n8, span8), c8mask = C / 8 - 1;
+    const long long n8 = bn_items(rows, C, 8);
+    const int span8 = span;
+    const int g8 = span_grid(n8, span8), c8mask = C / 8 - 1;
     if (R && scale2)
       hipLaunchKernelGGL((bn_act_fwd16_kernel<2>), dim3(g8), dim3(256), 0, s, Y, scale, shift, R, scale2, shift2, Z, n8, c8mask, relu, maskbits, span8);
     else if (R)
@@ -493,18 +502,21 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce16_kernel(const bf16_t* __re
 
 static inline bool use_v8(int dt, int C) { return dt == DT_BF16 && C % 8 == 0; }
 
-static inline void bwd_geometry16(long long rows, int C, int* cpb8, int* rpb, int* nblk) {
+// cpb: channel vectors per block, rpp (optional): rows a block reads per pass, rpb: rows per block, nblk: blocks = partial rows
+static inline void bwd_geometry16(long long rows, int C, int* cpb8, int* rpb, int* nblk, int* rpp_out = nullptr) {
   int c8 = C / 8;
   *cpb8 = c8 < 256 ? c8 : 256;
   const int rpp = 256 / *cpb8;
+  if (rpp_out) *rpp_out = rpp;
   *rpb = 32 * rpp;
   *nblk = ceil_div(rows, *rpb);
 }
 
-static inline void bwd_geometry(long long rows, int C, int* cpb4, int* rpb, int* nblk) {
+static inline void bwd_geometry(long long rows, int C, int* cpb4, int* rpb, int* nblk, int* rpp_out = nullptr) {
   int c4 = C / 4;
   *cpb4 = c4 < 256 ? c4 : 256;
   const int rpp = 256 / *cpb4;
+  if (rpp_out) *rpp_out = rpp;
   *rpb = 32 * rpp;
   *nblk = ceil_div(rows, *rpb);
 }
@@ -523,14 +535,14 @@ int launch_bn_bwd_reduce(const void* dZ, const void* Zmask, const unsigned* Zbit
   int cpb4, rpb, nblk;
   if (use_v8(dt, C) && !Zmask) {
     bwd_geometry16(rows, C, &cpb4, &rpb, &nblk);
-    hipLaunchKernelGGL(bn_bwd_reduce16_kernel, dim3(nblk, ceil_div(C / 8, cpb4)), dim3(256), 0, s, static_cast<const bf16_t*>(dZ), Zbits,
+    hipLaunchKernelGGL(bn_bwd_reduce16_kernel, dim3(nblk, col_blocks(C, 8, cpb4)), dim3(256), 0, s, static_cast<const bf16_t*>(dZ), Zbits,
                        static_cast<const bf16_t*>(Y), scale, shift, mean, invstd, partials, rows, C, cpb4, rpb);
     return check_launch("bn_bwd_reduce16");
   }
   R3M_REQUIRE(!use_v8(dt, C), "bn_bwd_reduce(bf16): pass the 1-bit mask (zbits) or no mask; a bf16 zmask tensor is not supported");
   bwd_geometry(rows, C, &cpb4, &rpb, &nblk);
   DT_DISPATCH(dt, "bn_bwd_reduce",
-              hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3(nblk, ceil_div(C / 4, cpb4)), dim3(256), 0, s,
+              hipLaunchKernelGGL((bn_bwd_reduce_kernel<T>), dim3(nblk, col_blocks(C, 4, cpb4)), dim3(256), 0, s,
                                  static_cast<const T*>(dZ), static_cast<const T*>(Zmask), Zbits, static_cast<const T*>(Y), scale,
                                  shift, mean, invstd, partials, rows, C, cpb4, rpb));
   return check_launch("bn_bwd_reduce");
@@ -634,16 +646,16 @@ int launch_bn_bwd_apply(const void* dZ, const void* Zmask, const unsigned* Zbits
                         long long rows, int C, int dt, hipStream_t s) {
   R3M_REQUIRE(is_pow2(C) && C >= 4, "bn_bwd_apply: C=%d must be a power of two >= 4", C);
   if (use_v8(dt, C) && !Zmask) {
-    const long long n8 = rows * C / 8;
-    const int span8 = bn_span(C / 8, 4);
-    hipLaunchKernelGGL(bn_bwd_apply16_kernel, dim3(ceil_div(n8, span8)), dim3(256), 0, s, static_cast<const bf16_t*>(dZ), Zbits,
+    const long long n8 = bn_items(rows, C, 8);
+    const int span8 = apply_span(true, C);
+    hipLaunchKernelGGL(bn_bwd_apply16_kernel, dim3(span_grid(n8, span8)), dim3(256), 0, s, static_cast<const bf16_t*>(dZ), Zbits,
                        static_cast<const bf16_t*>(Y), scale, shift, mean, invstd, c1, c2, static_cast<bf16_t*>(dY), n8, C / 8 - 1, span8);
     return check_launch("bn_bwd_apply16");
   }
-  const long long n4 = rows * C / 4;
-  const int span = bn_span(C / 4, C >= 512 ? 4 : 1);
+  const long long n4 = bn_items(rows, C, 4);
+  const int span = apply_span(false, C);
   DT_DISPATCH(dt, "bn_bwd_apply",
-              hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(ceil_div(n4, span)), dim3(256), 0, s, static_cast<const T*>(dZ),
+              hipLaunchKernelGGL((bn_bwd_apply_kernel<T>), dim3(span_grid(n4, span)), dim3(256), 0, s, static_cast<const T*>(dZ),
                                  static_cast<const T*>(Zmask), Zbits, static_cast<const T*>(Y), scale, shift, mean, invstd, c1, c2,
                                  static_cast<T*>(dY), n4, C / 4 - 1, span));
   return check_launch("bn_bwd_apply");
@@ -774,7 +786,7 @@ int launch_bn_bwd_reduce2(const void* dZ, const unsigned* Zbits, const void* YA,
   int cpb8, rpb, nblk;
   bwd_geometry16(rows, C, &cpb8, &rpb, &nblk);
   R3M_REQUIRE((long long)nblk * 2 * C <= set_stride, "bn_bwd_reduce2: partial sets overlap");
-  hipLaunchKernelGGL(bn_bwd_reduce2_16_kernel, dim3(nblk, ceil_div(C / 8, cpb8)), dim3(256), 0, s, static_cast<const bf16_t*>(dZ), Zbits,
+  hipLaunchKernelGGL(bn_bwd_reduce2_16_kernel, dim3(nblk, col_blocks(C, 8, cpb8)), dim3(256), 0, s, static_cast<const bf16_t*>(dZ), Zbits,
                      static_cast<const bf16_t*>(YA), coefA, coefA + C, static_cast<const bf16_t*>(YB), coefB, coefB + C, partials, set_stride,
                      rows, C, cpb8, rpb);
   return check_launch("bn_bwd_reduce2_16");
@@ -787,20 +799,48 @@ int launch_bn_bwd_apply2(const void* dZ, const unsigned* Zbits, const void* YA, 
   const BnApplyCoef A{coefA + 2LL * C, coefA, coefA + C, coefA + 4LL * C, coefA + 5LL * C};
   const BnApplyCoef B{coefB + 2LL * C, coefB, coefB + C, coefB + 4LL * C, coefB + 5LL * C};
   if (use_v8(dt, C)) {
-    const long long n8 = rows * C / 8;
-    const int span8 = bn_span(C / 8, 4);
-    hipLaunchKernelGGL(bn_bwd_apply2_16_kernel, dim3(ceil_div(n8, span8)), dim3(256), 0, s, static_cast<const bf16_t*>(dZ), Zbits,
+    const long long n8 = bn_items(rows, C, 8);
+    const int span8 = apply_span(true, C);
+    hipLaunchKernelGGL(bn_bwd_apply2_16_kernel, dim3(span_grid(n8, span8)), dim3(256), 0, s, static_cast<const bf16_t*>(dZ), Zbits,
                        static_cast<const bf16_t*>(YA), A, static_cast<bf16_t*>(dYA), static_cast<const bf16_t*>(YB), B,
                        static_cast<bf16_t*>(dYB), n8, C / 8 - 1, span8);
     return check_launch("bn_bwd_apply2_16");
   }
   R3M_REQUIRE(dt == DT_F32, "bn_bwd_apply2: dtype %d", dt);
-  const long long n4 = rows * C / 4;
-  const int span = bn_span(C / 4, C >= 512 ? 4 : 1);
-  hipLaunchKernelGGL((bn_bwd_apply2_kernel<float>), dim3(ceil_div(n4, span)), dim3(256), 0, s, static_cast<const float*>(dZ), Zbits,
+  const long long n4 = bn_items(rows, C, 4);
+  const int span = apply_span(false, C);
+  hipLaunchKernelGGL((bn_bwd_apply2_kernel<float>), dim3(span_grid(n4, span)), dim3(256), 0, s, static_cast<const float*>(dZ), Zbits,
                      static_cast<const float*>(YA), A, static_cast<float*>(dYA), static_cast<const float*>(YB), B,
                      static_cast<float*>(dYB), n4, C / 4 - 1, span);
   return check_launch("bn_bwd_apply2");
+}
+
+// What the launchers above pick for a [rows][C] tensor, without launching anything (r3m_debug_bn_geometry; the index names are in
+// include/r3m_hip.h). Every figure comes from the helper the launcher itself calls.
+int bn_debug_geometry(long long rows, int C, int dt, int* out, int cap) {
+  R3M_REQUIRE(out && cap >= 14, "debug_bn_geometry: the output buffer needs 14 ints");
+  R3M_REQUIRE(rows >= 1 && is_pow2(C) && C >= 4 && (dt == DT_F32 || dt == DT_BF16), "debug_bn_geometry: rows=%lld C=%d dtype=%d", rows, C, dt);
+  const int fv = fwd_v8(dt, C) ? 8 : 4;
+  out[0] = fv;
+  out[1] = fwd_span(dt, C);
+  out[2] = span_grid(bn_items(rows, C, fv), out[1]);
+  const bool v8 = use_v8(dt, C);
+  int cpb, rpb, nblk, rpp;
+  if (v8) bwd_geometry16(rows, C, &cpb, &rpb, &nblk, &rpp);
+  else bwd_geometry(rows, C, &cpb, &rpb, &nblk, &rpp);
+  const int bv = v8 ? 8 : 4;
+  out[3] = bv;
+  out[4] = rpb;
+  out[5] = rpp;
+  out[6] = col_blocks(C, bv, cpb);
+  out[7] = nblk;
+  out[8] = bv;
+  out[9] = apply_span(v8, C);
+  out[10] = span_grid(bn_items(rows, C, bv), out[9]);
+  out[11] = reduce_slices(nblk, C);
+  out[12] = reduce_slices(rows > 0x7fffffffLL ? 0x7fffffff : (int)rows, C);
+  out[13] = slice_cap(C);
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------

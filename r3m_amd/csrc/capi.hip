@@ -476,6 +476,56 @@ int r3m_bn_bwd(const float* dz, const float* zmask, const unsigned* zbits, const
                float* dbeta, float* dy, void* ws, size_t ws_bytes, long long rows, int C, int use_batch_stats, int accumulate, r3m_stream_t stream) {
   return r3m_bn_bwd_dt(dz, zmask, zbits, y, coef, dgamma, dbeta, dy, ws, ws_bytes, rows, C, use_batch_stats, accumulate, DT_F32, stream);
 }
+// The two BatchNorms of a downsample block's tail, as the engine's bn_backward_pair runs them when no dgrad epilogue wrote the partials:
+// workspace = [partial set A][partial set B][acc]; c1 / c2 go to rows 4, 5 of each coefficient block, where the paired second pass reads them
+size_t r3m_bn_pair_workspace_bytes(long long rows, int C) { return 2 * bn_acc_off(rows, C) + bn_acc_bytes(C); }
+int r3m_bn_bwd_pair_dt(const void* dz, const unsigned* zbits, const void* y_a, float* coef_a, const void* y_b, float* coef_b, float* dgamma_a,
+                       float* dbeta_a, void* dy_a, float* dgamma_b, float* dbeta_b, void* dy_b, void* ws, size_t ws_bytes, long long rows, int C,
+                       int use_batch_stats, int accumulate, int dtype, r3m_stream_t stream) {
+  if (check_dt(dtype, "bn_bwd_pair")) return 1;
+  R3M_REQUIRE(dz && zbits && y_a && coef_a && y_b && coef_b && dgamma_a && dbeta_a && dy_a && dgamma_b && dbeta_b && dy_b && ws,
+              "bn_bwd_pair: null argument");
+  R3M_REQUIRE(rows >= 1 && C >= 8, "bn_bwd_pair: rows=%lld C=%d", rows, C);
+  R3M_REQUIRE(ws_bytes >= r3m_bn_pair_workspace_bytes(rows, C), "bn_bwd_pair: workspace too small (need %zu)", r3m_bn_pair_workspace_bytes(rows, C));
+  float* partial = static_cast<float*>(ws);
+  const long long set = (long long)(bn_acc_off(rows, C) / 4);
+  double* acc = reinterpret_cast<double*>(static_cast<char*>(ws) + 2 * bn_acc_off(rows, C));
+  const int prow = bn_bwd_partial_rows(rows, C, dtype);
+  auto combine = [&](const float* p, float* coef, float* dgamma, float* dbeta) -> int {
+    if (int e = launch_bn_stats_reduce(p, prow, C, acc, S(stream))) return e;
+    return launch_bn_bwd_finalize_rows(acc, prow, rows, use_batch_stats, dgamma, dbeta, coef + 4LL * C, coef + 5LL * C, accumulate, C, S(stream));
+  };
+  auto sums = [&](const void* y, float* coef, float* dgamma, float* dbeta) -> int {
+    if (int e = launch_bn_bwd_reduce(dz, nullptr, zbits, y, coef + 2LL * C, coef + 3LL * C, coef, coef + C, partial, rows, C, dtype, S(stream))) return e;
+    return combine(partial, coef, dgamma, dbeta);
+  };
+  if (bn_bwd_reduce2_available(C, dtype)) {
+    if (int e = launch_bn_bwd_reduce2(dz, zbits, y_a, coef_a, y_b, coef_b, partial, set, rows, C, dtype, S(stream))) return e;
+    if (int e = combine(partial, coef_a, dgamma_a, dbeta_a)) return e;
+    if (int e = combine(partial + set, coef_b, dgamma_b, dbeta_b)) return e;
+  } else {
+    if (int e = sums(y_a, coef_a, dgamma_a, dbeta_a)) return e;
+    if (int e = sums(y_b, coef_b, dgamma_b, dbeta_b)) return e;
+  }
+  return launch_bn_bwd_apply2(dz, zbits, y_a, coef_a, dy_a, y_b, coef_b, dy_b, rows, C, dtype, S(stream));
+}
+// BatchNorm backward behind a dgrad whose epilogue wrote the first pass (r3m_conv2d_dgrad_bnred_dt), as the engine's bn_backward runs it
+// with fused_rows > 0: combine the partial rows (second sum x invstd), then the second pass. workspace: [acc][c1, c2]
+int r3m_bn_bwd_from_partials_dt(const void* dz, const unsigned* zbits, const void* y, const float* coef, const float* partials, int partial_rows,
+                                float* dgamma, float* dbeta, void* dy, void* ws, size_t ws_bytes, long long rows, int C, int use_batch_stats,
+                                int accumulate, int dtype, r3m_stream_t stream) {
+  if (check_dt(dtype, "bn_bwd_from_partials")) return 1;
+  R3M_REQUIRE(dz && y && coef && partials && dgamma && dbeta && dy && ws, "bn_bwd_from_partials: null argument");
+  R3M_REQUIRE(rows >= 1 && partial_rows >= 1, "bn_bwd_from_partials: rows=%lld partial_rows=%d", rows, partial_rows);
+  R3M_REQUIRE(ws_bytes >= bn_acc_bytes(C) + (size_t)2 * C * 4, "bn_bwd_from_partials: workspace too small (need %zu)", bn_acc_bytes(C) + (size_t)2 * C * 4);
+  double* acc = static_cast<double*>(ws);
+  float* c12 = reinterpret_cast<float*>(static_cast<char*>(ws) + bn_acc_bytes(C));
+  const float *mean = coef, *invstd = coef + C, *scale = coef + 2 * C, *shift = coef + 3 * C;
+  if (int e = launch_bn_stats_reduce(partials, partial_rows, C, acc, S(stream))) return e;
+  if (int e = launch_bn_bwd_finalize_rows(acc, partial_rows, rows, use_batch_stats, dgamma, dbeta, c12, c12 + C, accumulate, C, S(stream), invstd)) return e;
+  return launch_bn_bwd_apply(dz, nullptr, zbits, y, scale, shift, mean, invstd, c12, c12 + C, dy, rows, C, dtype, S(stream));
+}
+int r3m_debug_bn_geometry(long long rows, int C, int dtype, int* out, int cap) { return bn_debug_geometry(rows, C, dtype, out, cap) ? -1 : 14; }
 // stem tail fused: BatchNorm + ReLU + MaxPool(3,2,1) forward, and its backward (MaxPool gather inside both BN-backward passes)
 int r3m_bn_relu_maxpool_fwd_dt(const void* y, const float* coef, void* p, unsigned char* am, int N, int Hi, int Wi, int C, int dtype,
                                r3m_stream_t stream) {

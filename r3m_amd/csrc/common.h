@@ -224,6 +224,7 @@ int bn_bwd_pool_partial_rows(int N, int Hi, int Wi, int C);
 int launch_bn_bwd_apply2(const void* dZ, const unsigned* Zbits, const void* YA, const float* coefA, void* dYA, const void* YB,
                          const float* coefB, void* dYB, long long rows, int C, int dt, hipStream_t s);
 bool bn_bwd_reduce2_available(int C, int dt);
+int bn_debug_geometry(long long rows, int C, int dt, int* out, int cap);   // r3m_debug_bn_geometry: what the launchers pick, nothing launched
 int launch_bn_bwd_reduce2(const void* dZ, const unsigned* Zbits, const void* YA, const float* coefA, const void* YB, const float* coefB,
                           float* partials, long long set_stride /* floats between the two partial sets */, long long rows, int C, int dt,
                           hipStream_t s);

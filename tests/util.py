@@ -251,3 +251,208 @@ def check_dgrad_bnred(hip, case, mode, dtype):
     np.testing.assert_allclose(got_s2, ref_s2, rtol=0, atol=4e-6 * scale1)
     # and agree with the float64 expectation to the accuracy of the stored tensor
     np.testing.assert_allclose(got_s1, exp_s1, rtol=0, atol=(2e-5 if dtype == "fp32" else 2e-2) * scale1 / np.sqrt(N * Hi * Wi) + 1e-6 * scale1)
+
+
+# ---- BatchNorm passes one by one (tests/test_gpu_bn.py on the GPU, tests/test_bn_geometry.py for the case list on the CPU) ---------------
+# A case is (rows, C, dtype); dtype "fp32" | "bf16". The list is derived from what the library itself reports: the plans' BatchNorm
+# shapes (r3m_resnet_conv_info) and the launch geometry (r3m_debug_bn_geometry), so it follows the launchers when they change.
+BN_GEOM_FIELDS = ("fwd_vec", "fwd_span", "fwd_grid", "red_vec", "rpb", "rpp", "col_blocks", "nblk", "app_vec", "app_span", "app_grid",
+                  "slices", "slices_of_rows", "slice_cap")
+BN_FRAME_SIZES = [(32, 32), (33, 47), (47, 33), (97, 131), (131, 97), (96, 160), (160, 96)]
+BN_CHANNELS = (64, 128, 256, 512, 1024, 2048)          # every channel count behind the stem of ResNet-18 / 34 / 50
+BN_LARGE = (32 * 56 * 56, 64)                          # the 56 x 56 x 64 map of 32 frames: 25.7 MB in fp32, many blocks and slices
+
+
+def bn_geometry(L, rows, C, dtype):
+    import ctypes
+    buf = (ctypes.c_int * 16)()
+    n = L.r3m_debug_bn_geometry(rows, C, 0 if dtype == "fp32" else 1, buf, 16)
+    assert n == len(BN_GEOM_FIELDS), L.r3m_last_error()
+    return dict(zip(BN_GEOM_FIELDS, buf[:n]))
+
+
+def bn_span_tail(rows, C, vec, span):
+    """where the last block of a span-wide elementwise launch ends: 'full' (n % span == 0), 'one' (one row of vectors, the smallest
+    remainder a [rows][C] tensor can leave; a single vector when C == vec), 'all_but_one' (span minus one row of vectors), 'mid_walk'
+    (inside the block's 256-wide walk: past its first iteration and not on an iteration boundary, or, when a row fills a whole
+    iteration, after exactly two of the four), else 'part'"""
+    cv = C // vec
+    r = (rows * cv) % span
+    if r == 0:
+        return "full"
+    if r == cv:
+        return "one"
+    if r == span - cv:
+        return "all_but_one"
+    if span > 256 and ((r > 256 and r % 256 != 0) or (cv == 256 and r == 512)):
+        return "mid_walk"
+    return "part"
+
+
+def bn_class(L, rows, C, dtype):
+    """everything the launchers of csrc/bn.hip can tell apart about a [rows][C] tensor, minus the sizes themselves"""
+    g = bn_geometry(L, rows, C, dtype)
+    nf, na = rows * C // g["fwd_vec"], rows * C // g["app_vec"]
+    return (dtype, C, g["fwd_span"], nf % g["fwd_span"] == 0, g["fwd_grid"] > 1, g["col_blocks"], rows < g["rpp"], rows % g["rpb"] == 0,
+            g["nblk"] > 1, g["app_span"], na % g["app_span"] == 0, g["app_grid"] > 1, g["slices"] == g["slice_cap"])
+
+
+def bn_plan_shapes(L, sizes, frame_sizes, frame_counts):
+    """distinct (rows, C) = (F * Ho * Wo, Co) of the BatchNorms behind the stem (the stem's own runs the fused pool kernels)"""
+    from route_sig import plan_convs
+    out = []
+    for size in sizes:
+        for (H, W) in frame_sizes:
+            for F_ in frame_counts:
+                h = L.r3m_resnet_create_hw(size, F_, 0, H, W)
+                assert h, L.r3m_last_error()
+                try:
+                    for (Ci, Co, k, s, p, Hi, Wi, Ho, Wo) in plan_convs(L, h)[1:]:
+                        if (F_ * Ho * Wo, Co) not in out:
+                            out.append((F_ * Ho * Wo, Co))
+                finally:
+                    L.r3m_resnet_destroy(h)
+    return out
+
+
+_bn_cases = None
+
+
+def bn_cases():
+    """[(rows, C, dtype, why)]: (a) the BatchNorm shapes of ResNet-18 / -50 at BN_FRAME_SIZES for 1 and 3 frames, (b) per channel count and
+    dtype the boundaries of every geometry class r3m_debug_bn_geometry reports, (c) one large case per dtype."""
+    global _bn_cases
+    if _bn_cases is not None:
+        return _bn_cases
+    from r3m_amd import _lib
+    L = _lib.lib()
+    out, seen = [], set()
+
+    def add(rows, C, dtype, why):
+        if rows >= 1 and (rows, C, dtype) not in seen:
+            seen.add((rows, C, dtype))
+            out.append((rows, C, dtype, why))
+
+    for (rows, C) in bn_plan_shapes(L, (18, 50), BN_FRAME_SIZES, (1, 3)):
+        for dtype in ("fp32", "bf16"):
+            add(rows, C, dtype, "plan")
+    for dtype in ("fp32", "bf16"):
+        for C in BN_CHANNELS:
+            g = bn_geometry(L, 1, C, dtype)
+            rpp, rpb = g["rpp"], g["rpb"]
+            for rows in (rpp - 1, rpp, rpb - 1, rpb, rpb + 1, 2 * rpb - 1, 2 * rpb, 2 * rpb + 1):
+                add(rows, C, dtype, "reduce_block")
+            for (vec, span) in {(g["fwd_vec"], g["fwd_span"]), (g["app_vec"], g["app_span"])}:
+                rps = max(span // (C // vec), 1)                  # rows per span
+                for rows in (2 * rps, 2 * rps + 1, 3 * rps - 1):
+                    add(rows, C, dtype, "span_tail")
+                mid = [r for r in range(2 * rps + 1, 3 * rps) if bn_span_tail(r, C, vec, span) == "mid_walk"]
+                if mid:
+                    add(mid[0], C, dtype, "span_tail")
+            # one representative of every class a row count up to three blocks / spans can fall into
+            have = {bn_class(L, r, c, d) for (r, c, d, _) in out if c == C and d == dtype}
+            for rows in range(1, 3 * max(rpb, 1024 * 8 // C) + 2):
+                cls = bn_class(L, rows, C, dtype)
+                if cls not in have:
+                    have.add(cls)
+                    add(rows, C, dtype, "class")
+    # a tail of literally one 16-byte vector needs one vector per row: C = 8 in bf16 (the launchers take it; no mask bits at these sizes)
+    add(1025, 8, "bf16", "one_vector")
+    add(2047, 8, "bf16", "one_vector")
+    for dtype in ("fp32", "bf16"):
+        add(BN_LARGE[0], BN_LARGE[1], dtype, "large")
+    _bn_cases = out
+    return out
+
+
+def bn_possible_tails(C, vec, span):
+    """the tail kinds (bn_span_tail) a multi-block launch over [rows][C] can end in: a row is C / vec items, so the remainder of the last
+    block is a multiple of that; rows per span = span / (C / vec) when a row is shorter than the span, else every block is full"""
+    rps = span // (C // vec)
+    if rps <= 1:
+        return {"full"}
+    return {bn_span_tail(rps + k, C, vec, span) for k in range(rps)}
+
+
+def bn_pair_cases():
+    """[(rows, C, dtype)] for the paired tail kernels (C >= 64: a downsample block's tail): per channel count and dtype one multi-block
+    case of EVERY tail kind the paired second pass can end in (bn_span_tail of the backward-apply span: apply2 / apply2_16 walk their
+    span on their own), a single-block case, every case with rows <= 3, the large case, and every third case of the rest."""
+    L_ = None
+    out, seen = [], set()
+    for i, (rows, C, dtype, why) in enumerate(bn_cases()):
+        if C < 64:
+            continue
+        if L_ is None:
+            from r3m_amd import _lib
+            L_ = _lib.lib()
+        g = bn_geometry(L_, rows, C, dtype)
+        key = (C, dtype, bn_span_tail(rows, C, g["app_vec"], g["app_span"]), g["app_grid"] > 1)
+        if key not in seen or rows <= 3 or why == "large" or i % 3 == 0:
+            seen.add(key)
+            out.append((rows, C, dtype))
+    return out
+
+
+def bn_case_id(c):
+    return "{}x{}_{}_{}".format(*c)
+
+
+def bn_coef_of(y, gamma, beta, eps=1e-5):
+    """fp32 coefficient block [4][C] = mean, invstd, scale, shift from the float64 batch statistics of y"""
+    m = y.double().mean(0)
+    v = y.double().var(0, unbiased=False)
+    inv = 1.0 / torch.sqrt(v + eps)
+    sc = gamma.double() * inv
+    return torch.stack([m, inv, sc, beta.double() - m * sc]).float()
+
+
+def bn_pre_activation(inp, mode):
+    """float64 t = scale y + shift [+ r] [+ scale2 y2 + shift2] with the fp32 coefficients cast to float64"""
+    c = inp["coef"].double()
+    t = inp["y"].double() * c[2] + c[3]
+    if mode == "identity":
+        t = t + inp["r"].double()
+    elif mode == "downsample":
+        c2 = inp["coef2"].double()
+        t = t + (inp["y2"].double() * c2[2] + c2[3])
+    return t
+
+
+def bn_inputs(rows, C, dtype, mode, coef=None, coef2=None):
+    """Inputs of one case (CPU tensors, fp32 values; bf16 cases hold bf16-representable values). Coefficients: the batch statistics of y
+    / y2 unless given. y is then moved off the ReLU kink of THIS mode (|t| < 1e-3 in float64 -> y + 0.05), so that neither the mask
+    recomputed in fp32 nor the bf16 sign check depends on a tie; 'near' is the fraction still within 1e-4 afterwards."""
+    q = q_bf16 if dtype == "bf16" else (lambda t: t)
+    inp = dict(y=q(rnd((rows, C), 11, -2.0, 3.0)), r=q(rnd((rows, C), 16, 0.0, 1.0)), y2=q(rnd((rows, C), 17, -1.0, 1.0)),
+               dz=q(rnd((rows, C), 20)), gamma=rnd((C,), 12, 0.5, 1.5), beta=rnd((C,), 13, -0.3, 0.3), gamma2=rnd((C,), 18, 0.5, 1.5),
+               beta2=rnd((C,), 19, -0.3, 0.3))
+    inp["coef"] = bn_coef_of(inp["y"], inp["gamma"], inp["beta"]) if coef is None else coef
+    inp["coef2"] = bn_coef_of(inp["y2"], inp["gamma2"], inp["beta2"]) if coef2 is None else coef2
+    for _ in range(8):
+        near = bn_pre_activation(inp, mode).abs() < 1e-3
+        if not bool(near.any()):
+            break
+        inp["y"] = q(torch.where(near, inp["y"] + 0.05, inp["y"]))
+    inp["near"] = float((bn_pre_activation(inp, mode).abs() <= 1e-4).double().mean())
+    return inp
+
+
+def bn_bwd_ref(dz, mask, y, coef, use_batch_stats, dt=torch.float64):
+    """dbeta, dgamma, dy of BatchNorm (+ mask) backward with the given coefficients, evaluated in `dt` (float64: the reference;
+    float32: the witness of what the formula itself loses in fp32)"""
+    c = coef.to(dt)
+    g = dz.to(dt) * mask.to(dt)
+    yhat = (y.to(dt) - c[0]) * c[1]
+    db, dg = g.sum(0), (g * yhat).sum(0)
+    if use_batch_stats:
+        dy = c[2] * (g - g.mean(0) - yhat * (g * yhat).mean(0))
+    else:
+        dy = c[2] * g
+    return db, dg, dy
+
+
+def unpack_bits(words, n):
+    """uint32 / int32 words (numpy) -> bool [n]: element j = bit j & 31 of word j >> 5"""
+    w = np.asarray(words).view(np.uint32)
+    return (((w[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).reshape(-1)[:n]).astype(bool)
