@@ -34,6 +34,14 @@ int r3m_debug_occupancy(int* out4);   /* resident blocks/CU predicted for {gemm1
 int r3m_debug_occupy(int blocks, int lds_bytes, double milliseconds, r3m_stream_t stream);
 /* Diagnostic: 0 = the encoder's persistent-kernel launches assign tiles statically, 1 (default) = per-XCD tile queues. Returns the old value. */
 int r3m_debug_set_dynamic_tiles(int on);
+/* Diagnostic (tests): the NEXT convolution launches of the calling thread draw their tiles from per-XCD tile queues, as every launch
+   inside r3m_resnet_forward / _backward does (the operator entry points otherwise launch with the static tile split). counters:
+   sets x 8 unsigned on the device, ZEROED by the caller on the stream of the launch; one set serves one launch (a stride-2 input
+   gradient is up to four launches: pass 4 sets), sets nobody used are dropped after the last launch of the call. NULL takes them back
+   (do that when the call they were meant for failed before it launched). Only the fp32 persistent kernel (routes 11 - 13) reads them,
+   and only for launches of at least 64 row panels and 64 blocks: smaller ones keep the static split and leave the counters zero.
+   Queue launches leave every counter of their set non-zero. */
+void r3m_debug_next_launch_tile_queues(unsigned* counters, int sets);
 /* Diagnostic, PROBE BUILDS ONLY (-DR3M_PROBES; the shipped library does not contain the kernel and returns -1): 1 = eligible bf16
    forward / dgrad launches run the round-5 persistent big-tile experiment csrc/conv_pw16.hip (pointwise + gather forms), 3 = + its
    3x3 window form; 0 = off. Measured not faster inside the step. Returns the old value. */
@@ -257,6 +265,25 @@ int r3m_conv2d_dgrad_bnred_dt(const void* dy, const float* w_ohwi, void* dx, voi
                               int Wi, int Ci, int Co, int k, int stride, int pad, const void* residual_grad,
                               const unsigned* residual_bits, const void* bn_y, const unsigned* bn_bits, const float* bn_scale,
                               const float* bn_shift, const float* bn_mean, float* partials, int dtype, r3m_stream_t stream);
+/* The two input-gradient epilogues of a residual block's entry that only the engine launched so far (tests), through the launcher
+ * the engine calls, the weight image made in the workspace as r3m_conv2d_dgrad_dt does:
+ *   accumulate = 1                 dx += dgrad: the downsample branch (k = 1, pad 0, stride 1 or 2) adding onto the input gradient the
+ *                                  block's first convolution stored. A strided 1x1 leaves the pixels without taps untouched.
+ *   residual_grad, residual_bits   dx = dgrad + residual_grad * [residual_bits]: the join at the input of an identity block (stride 1)
+ *                                  without BatchNorm partials (every identity block of a bf16 plan, the first block of an fp32 plan).
+ *                                  residual_grad: [N,Hi,Wi,Ci] of the dtype; residual_bits: 1 bit per element, required (the engine
+ *                                  always passes the block output's mask bits).
+ * Exactly one of the two. */
+int r3m_conv2d_dgrad_join_dt(const void* dy, const float* w_ohwi, void* dx, void* workspace, size_t workspace_bytes, int N, int Hi,
+                             int Wi, int Ci, int Co, int k, int stride, int pad, int accumulate, const void* residual_grad,
+                             const unsigned* residual_bits, int dtype, r3m_stream_t stream);
+/* The inference forward of one convolution, as r3m_resnet_forward(training = 2) launches it (tests): out = [relu](conv(x, w) * scale[co]
+ * + shift[co] [+ out]) stored by the convolution kernel itself, rounded once for bf16. flags: 128 (eval BatchNorm: the downsample
+ * branch), 128 | 16 (+ ReLU: inner convolutions), 128 | 2 | 16 (+ the residual, which `out` holds on entry: a block's last
+ * convolution). x, w as r3m_conv2d_fwd_dt; scale, shift: fp32 [Co]. Returns non-zero with a message where
+ * r3m_debug_conv_fuses_affine answers 0: the engine does not make that launch (it runs conv + r3m_bn_act_fwd instead). */
+int r3m_conv2d_fwd_affine_dt(const void* x, const void* w_ohwi, void* out, const float* scale, const float* shift, int N, int Hi, int Wi,
+                             int Ci, int Co, int k, int stride, int pad, int flags, int dtype, r3m_stream_t stream);
 size_t r3m_conv2d_wgrad_workspace_bytes_dt(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int dtype);
 int r3m_conv2d_wgrad_dt(const void* x, const void* dy, float* dw_ohwi, void* workspace, size_t workspace_bytes, int N, int Hi,
                         int Wi, int Ci, int Co, int k, int stride, int pad, int accumulate, int dtype, r3m_stream_t stream);

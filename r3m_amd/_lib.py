@@ -25,6 +25,7 @@ SIGNATURES = {
     "r3m_debug_occupancy": (c_i, [C.POINTER(c_i)]),
     "r3m_debug_occupy": (c_i, [c_i, c_i, C.c_double, C.c_void_p]),
     "r3m_debug_set_dynamic_tiles": (c_i, [c_i]),
+    "r3m_debug_next_launch_tile_queues": (None, [c_f, c_i]),
     "r3m_debug_set_pw16": (c_i, [c_i]),
     "r3m_debug_set_conv3x3_bf16": (c_i, [c_i]),
     "r3m_debug_set_fused_inference": (c_i, [c_i]),
@@ -91,6 +92,8 @@ SIGNATURES = {
     "r3m_conv2d_dgrad_dt": (c_i, [c_f, c_f, c_f, c_f, c_sz] + [c_i] * 9 + [c_f]),
     "r3m_conv2d_dgrad_bnred_rows": (c_i, [c_i] * 4),
     "r3m_conv2d_dgrad_bnred_dt": (c_i, [c_f, c_f, c_f, c_f, c_sz] + [c_i] * 8 + [c_f] * 8 + [c_i, c_f]),
+    "r3m_conv2d_dgrad_join_dt": (c_i, [c_f, c_f, c_f, c_f, c_sz] + [c_i] * 9 + [c_f, c_f, c_i, c_f]),
+    "r3m_conv2d_fwd_affine_dt": (c_i, [c_f] * 5 + [c_i] * 10 + [c_f]),
     "r3m_conv2d_wgrad_workspace_bytes_dt": (c_sz, [c_i] * 9),
     "r3m_conv2d_wgrad_dt": (c_i, [c_f, c_f, c_f, c_f, c_sz] + [c_i] * 10 + [c_f]),
     "r3m_stem_conv_fwd_dt": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_f]),

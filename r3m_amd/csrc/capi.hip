@@ -131,6 +131,7 @@ int r3m_debug_occupy(int blocks, int lds_bytes, double milliseconds, r3m_stream_
   return r3m::check_launch("debug_occupy");
 }
 int r3m_debug_set_dynamic_tiles(int on) { return r3m::gg_set_dynamic_tiles(on); }
+void r3m_debug_next_launch_tile_queues(unsigned* counters, int sets) { r3m::gg_set_tile_counters(counters, counters && sets > 0 ? sets : 0); }
 int r3m_debug_set_pw16(int mode) { return r3m::pw16_set_mode(mode); }
 int r3m_debug_set_conv3x3_bf16(int mode) { return r3m::row16_set_mode(mode); }
 int r3m_debug_set_fused_inference(int on) { return r3m::engine_set_fused_inference(on); }
@@ -324,6 +325,30 @@ int r3m_conv2d_dgrad_bnred_dt(const void* dy, const float* w, void* dx, void* ws
   BnRedArgs br{FP(bn_y), bn_bits, bn_scale, bn_shift, bn_mean, partials, 0};
   return conv_dgrad_launch(FP(dy), Wt, FPM(dx), FP(residual_grad), nullptr, residual_bits, {N, Hi, Wi, Ci, Co, k, stride, pad},
                            residual_grad ? EPI_MASKED_ADD : 0, dtype, S(stream), &br);
+}
+int r3m_conv2d_dgrad_join_dt(const void* dy, const float* w, void* dx, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int Ci, int Co, int k,
+                             int stride, int pad, int accumulate, const void* residual_grad, const unsigned* residual_bits, int dtype,
+                             r3m_stream_t stream) {
+  if (check_dt(dtype, "conv2d_dgrad_join")) return 1;
+  R3M_REQUIRE(dy && w && dx && ws, "conv2d_dgrad_join: null argument");
+  R3M_REQUIRE((accumulate != 0) != (residual_grad != nullptr), "conv2d_dgrad_join: pass accumulate = 1 or a residual gradient, one of the two");
+  R3M_REQUIRE(!accumulate || (k == 1 && pad == 0), "conv2d_dgrad_join: accumulate is the downsample branch's (k = 1, pad 0), not k=%d pad=%d", k, pad);
+  R3M_REQUIRE(!residual_grad || (residual_bits && stride == 1), "conv2d_dgrad_join: a residual gradient needs its mask bits and stride 1");
+  R3M_REQUIRE(ws_bytes >= r3m_conv2d_dgrad_workspace_bytes(Ci, Co, k), "conv2d_dgrad_join: workspace too small");
+  float* Wt = static_cast<float*>(ws);
+  if (dtype == DT_BF16) { if (int e = launch_transpose_w_bf16(w, Wt, Co, k * k, Ci, S(stream))) return e; }
+  else if (int e = launch_transpose_w(w, Wt, Co, k * k, Ci, S(stream))) return e;
+  return conv_dgrad_launch(FP(dy), Wt, FPM(dx), FP(residual_grad), nullptr, residual_bits, {N, Hi, Wi, Ci, Co, k, stride, pad},
+                           accumulate ? EPI_ACCUM : EPI_MASKED_ADD, dtype, S(stream));
+}
+int r3m_conv2d_fwd_affine_dt(const void* x, const void* w, void* out, const float* scale, const float* shift, int N, int Hi, int Wi, int Ci,
+                             int Co, int k, int stride, int pad, int flags, int dtype, r3m_stream_t stream) {
+  if (check_dt(dtype, "conv2d_fwd_affine")) return 1;
+  R3M_REQUIRE(x && w && out && scale && shift, "conv2d_fwd_affine: null argument");
+  const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
+  R3M_REQUIRE(conv_forward_affine_fusable(g, flags, dtype), "conv2d_fwd_affine: the kernel of this launch does not store epilogue flags %d "
+              "(128, 128|16 or 128|2|16 on a fusing route): the engine runs conv + bn_act_fwd here", flags);
+  return conv_forward_launch_affine(FP(x), FP(w), FPM(out), scale, shift, g, flags, dtype, S(stream));
 }
 int r3m_conv2d_dgrad(const float* dy, const float* w, float* dx, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int Ci, int Co,
                      int k, int stride, int pad, r3m_stream_t stream) {

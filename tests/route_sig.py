@@ -7,9 +7,12 @@ import ctypes as C
 
 STATS, ACCUM, MASKED_ADD, BNRED, AFFINE, RELU = 1, 2, 4, 64, 128, 16
 # (dgrad, flags, mask_bits) the operator entry points of include/r3m_hip.h can ask for: r3m_conv2d_fwd[_dt] with / without statistics,
-# r3m_conv2d_dgrad[_dt], r3m_conv2d_dgrad_bnred_dt in its three modes. The engine's other epilogues (accumulate onto a stored
-# gradient, masked join without partials, eval-BatchNorm forwards) have no entry point of their own.
-OPERATOR_EPILOGUES = {(0, STATS, 0), (0, 0, 0), (1, 0, 0), (1, BNRED, 0), (1, BNRED, 1), (1, BNRED | MASKED_ADD, 1)}
+# r3m_conv2d_dgrad[_dt], r3m_conv2d_dgrad_bnred_dt in its three modes, r3m_conv2d_dgrad_join_dt (accumulate onto a stored gradient;
+# masked join without partials -- its residual bits are not the mask_bits of a signature, which are the BatchNorm partials'),
+# r3m_conv2d_fwd_affine_dt (the three eval-BatchNorm stores of inference). Nothing the engine launches is left without one.
+OPERATOR_EPILOGUES = {(0, STATS, 0), (0, 0, 0), (1, 0, 0), (1, BNRED, 0), (1, BNRED, 1), (1, BNRED | MASKED_ADD, 1),
+                      (1, ACCUM, 0), (1, MASKED_ADD, 0), (1, MASKED_ADD, 1),
+                      (0, AFFINE, 0), (0, AFFINE | RELU, 0), (0, AFFINE | ACCUM | RELU, 0)}
 BNRED_MODES = {"recompute": (BNRED, 0), "bits": (BNRED, 1), "bits+residual": (BNRED | MASKED_ADD, 1)}
 
 
@@ -39,6 +42,60 @@ def conv_case_signatures(L, cases, dt):
 def bnred_case_signatures(L, cases):
     """what check_dgrad_bnred launches for each (case, mode, dtype)"""
     return {signature(L, c, 1, *BNRED_MODES[mode], 0 if dtype == "fp32" else 1): (c, mode, dtype) for (c, mode, dtype) in cases}
+
+
+def affine_case_signatures(L, cases, dt):
+    """what check_conv_affine launches for each (case, flags)"""
+    return {signature(L, c, 0, fl, 0, dt): (c, fl) for (c, fl) in cases}
+
+
+def join_case_signatures(L, cases, dt):
+    """what check_dgrad_join launches for each (case, mode): mode 'accumulate' -> EPI_ACCUM, 'join' -> EPI_MASKED_ADD with residual bits and
+    no BatchNorm partials. The engine asks the join with mask_bits 0 (first block) and 1 (bf16 plans: the bits it would hand the partials
+    it does not fuse); without EPI_BNRED the dispatch never sees them, which signature() shows: both are recorded."""
+    out = {}
+    for (c, mode) in cases:
+        if mode == "accumulate":
+            out[signature(L, c, 1, ACCUM, 0, dt)] = (c, mode)
+        else:
+            for bits in (0, 1):
+                out[signature(L, c, 1, MASKED_ADD, bits, dt)] = (c, mode)
+    return out
+
+
+def pw_queue_grids(L, case, dgrad, flags):
+    """[(gridM, gridN)] of every launch of an fp32 convolution on the persistent kernel, from the tile sizes csrc/conv_pw.hip launch_pw_gemm
+    picks: 128 x 128 for outputs a multiple of 128 wide; else 256 x 64, or 512 x 64 for the burst launches (dense output rows, K >= 2 N,
+    flags 0 / statistics / 128|16 / partials with the mask recomputed). launch_pw_shape hands the tile queues on when gridM >= 64 and
+    min(tiles, resident blocks) >= 64, which gridM >= 64 implies on any device of 64 CUs or more. () when a launch takes another kernel."""
+    N, Hi, Wi, Ci, Co, k, s, p = case
+    r = routes(L, case, dgrad, flags, 0, 0)
+    if not r or any(x not in (11, 12, 13) for x in r):
+        return ()
+    Ho, Wo = (Hi + 2 * p - k) // s + 1, (Wi + 2 * p - k) // s + 1
+    if not dgrad:
+        Ms, Nc, K = [N * Ho * Wo], Co, (1 if (k == 1 and s == 1 and p == 0) else k * k) * Ci
+    elif s == 1:
+        Ms, Nc, K = [N * Hi * Wi], Ci, (1 if (k == 1 and p == 0) else k * k) * Co
+    else:       # one launch per parity class that has taps (and extent); strided output rows: never the burst tile
+        Ms = []
+        for py in (0, 1):
+            for px in (0, 1):
+                Hg, Wg = (Hi - py + 1) // 2, (Wi - px + 1) // 2
+                taps = sum(1 for kh in range(k) for kw in range(k) if (py + p - kh) % 2 == 0 and (px + p - kw) % 2 == 0)
+                if Hg > 0 and Wg > 0 and not (taps == 0 and flags == ACCUM):
+                    Ms.append(N * Hg * Wg)
+        Nc, K = Ci, None
+    assert len(Ms) == len(r), (case, Ms, r)
+    out = []
+    for M, route in zip(Ms, r):
+        if Nc % 128 == 0:
+            BM, BN = 128, 128
+        else:
+            burst = route != 13 and K >= 2 * Nc and flags in (0, STATS, AFFINE | RELU, BNRED)
+            BM, BN = (512 if burst else 256), 64
+        out.append((-(-M // BM), Nc // BN))
+    return tuple(out)
 
 
 def plan_convs(L, h):

@@ -143,32 +143,34 @@ def test_every_engine_route_at_non_square_sizes_has_an_operator_case():
     with the flags the engine asks, is the signature of a case of tests/test_gpu_ops_hw.py's lists -- a route the engine can take at a
     supported frame size and no operator test runs fails HERE, without a GPU, and names the geometry to add.
 
-    Epilogues no operator entry point can ask for (route_sig.OPERATOR_EPILOGUES: the downsample branch's accumulate, the masked join
-    without partials, the eval-BatchNorm forwards of inference) cannot be matched flag for flag: for those, every kernel family of the
-    launch must be run by an operator case of the same (dtype, direction, k, stride, width class, map orientation)."""
+    Every epilogue the engine asks has an operator entry point (route_sig.OPERATOR_EPILOGUES): the downsample branch's accumulate, the
+    masked join without partials and the eval-BatchNorm stores of inference are matched flag for flag against the lists of
+    tests/test_gpu_conv_epilogues.py, like everything else. Nothing is matched by kernel family only any more."""
     from r3m_amd import _lib
+    import test_gpu_conv_epilogues as E
     import test_gpu_ops_hw as T
     L = _lib.lib()
     have = {}
     have.update(route_sig.conv_case_signatures(L, T.HW_CONV_CASES, 0))
     have.update(route_sig.conv_case_signatures(L, T.HW_BF16_CASES + T.HW_ROW16_CASES, 1))
     have.update(route_sig.bnred_case_signatures(L, T.HW_BNRED_CASES))
+    have.update(route_sig.affine_case_signatures(L, E.AFFINE_FP32_CASES, 0))
+    have.update(route_sig.affine_case_signatures(L, E.AFFINE_BF16_CASES + E.AFFINE_BF16_3X3_CASES, 1))
+    have.update(route_sig.join_case_signatures(L, E.JOIN_CASES, 0))
+    have.update(route_sig.join_case_signatures(L, E.JOIN_CASES, 1))
     assert all(sig[4] for sig in have), [c for sig, c in have.items() if not sig[4]]      # no listed case is refused by the dispatch
-    families = {(sig[0], sig[1], r) + sig[5:] for sig in have for r in sig[4]}
-    missing, missing_family = {}, {}
+    missing, n = {}, 0
     for plan, (case, dgrad, flags, bits) in _engine_launches(L):
         sig = route_sig.signature(L, case, dgrad, flags, bits, plan[1])
         assert sig[4], (plan, case, dgrad, flags, bits, L.r3m_last_error())
-        if (dgrad, flags, bits) in route_sig.OPERATOR_EPILOGUES:
-            if sig not in have:
-                missing.setdefault(sig, (plan, case))
-        else:
-            for r in sig[4]:
-                if (sig[0], sig[1], r) + sig[5:] not in families:
-                    missing_family.setdefault((sig[0], sig[1], r) + sig[5:], (plan, case, flags, bits))
-    assert not missing and not missing_family, "no operator case in tests/test_gpu_ops_hw.py for:\n" + "\n".join(
+        assert (dgrad, flags, bits) in route_sig.OPERATOR_EPILOGUES, (plan, case, dgrad, flags, bits)
+        n += 1
+        if sig not in have:
+            missing.setdefault(sig, (plan, case))
+    assert n > 10000
+    assert not missing, "no operator case in tests/test_gpu_ops_hw.py / tests/test_gpu_conv_epilogues.py for:\n" + "\n".join(
         f"  signature {k}: e.g. resnet{v[0][0]} dtype {v[0][1]} F={v[0][2]} at {v[0][3]} x {v[0][4]}, conv (N, Hi, Wi, Ci, Co, k, s, p) = {v[1]}"
-        for k, v in list(missing.items()) + list(missing_family.items()))
+        for k, v in missing.items())
 
 
 def test_no_non_square_layer_is_refused_either_way_round(route_hw):
@@ -261,3 +263,87 @@ def test_operator_case_groups_hold_what_they_are_there_for():
     assert all(fwd(c, 1) == (BF16_ROW,) for c in T.HW_ROW16_CASES)
     assert {(c[2] > c[1], c[4] % 128 == 0) for c in T.HW_ROW16_CASES} == {(a, b) for a in (True, False) for b in (True, False)}
     assert all(fwd(c, 1) == (BF16_HALO,) for c in H16["row16_too_wide"]) and {c[4] for c in H16["row16_too_wide"]} == {64, 128}
+
+
+# ---- the engine-only epilogues and the tile queues (tests/test_gpu_conv_epilogues.py) -------------------------------------------------------
+def test_conv_epilogue_case_groups_hold_what_they_are_there_for():
+    """per group of tests/test_gpu_conv_epilogues.py the routes, tiles, flag sets and extents its comment promises, and that the engine
+    would really make every listed launch (r3m_debug_conv_fuses_affine) and none of the refused ones"""
+    from r3m_amd import _lib
+    import test_gpu_conv_epilogues as E
+    L = _lib.lib()
+    A, AR, AAR = route_sig.AFFINE, route_sig.AFFINE | route_sig.RELU, route_sig.AFFINE | ACCUM | route_sig.RELU
+    fwd = lambda c, fl, dt=0: route_sig.routes(L, c, 0, fl, 0, dt)
+    dgr = lambda c, fl, dt=0: route_sig.routes(L, c, 1, fl, 0, dt)
+    fuses = lambda c, fl, dt: L.r3m_debug_conv_fuses_affine(*c, fl, dt)
+    rows = lambda c: c[0] * ((c[1] + 2 * c[7] - c[5]) // c[6] + 1) * ((c[2] + 2 * c[7] - c[5]) // c[6] + 1)
+    orient = lambda g: {route_sig.shape_class(c[1], c[2]) for (c, _) in g}
+    G = E.AFFINE_FP32_GROUPS
+    assert all(fuses(c, fl, 0) == 1 for (c, fl) in E.AFFINE_FP32_CASES)
+    assert all(fuses(c, fl, 1) == 1 for (c, fl) in E.AFFINE_BF16_CASES + E.AFFINE_BF16_3X3_CASES)
+    assert all(fuses(c, fl, dt) == 0 for (c, fl, dt) in E.AFFINE_REFUSED) and {dt for (_, _, dt) in E.AFFINE_REFUSED} == {0, 1}
+    assert any(fwd(c, fl) == (WIN,) and fl == A for (c, fl, dt) in E.AFFINE_REFUSED if dt == 0)
+    assert all(fwd(c, fl) == (WIN,) for (c, fls) in G["window"] for fl in fls) and all(set(fls) == {AR, AAR} for (_, fls) in G["window"])
+    assert {"wide", "tall"} <= orient(G["window"]) and any(rows(c) % 128 for (c, _) in G["window"])
+    for name, route in (("pointwise_128", PW_POINT), ("gather_128", PW_GATHER)):
+        assert all(fwd(c, fl) == (route,) and c[4] % 128 == 0 for (c, fls) in G[name] for fl in fls), name
+        assert all(set(fls) == {A, AR, AAR} for (_, fls) in G[name]) and {"wide", "tall"} <= orient(G[name])
+        assert any(rows(c) % 128 and rows(c) > 128 for (c, _) in G[name]), name
+    assert {c[6] for (c, _) in G["gather_128"]} == {1, 2}
+    # 64-wide outputs: the burst launches take the 512 x 64 tile (half the row panels of the 256 x 64 one), the others the 256 x 64 tile
+    t64 = {(fwd(c, fl)[0], fl, route_sig.pw_queue_grids(L, c, 0, fl)[0][0] == -(-rows(c) // 512)) for (c, fls) in G["tile_64"] for fl in fls}
+    assert all(c[4] == 64 and rows(c) % 512 and rows(c) > 512 for (c, _) in G["tile_64"])
+    assert {(PW_GATHER, AR, True), (PW_GATHER, AAR, False), (PW_GATHER, A, False), (PW_POINT, AR, True), (PW_POINT, AAR, False),
+            (PW_POINT, AR, False), (PW_POINT, A, False)} <= t64, t64
+    assert all(fwd(c, A) == (PW_GATHER,) and c[5:] == (1, 2, 0) and fls == (A,) for (c, fls) in G["downsample"])
+    assert {(c[1] % 2, c[2] % 2) for (c, _) in G["downsample"]} == {(1, 0), (0, 1), (1, 1), (0, 0)}
+    assert {fwd(c, AR)[0] for (c, _) in G["one_pixel"]} == {WIN, PW_POINT} and all(c[1:3] == (1, 1) for (c, _) in G["one_pixel"])
+    # bf16: route 30 with all three flag sets, Co = 64 and 128 and more, ragged M, wide and tall; 32 by default and 31 when switched for the
+    # 3x3 list; 31 in the default mode on the maps too wide for the kernel-row kernel
+    H = E.AFFINE_BF16_GROUPS
+    assert all(fwd(c, fl, 1) == (BF16,) for (c, fls) in H["gather"] for fl in fls)
+    assert {fl for (_, fls) in H["gather"] for fl in fls} == {A, AR, AAR} and {64, 128} <= {c[4] for (c, _) in H["gather"]}
+    assert {"wide", "tall"} <= orient(H["gather"]) and any(rows(c) % 256 for (c, _) in H["gather"])
+    assert all(fwd(c, fl, 1) == (BF16_HALO,) for (c, fls) in H["row16_too_wide"] for fl in fls)
+    assert all(fwd(c, fl, 1) == (BF16_ROW,) and set(fls) == {AR, AAR} for (c, fls) in H["conv3x3"] for fl in fls)
+    old = L.r3m_debug_set_conv3x3_bf16(0)
+    try:
+        assert all(fwd(c, fl, 1) == (BF16_HALO,) for (c, fls) in H["conv3x3"] for fl in fls)
+    finally:
+        L.r3m_debug_set_conv3x3_bf16(old)
+    assert {(route_sig.shape_class(c[1], c[2]), c[4]) for (c, _) in H["conv3x3"]} >= {(o, co) for o in ("wide", "tall") for co in (64, 128)}
+    assert any(rows(c) % 128 for (c, _) in H["conv3x3"] if c[4] == 128) and any(rows(c) % 256 for (c, _) in H["conv3x3"] if c[4] == 64)
+    # input gradients
+    J = E.JOIN_GROUPS
+    s2 = [c for (c, m) in J["accumulate_stride2"]]
+    assert all(m == "accumulate" and c[5:] == (1, 2, 0) for (c, m) in J["accumulate_stride2"])
+    assert {(c[1] % 2, c[2] % 2) for c in s2} == {(1, 0), (0, 1), (1, 1), (0, 0)}
+    assert {dgr(c, ACCUM) for c in s2} == {(PW_STRIDED,), (21,)} and all(dgr(c, ACCUM, 1) == (BF16,) for c in s2)     # ONE launch: three classes skipped
+    assert all(c[3:] == (64, 256, 1, 1, 0) and dgr(c, ACCUM) == (PW_POINT,) for (c, m) in J["accumulate_stride1"])
+    jn = [c for (c, m) in J["join"]]
+    assert all(m == "join" and c[6] == 1 for (c, m) in J["join"])
+    assert {dgr(c, MASKED_ADD)[0] for c in jn} == {WIN, PW_POINT, PW_GATHER} and {dgr(c, MASKED_ADD, 1)[0] for c in jn} == {BF16, BF16_HALO, BF16_ROW}
+    assert any(c[3:] == (64, 64, 3, 1, 1) and dgr(c, MASKED_ADD) == (PW_GATHER,) for c in jn)                         # the first-block form
+    assert {c[3] for c in jn if c[5] == 3} >= {64, 128, 256}
+
+
+def test_tile_queue_cases_pass_the_launchers_threshold():
+    """conv_pw.hip launch_pw_shape hands the queues on when gridM >= 64 (and at least 64 blocks, which that implies): every queue case
+    marked `used` has every launch at or above it on the persistent kernel, the others have every launch below; gridM covers 64, 74
+    (= 9 x 8 + 2: a ragged last group of panels) against 63, gridN 1 and more, both tile widths, and a four-launch stride-2 input gradient"""
+    from r3m_amd import _lib
+    import test_gpu_conv_epilogues as E
+    L = _lib.lib()
+    seen, kinds = set(), set()
+    for (kind, case, flags, used) in E.QUEUE_CASES:
+        dgrad, fl = {"fwd_stats": (0, STATS), "affine": (0, flags), "dgrad": (1, 0), "accumulate": (1, ACCUM)}[kind]
+        grids = route_sig.pw_queue_grids(L, case, dgrad, fl)
+        assert grids, (kind, case, "not on the persistent kernel")
+        assert all((gm >= 64) == used for (gm, gn) in grids), (kind, case, grids)
+        seen |= {(gm, min(gn, 2), case[3 if dgrad else 4] % 128 == 0) for (gm, gn) in grids}
+        kinds.add((kind, used, len(grids)))
+    assert {(64, 1, True), (74, 1, True), (74, 2, True), (63, 1, True), (74, 1, False)} <= seen, seen
+    assert {("fwd_stats", True, 1), ("fwd_stats", False, 1), ("affine", True, 1), ("affine", False, 1), ("dgrad", True, 1), ("dgrad", True, 4),
+            ("accumulate", True, 1)} <= kinds, kinds
+    # the burst launches of 64-wide outputs run the 512 x 64 tile: 6 x 56 x 56 rows are 37 panels there, NOT a queue case
+    assert route_sig.pw_queue_grids(L, (6, 56, 56, 64, 64, 3, 1, 1), 0, STATS) == ((37, 1),)

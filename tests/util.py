@@ -456,3 +456,250 @@ def unpack_bits(words, n):
     """uint32 / int32 words (numpy) -> bool [n]: element j = bit j & 31 of word j >> 5"""
     w = np.asarray(words).view(np.uint32)
     return (((w[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1).reshape(-1)[:n]).astype(bool)
+
+
+# ---- the conv epilogues and the tile queues that only the engine launched (tests/test_gpu_conv_epilogues.py) ----------------------------
+# r3m_conv2d_fwd_affine_dt, r3m_conv2d_dgrad_join_dt and r3m_debug_next_launch_tile_queues against float64 on the operands the kernel
+# multiplies. Ceilings: the ones check_conv_fp32 / check_conv_bf16 / check_dgrad_bnred use for the same stores (fp32 2e-5 of the output
+# range; bf16 2^-8 max, 2^-9 l2: the fused stores round once). Every body asserts its input conditions on the float64 reference.
+AFFINE, ACCUM, RELU = 128, 2, 16
+
+
+def describe_bad(got_nhwc, ref_nhwc, tol_abs):
+    """WHERE a [.., C] result is off: whole 128-row tiles (scheduling), single rows (addressing), columns (epilogue operands) or everything"""
+    C_ = ref_nhwc.shape[-1]
+    d = (got_nhwc.double() - ref_nhwc.double()).abs().reshape(-1, C_)
+    bad = (~torch.isfinite(d)) | (d > tol_abs)
+    rows = torch.nonzero(bad.any(1)).flatten()
+    cols = torch.nonzero(bad.any(0)).flatten()
+    return (f"non-finite {int((~torch.isfinite(d)).sum())}; {len(rows)} bad rows of {d.shape[0]} (first {rows[:6].tolist()}, last "
+            f"{rows[-3:].tolist()}, 128-row tiles {sorted(set((rows // 128).tolist()))[:12]}); {len(cols)} bad columns of {C_} (first "
+            f"{cols[:6].tolist()}, last {cols[-3:].tolist()})")
+
+
+def assert_close_store(what, got_nchw, ref_nchw, dtype):
+    """got (fp32 values, CPU, NCHW) against the float64 reference under the shared ceilings; the figures are printed before they are asserted"""
+    import pytest
+    e_max, e_l2 = rel_err(got_nchw.numpy(), ref_nchw.numpy())
+    print(f"{what}: max-rel {e_max:.3e} l2-rel {e_l2:.3e}")
+    ok = e_max < 2e-5 if dtype == "fp32" else (e_max < EPS_BF16 and e_l2 < EPS_BF16 / 2)
+    if not ok:
+        tol = (2e-5 if dtype == "fp32" else EPS_BF16) * float(ref_nchw.abs().max())
+        pytest.fail(f"{what}: max-rel {e_max} l2-rel {e_l2}; " + describe_bad(nhwc(got_nchw), nhwc(ref_nchw), tol))
+
+
+def assert_range(ref, summands, what):
+    """the output range is at least 1/4 of the largest summand's: no cancellation that would make a relative ceiling meaningless"""
+    top = max(float(s.abs().max()) for s in summands)
+    assert float(ref.abs().max()) >= 0.25 * top > 0, f"{what}: output range {float(ref.abs().max())} against summands up to {top}"
+
+
+class tile_queues:
+    """`with tile_queues(hip, sets) as ctr:` the next convolution launches of this thread draw their tiles from sets x 8 zeroed counters
+    (what the engine's TileCounters hands every launch); taken back on exit whatever happened"""
+
+    def __init__(self, hip, sets=1):
+        self.hip, self.sets = hip, sets
+        self.ctr = torch.zeros(sets * 8, dtype=torch.int32, device=DEV)
+
+    def __enter__(self):
+        self.hip.r3m_debug_next_launch_tile_queues(self.ctr.data_ptr(), self.sets)
+        return self.ctr
+
+    def __exit__(self, *exc):
+        self.hip.r3m_debug_next_launch_tile_queues(None, 0)
+        return False
+
+
+def assert_queues_used(ctr, sets_used, what):
+    """a launch that drew its tiles from the queues leaves every counter of its set non-zero (every block takes at least one ticket);
+    one that kept the static split leaves them zero"""
+    c = ctr.cpu().view(-1, 8)
+    used = [bool((row > 0).all()) for row in c]
+    idle = [bool((row == 0).all()) for row in c]
+    assert used[:sets_used] == [True] * sets_used and idle[sets_used:] == [True] * (len(c) - sets_used), f"{what}: tile counters {c.tolist()}"
+
+
+def _dev_ops(case, dtype):
+    tdt = torch.float32 if dtype == "fp32" else torch.bfloat16
+    q = (lambda t: t) if dtype == "fp32" else q_bf16
+    return tdt, q, (0 if dtype == "fp32" else 1)
+
+
+def check_conv_affine(hip, case, flags, dtype, queues=0):
+    """r3m_conv2d_fwd_affine_dt (the inference store: flags 128, 128|16, 128|2|16) against float64 [relu](conv * scale + shift [+ residual]).
+    fp32: also torch.equal to r3m_conv2d_fwd followed by r3m_bn_act_fwd (the header's claim for r3m_resnet_forward, per launch).
+    queues = 1: the launch once more with tile queues, torch.equal to the static one, the queues really used; queues = -1: handed over
+    but the launcher must keep the static split."""
+    N, Hi, Wi, Ci, Co, k, s, p = case
+    tdt, q, dt = _dev_ops(case, dtype)
+    x = q(rnd((N, Ci, Hi, Wi), 1))
+    w = q(rnd((Co, Ci, k, k), 2, -0.2, 0.2))
+    y = F.conv2d(x.double(), w.double(), stride=s, padding=p)
+    Ho, Wo = y.shape[2], y.shape[3]
+    sd = float(y.pow(2).mean().sqrt())
+    scale = rnd((Co,), 21, 0.5, 1.5)
+    shift = rnd((Co,), 22, -0.6, 0.6) * sd
+    res = q(rnd(tuple(y.shape), 23) * sd) if flags & ACCUM else None
+    terms = [y * scale.double().view(1, -1, 1, 1), shift.double().view(1, -1, 1, 1).expand_as(y)] + ([res.double()] if res is not None else [])
+    t = sum(terms[1:], terms[0])
+    ref = torch.relu(t) if flags & RELU else t
+    what = f"affine forward {dtype} flags {flags} {case}"
+    assert_range(ref, terms, what)
+    if flags & RELU:
+        zeros = float((ref == 0).double().mean())
+        assert 0.2 <= zeros <= 0.8, f"{what}: {zeros:.2f} of the reference outputs are zero"
+    if res is not None:
+        assert float(res.abs().max()) > 0
+
+    xd = nhwc(x).to(DEV).to(tdt)
+    wd = w.permute(0, 2, 3, 1).contiguous().to(DEV).to(tdt)               # OHWI (bf16: the values are bf16 already)
+    sc, sh = scale.to(DEV), shift.to(DEV)
+
+    def launch():
+        out = nhwc(res).to(DEV).to(tdt) if res is not None else torch.full((N, Ho, Wo, Co), float("nan"), dtype=tdt, device=DEV)
+        rc = hip.r3m_conv2d_fwd_affine_dt(xd.data_ptr(), wd.data_ptr(), out.data_ptr(), sc.data_ptr(), sh.data_ptr(), N, Hi, Wi, Ci, Co, k, s, p,
+                                          flags, dt, _st())
+        assert rc == 0, hip.r3m_last_error()
+        return out
+
+    out = launch()
+    assert_close_store(what, nchw(out.float().cpu()), ref, dtype)
+    if dtype == "fp32":
+        yd = torch.full((N, Ho, Wo, Co), float("nan"), device=DEV)
+        assert hip.r3m_conv2d_fwd(xd.data_ptr(), wd.data_ptr(), yd.data_ptr(), None, N, Hi, Wi, Ci, Co, k, s, p, _st()) == 0, hip.r3m_last_error()
+        coef = torch.stack([torch.zeros(Co), torch.ones(Co), scale, shift]).contiguous().to(DEV)
+        z = torch.full((N, Ho, Wo, Co), float("nan"), device=DEV)
+        rd = nhwc(res).to(DEV) if res is not None else None
+        rc = hip.r3m_bn_act_fwd(yd.data_ptr(), coef.data_ptr(), None if rd is None else rd.data_ptr(), None, None, z.data_ptr(), N * Ho * Wo, Co,
+                                1 if flags & RELU else 0, None, _st())
+        assert rc == 0, hip.r3m_last_error()
+        if not torch.equal(out, z):
+            import pytest
+            pytest.fail(f"{what}: the fused store differs from conv + bn_act_fwd: " + describe_bad(out.cpu(), z.cpu(), 0.0))
+    if queues:
+        with tile_queues(hip, 1) as ctr:
+            out_q = launch()
+            assert_queues_used(ctr, 1 if queues > 0 else 0, what)
+        if not torch.equal(out_q, out):
+            import pytest
+            pytest.fail(f"{what}: the launch with tile queues differs from the static split: " + describe_bad(out_q.cpu(), out.cpu(), 0.0))
+
+
+def check_dgrad_join(hip, case, mode, dtype, queues=0):
+    """r3m_conv2d_dgrad_join_dt against float64. mode 'accumulate': dx_old + dgrad with dx_old non-zero everywhere; at a strided 1x1 the
+    pixels of the tap-less parity classes must come back bit-identical. mode 'join': dgrad + residual_grad * [bits], dx pre-filled with NaN.
+    queues = n > 0: once more with n counter sets of tile queues of which the launches that reach the threshold use one each (all that run,
+    in these cases), torch.equal to the static launch."""
+    import pytest
+    N, Hi, Wi, Ci, Co, k, s, p = case
+    tdt, q, dt = _dev_ops(case, dtype)
+    Ho, Wo = (Hi + 2 * p - k) // s + 1, (Wi + 2 * p - k) // s + 1
+    w = q(rnd((Co, Ci, k, k), 2, -0.2, 0.2))
+    dy = q(rnd((N, Co, Ho, Wo), 3))
+    xr = torch.zeros((N, Ci, Hi, Wi), dtype=torch.float64, requires_grad=True)
+    F.conv2d(xr, w.double(), stride=s, padding=p).backward(dy.double())
+    dg = xr.grad
+    sd = float(dg.pow(2).mean().sqrt())
+    what = f"dgrad {mode} {dtype} {case}"
+    if mode == "accumulate":
+        old = q(rnd((N, Ci, Hi, Wi), 31, 0.25, 1.0) * torch.where(rnd((N, Ci, Hi, Wi), 32) > 0, 1.0, -1.0) * sd)
+        assert bool((old != 0).all()), f"{what}: the old contents must be non-zero everywhere"
+        terms, ref = [dg, old.double()], dg + old.double()
+        res = bits = None
+    else:
+        res = q(rnd((N, Ci, Hi, Wi), 5) * sd)
+        mask = rnd((N, Ci, Hi, Wi), 6) > 0.0
+        frac = float(mask.double().mean())
+        assert 0.2 <= frac <= 0.8, f"{what}: {frac:.2f} of the bits are set"
+        assert float((res.double() * mask).abs().max()) > 0
+        terms, ref = [dg, res.double() * mask], dg + res.double() * mask
+        bits = torch.from_numpy(pack_bits(nhwc(mask)).astype(np.int64)).to(torch.int32).to(DEV)
+    assert_range(ref, terms, what)
+
+    dyd = nhwc(dy).to(DEV).to(tdt)
+    wd = w.permute(0, 2, 3, 1).contiguous().to(DEV)                        # fp32 master (the entry point transposes / converts)
+    wsb = hip.r3m_conv2d_dgrad_workspace_bytes(Ci, Co, k)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=DEV)
+    resd = nhwc(res).to(DEV).to(tdt) if res is not None else None
+
+    def launch():
+        dxd = nhwc(old).to(DEV).to(tdt) if mode == "accumulate" else torch.full((N, Hi, Wi, Ci), float("nan"), dtype=tdt, device=DEV)
+        rc = hip.r3m_conv2d_dgrad_join_dt(dyd.data_ptr(), wd.data_ptr(), dxd.data_ptr(), ws.data_ptr(), wsb, N, Hi, Wi, Ci, Co, k, s, p,
+                                          1 if mode == "accumulate" else 0, None if resd is None else resd.data_ptr(),
+                                          None if bits is None else bits.data_ptr(), dt, _st())
+        assert rc == 0, hip.r3m_last_error()
+        return dxd
+
+    dxd = launch()
+    dx = nchw(dxd.float().cpu())
+    assert_close_store(what, dx, ref, dtype)
+    if mode == "accumulate" and k == 1 and s > 1:
+        untouched = torch.ones((Hi, Wi), dtype=torch.bool)
+        untouched[::s, ::s] = False
+        assert bool(untouched.any()) and torch.equal(dx[:, :, untouched], old[:, :, untouched]), \
+            f"{what}: a pixel of a parity class without taps did not keep its old contents bit for bit"
+    if queues:
+        with tile_queues(hip, queues) as ctr:
+            dx_q = launch()
+            launches = 1 if (s == 1 or k == 1) else 4
+            assert_queues_used(ctr, launches, what)
+        if not torch.equal(dx_q, dxd):
+            pytest.fail(f"{what}: the launch with tile queues differs from the static split: " + describe_bad(dx_q.cpu(), dxd.cpu(), 0.0))
+
+
+def check_conv_queues(hip, case, kind, used=True):
+    """fp32 r3m_conv2d_fwd with statistics (kind 'fwd_stats') or r3m_conv2d_dgrad (kind 'dgrad'; four counter sets, one per parity launch of
+    a stride-2 3x3) with tile queues: NaN-prefilled output against float64 (a tile no queue serves stays NaN) and torch.equal to the
+    static launch (per tile the order of the MFMA sums is the same). used = False: the launcher must keep the static split."""
+    import pytest
+    N, Hi, Wi, Ci, Co, k, s, p = case
+    x = rnd((N, Ci, Hi, Wi), 1)
+    w = rnd((Co, Ci, k, k), 2, -0.2, 0.2)
+    wd = w.permute(0, 2, 3, 1).contiguous().to(DEV)
+    what = f"tile queues {kind} {case}"
+    if kind == "fwd_stats":
+        ref = F.conv2d(x.double(), w.double(), stride=s, padding=p)
+        Ho, Wo = ref.shape[2], ref.shape[3]
+        xd = nhwc(x).to(DEV)
+        rows = hip.r3m_conv2d_stats_rows(N, Hi, Wi, Co, k, s, p)
+        sets, launches = 1, 1
+
+        def launch():
+            yd = torch.full((N, Ho, Wo, Co), float("nan"), device=DEV)
+            stats = torch.full((rows, 2, Co), float("nan"), device=DEV)
+            rc = hip.r3m_conv2d_fwd(xd.data_ptr(), wd.data_ptr(), yd.data_ptr(), stats.data_ptr(), N, Hi, Wi, Ci, Co, k, s, p, _st())
+            assert rc == 0, hip.r3m_last_error()
+            return yd, stats
+    else:
+        Ho, Wo = (Hi + 2 * p - k) // s + 1, (Wi + 2 * p - k) // s + 1
+        dy = rnd((N, Co, Ho, Wo), 3)
+        xr = torch.zeros((N, Ci, Hi, Wi), dtype=torch.float64, requires_grad=True)
+        F.conv2d(xr, w.double(), stride=s, padding=p).backward(dy.double())
+        ref = xr.grad
+        dyd = nhwc(dy).to(DEV)
+        wsb = hip.r3m_conv2d_dgrad_workspace_bytes(Ci, Co, k)
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=DEV)
+        sets = 4
+        launches = 1 if s == 1 else (4 if k == 3 else 1)
+
+        def launch():
+            dxd = torch.full((N, Hi, Wi, Ci), float("nan"), device=DEV)
+            rc = hip.r3m_conv2d_dgrad(dyd.data_ptr(), wd.data_ptr(), dxd.data_ptr(), ws.data_ptr(), wsb, N, Hi, Wi, Ci, Co, k, s, p, _st())
+            assert rc == 0, hip.r3m_last_error()
+            return dxd, None
+
+    out_s, stats_s = launch()
+    with tile_queues(hip, sets) as ctr:
+        out_q, stats_q = launch()
+        assert_queues_used(ctr, launches if used else 0, what)
+    assert_close_store(what + " (queues)", nchw(out_q.cpu()), ref, "fp32")
+    assert_close_store(what + " (static)", nchw(out_s.cpu()), ref, "fp32")
+    if not torch.equal(out_q, out_s):
+        pytest.fail(f"{what}: the launch with tile queues differs from the static split: " + describe_bad(out_q.cpu(), out_s.cpu(), 0.0))
+    if stats_s is not None:
+        assert torch.isfinite(stats_q).all(), f"{what}: a statistics row was not written"
+        assert torch.equal(stats_q, stats_s), f"{what}: the statistics partials differ between the queue and the static launch"
+        yr = ref.double()
+        np.testing.assert_allclose(stats_q[:, 0].double().sum(0).cpu().numpy(), yr.sum((0, 2, 3)).numpy(), rtol=1e-4, atol=1e-3 * float(yr.abs().max()))
+        np.testing.assert_allclose(stats_q[:, 1].double().sum(0).cpu().numpy(), (yr * yr).sum((0, 2, 3)).numpy(), rtol=1e-4)
