@@ -120,7 +120,7 @@ struct WgradParams {
   int debug;           // timing probes (probe builds, R3M_WG_DEBUG: 1 no DMA at all, 2 no X pieces, 4 no dY pieces); 0 in production
 };
 
-// ---- launchers (conv.hip) ----
+// ---- launchers (conv.hip): fp32 forward / input-gradient gather-GEMM, dgrad weight transposes ----
 int debug_occupancy(int* out4);
 int launch_gather_gemm(const GatherGemmParams& p, hipStream_t s);
 double gather_gemm_alg_bytes(const GatherGemmParams& p, int elem_bytes);
@@ -130,24 +130,32 @@ int gather_gemm_grid_m(int M, int Nc);   // number of row blocks the launcher wi
 // kernel: a block that finds its CU shared with another stream's kernel — RCCL during an overlapped all-reduce — simply takes
 // fewer tiles). Consumed (and cleared) by that launch whether or not it uses them; launches without it assign tiles statically.
 void gg_set_tile_counters(unsigned* ctr8, int sets = 1);
+int gg_set_dynamic_tiles(int on);        // diagnostic switch (r3m_debug_set_dynamic_tiles): 0 = ignore the counters, assign statically
 void gg_route_record_begin(int* out, int cap);   // dry run on this thread: launch_gather_gemm records its kernel family and launches nothing
 int gg_route_record_end();                       // -> launches seen since begin
-bool wgrad_rowwin_eligible(const WgradParams& p);                       // wgrad_win.hip: 3x3 / stride 1 / pad 1, fp32, whole 64- or 128-wide tiles
-int launch_wgrad_rowwin(WgradParams& p, int splitK, hipStream_t s);
-int gg_set_dynamic_tiles(int on);        // diagnostic switch (r3m_debug_set_dynamic_tiles): 0 = ignore the counters, assign statically
-bool pw_gemm_eligible(const GatherGemmParams& p);
-int pw_gemm_form(const GatherGemmParams& p);            // 0 none, 1 pointwise, 2 gather, 3 gather with strided output rows          // conv_pw.hip: persistent kernel for 1x1 / stride-1 launches (fp32)
-int launch_pw_gemm(const GatherGemmParams& p, hipStream_t s);
-int launch_wgrad(const WgradParams& p, int splitK, hipStream_t s);
-int wgrad_pick_split(int M, int Co, int Ci, int T);
-int launch_wgrad_reduce(const float* partial, float* dW, long long n, int splitK, int accumulate, hipStream_t s);
 struct WtEntry { long long w_off, wt_off; int Co, T, Ci, pad_; };
 int launch_transpose_w_all(const float* params, void* wt, const WtEntry* tab, const int* tile0, int n, int tiles, int dt, hipStream_t s);
 int launch_transpose_w(const float* W, float* Wt, int Co, int T, int Ci, hipStream_t s);
+
+// ---- launchers (conv_pw.hip): persistent kernel for 1x1 / stride-1 launches and dense or parity-strided gathers (fp32) ----
+bool pw_gemm_eligible(const GatherGemmParams& p);
+int pw_gemm_form(const GatherGemmParams& p);            // 0 none, 1 pointwise, 2 gather, 3 gather with strided output rows
+int launch_pw_gemm(const GatherGemmParams& p, hipStream_t s);
+
+// ---- launchers (wgrad.hip): fp32 weight gradient ----
+int launch_wgrad(const WgradParams& p, int splitK, hipStream_t s);
+int wgrad_pick_split(int M, int Co, int Ci, int T);
+int launch_wgrad_reduce(const float* partial, float* dW, long long n, int splitK, int accumulate, hipStream_t s);
+int wgrad_debug_occupancy(int* out);     // debug_occupancy's fourth output
+
+// ---- launchers (wgrad_win.hip): 3x3 / stride 1 / pad 1, fp32, whole 64- or 128-wide tiles ----
+bool wgrad_rowwin_eligible(const WgradParams& p);
+int launch_wgrad_rowwin(WgradParams& p, int splitK, hipStream_t s);
+
+// ---- launchers (stem.hip): the fp32 stem of 224 x 224 frames ----
 int launch_stem_prep(const float* x_nchw, float* xn, int F, hipStream_t s);
 struct FrameSource;   // augment_dev.h: raw clips + crop boxes
 int launch_stem_prep_crop(const FrameSource& src, float* xn, int F, hipStream_t s);
-int launch_stem_prep16_crop(const FrameSource& src, void* xn16, int F, hipStream_t s);
 int launch_stem_fwd(const float* xn, const float* w147, void* y, float* stats, int F, int dt, hipStream_t s);
 size_t stem_wgrad_ws_floats();
 int launch_stem_wgrad(const float* xn, const void* dY, float* dw147, float* ws, int F, int accumulate, int dt, hipStream_t s);
@@ -178,6 +186,7 @@ int launch_transpose_w_bf16(const float* W, void* Wt, int Co, int T, int Ci, hip
 // ---- launchers (stem_bf16.hip): the stem on the bf16 MFMA, from a padded bf16 image of the normalised frames ----
 size_t stem_xn16_bytes(int F);
 int launch_stem_prep16(const float* x_nchw, void* xn16, int F, hipStream_t s);
+int launch_stem_prep16_crop(const FrameSource& src, void* xn16, int F, hipStream_t s);
 int launch_stem_fwd16(const void* xn16, const float* w147, void* y, float* stats, int F, hipStream_t s);
 size_t stem_wgrad16_ws_floats();
 int launch_stem_wgrad16(const void* xn16, const void* dY, float* dw147, float* ws, int F, int accumulate, hipStream_t s);

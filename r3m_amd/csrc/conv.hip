@@ -1,32 +1,41 @@
-// r3m_amd — convolution hot path for gfx950 (MI355X): NHWC fp32 implicit GEMM on the f32-input MFMA
+// r3m_amd — fp32 forward / input-gradient convolutions for gfx950 (MI355X): NHWC implicit GEMM on the f32-input MFMA
 // (v_mfma_f32_32x32x2_f32, exact fp32 == fmaf chain), LDS-staged operand tiles, XCD-aware block order.
 //
-// Replaces what the reference reaches through torchvision's ResNet -> ATen conv2d / cuDNN
-// (call sites /root/reference/r3m/models/models_r3m.py:44-52,99): forward, dgrad and wgrad of every
-// 1x1 / 3x3 / 7x7 convolution of ResNet-18/34/50, plus nn.Linear of the language
-// reward head (/root/reference/r3m/models/models_language.py:43-51), which is the same GEMM with a bias epilogue.
+// Replaces what the reference reaches through torchvision's ResNet -> ATen conv2d / cuDNN (r3m/models/models_r3m.py): forward and
+// dgrad of every 1x1 / 3x3 convolution of ResNet-18/34/50 behind the stem, plus nn.Linear of the language reward head
+// (r3m/models/models_language.py), which is the same GEMM with a bias epilogue.
 //
-//   * gather-GEMM : out[m, n] = sum_{tap, c} in[pix(m) + off(tap), c] * W[n, tap, c]
-//       forward conv (taps = kh,kw; input stride = conv stride), dgrad (taps flipped; stride-2 dgrad is run as
-//       4 output-parity classes so no MFMA work is spent on structural zeros), Linear (1 tap).
-//       Epilogues: raw store (+ BatchNorm sum / sum-of-squares partials), accumulate, masked residual-gradient add,
-//       bias (+ReLU), ReLU-mask.  Kernels (128x128 tiles, or 256x64 for 64-channel outputs):
-//         gather_gemm_glds2_kernel : the production kernel. global -> LDS directly (global_load_lds_dwordx4), XOR-swizzled 128-byte
-//                                    rows, low-VALU K loop (pointer arrays, two K tiles per iteration), DMA pieces issued between MFMAs
-//         gather_gemm_glds_kernel  : generic direct-to-LDS variant (odd Cin/32; timing probes)
-//         gather_gemm_kernel       : global -> VGPR -> LDS fallback, 36-float padded rows (R3M_GG_GLDS=0)
-//   * wgrad_glds_kernel / wgrad_kernel : dW[co, tap, ci] = sum_m dY[m, co] * in[pix(m) + off(tap), ci]   (split-K over m, XCD-aware order)
-//   * stem_prep / stem_fwd / stem_wgrad : conv1 7x7/2 straight from the frames (no im2col in HBM); legacy im2col route kept in the C ABI
-//   (bf16 plans run conv_bf16.hip / stem_bf16.hip instead.)
+//   gather-GEMM : out[m, n] = sum_{tap, c} in[pix(m) + off(tap), c] * W[n, tap, c]
+//     forward conv (taps = kh,kw; input stride = conv stride), dgrad (taps flipped; stride-2 dgrad is run as 4 output-parity
+//     classes so no MFMA work is spent on structural zeros), Linear (1 tap).
+//     Epilogues (conv_dev.h gg_epilogue): raw store (+ BatchNorm sum / sum-of-squares partials), accumulate, masked
+//     residual-gradient add, bias (+ReLU), ReLU-mask, BatchNorm-backward partials; the window kernel also eval-mode BatchNorm.
+//
+// launch_gather_gemm = requirements -> gg_prepare (packed taps) -> gg_route (a pure function of the launch) -> switch (route).
+// Tiles are 128 x 128 ("wide": Nc a multiple of 128) or 256 x 64. Route numbers are public (r3m_debug_conv_route):
+//    1      conv3x3_win_kernel        3x3 / stride 1 / pad 1, wide, W <= 28: the 128- to 512-channel 3x3 layers, forward and dgrad
+//   11-13   conv_pw.hip               persistent kernel (pointwise / gather / strided output rows): every other ResNet launch whose
+//                                     channel counts are multiples of 64 — the 1x1 layers, the 64-channel and wider-than-28 3x3 layers,
+//                                     the stride-2 layers and their parity-class dgrads
+//   20      gather_gemm_k16_kernel    wide, one tap, K <= 256, N >= 2 K, where the persistent kernel does not apply: Ci = 32 / 96 / 160 / 224,
+//                                     an epilogue it does not build (bias of a Linear), a 1x1 / stride-2 downsample whose output map is
+//                                     under 2 rows x 4 columns (frames near 32 x 32)
+//   21      gather_gemm_glds2_kernel  every other launch with Ci/32 even, Ci <= 2048; wide <128,128,2,2> or narrow <256,64,4,1>: 3x3 layers on
+//                                     maps under 2 x 4 outputs, the 128-wide dgrad with residual join + BatchNorm partials on maps wider than
+//                                     28, the Linear layers
+//   22      gg_other_kernel():        odd Ci/32 or Ci > 2048 — r3m_conv2d_* / r3m_linear_* and the fuzz tests on 96- and 160-channel sides
+//             gather_gemm_glds_kernel             wide
+//             gather_gemm_kernel<256,64,4,1>      narrow (global -> VGPR -> LDS, 36-float padded rows)
+//             gather_gemm_kernel<128,128,2,2>     probe builds with R3M_GG_GLDS=0 (A/B of the register-staged predecessor)
+//   30-33   conv_bf16.hip             bf16 plans: handed to launch_gather_gemm_bf16 before any fp32 requirement
+// Also here: the dgrad weight transposes (transpose_w_kernel, transpose_w_all_kernel) and debug_occupancy.
+// The weight gradients are in wgrad.hip / wgrad_win.hip, the 224 x 224 stem in stem.hip.
 //
 // All staging is branch-free: taps that fall outside the image and rows past the end read a valid dummy address (a
 // zero line / a clamped pixel) instead of being skipped, so the loader is straight-line code the compiler can interleave
 // with the MFMA stream; the tap table is a dword array in the kernarg segment (scalar loads).
 #include "common.h"
 #include "conv_dev.h"
-#include "augment_dev.h"
-#include <cstdlib>
-#include <cstring>
 #include <utility>
 
 namespace r3m {
@@ -961,13 +970,21 @@ static int gg_route(const GatherGemmParams& p) {
   if (R3M_ENV_INT("R3M_GG_PW", 1) && pw_gemm_eligible(p)) return GG_ROUTE_PW + pw_gemm_form(p);
   return glds2 ? GG_ROUTE_GLDS2 : GG_ROUTE_OTHER;
 }
+
+// What launch_gather_gemm and gather_gemm_fuses_affine do to their copy of the parameters before anything looks at it: the packed tap
+// table the kernels and gg_route read, and the probe switch. It checks nothing, so the query answers for any parameters.
+static void gg_prepare(GatherGemmParams& p) {
+  for (int t = 0; t < p.ntaps; ++t)
+    p.tap[t] = (int)((unsigned)(unsigned char)p.dy[t] | ((unsigned)(unsigned char)p.dx[t] << 8) | ((unsigned)p.wt[t] << 16));
+  p.debug = R3M_ENV_INT("R3M_GG_DEBUG", 0);   // timing probes only (wrong results when != 0)
+}
+
 // inference forward: can this launch apply eval-mode BatchNorm (+ residual) (+ ReLU) where it stores (EPI_AFFINE family)? True for the
 // kernels every ResNet layer runs (the persistent kernel, the 3x3 window kernel; every bf16 kernel); the engine falls back to
 // conv + bn_act_fwd for anything else (odd shapes of the fuzz tests).
 bool gather_gemm_fuses_affine(const GatherGemmParams& p_in) {
   GatherGemmParams p = p_in;
-  for (int t = 0; t < p.ntaps; ++t)
-    p.tap[t] = (int)((unsigned)(unsigned char)p.dy[t] | ((unsigned)(unsigned char)p.dx[t] << 8) | ((unsigned)p.wt[t] << 16));
+  gg_prepare(p);
   if (p.dtype == DT_BF16) return (p.Nc & 7) == 0 && (p.Ci & 63) == 0 && gg16_route_builds(gg16_route(p), p.flags);
   const int r = gg_route(p);
   if (r == GG_ROUTE_WIN) return p.flags == (EPI_AFFINE | EPI_RELU) || p.flags == (EPI_AFFINE | EPI_ACCUM | EPI_RELU);
@@ -977,926 +994,116 @@ static thread_local int* t_route_out = nullptr;      // dry run (r3m_debug_conv_
 static thread_local int t_route_n = 0, t_route_cap = 0;
 void gg_route_record_begin(int* out, int cap) { t_route_out = out; t_route_n = 0; t_route_cap = cap; }
 int gg_route_record_end() { const int n = t_route_n; t_route_out = nullptr; t_route_n = t_route_cap = 0; return n; }
+static int gg_route_record(int route) {
+  if (t_route_n < t_route_cap) t_route_out[t_route_n] = route;
+  ++t_route_n;
+  return 0;
+}
+
+// The three kernels behind GG_ROUTE_OTHER (launches gg_route leaves to neither the window, the persistent, the 16-wide-K nor the
+// low-VALU kernel; no ResNet layer, but r3m_conv2d_* / r3m_linear_* and the fuzz tests on 96- and 160-channel sides):
+//   GG_OTHER_GLDS   wide, odd Ci/32 (or Ci > 2048; probe builds: R3M_GG_GLDS=1)    gather_gemm_glds_kernel
+//   GG_OTHER_NARROW narrow (Nc no multiple of 128)                                  gather_gemm_kernel<256,64,4,1>
+//   GG_OTHER_REG    wide, probe build with R3M_GG_GLDS=0                            gather_gemm_kernel<128,128,2,2>
+enum : int { GG_OTHER_GLDS, GG_OTHER_NARROW, GG_OTHER_REG };
+static int gg_other_kernel(bool wide) {
+  if (!wide) return GG_OTHER_NARROW;
+#ifdef R3M_PROBES
+  if (!gg_use_glds()) return GG_OTHER_REG;
+#endif
+  return GG_OTHER_GLDS;
+}
 
 int launch_gather_gemm(const GatherGemmParams& p_in, hipStream_t s) {
   GatherGemmParams p = p_in;
   p.tile_ctr = t_tile_ctr;     // one set of counters serves ONE launch: the parity-class launches of a stride-2 dgrad take the next
   if (t_tile_ctr && --t_tile_ctr_sets > 0) t_tile_ctr += 8;   // set each, and the next layer must not reuse any of them
   else { t_tile_ctr = nullptr; t_tile_ctr_sets = 0; }
+  R3M_REQUIRE(p.ntaps >= 0 && p.ntaps <= MAX_TAPS, "gather_gemm: ntaps=%d", p.ntaps);     // both precisions
+  R3M_REQUIRE(p.M > 0 && p.Nc > 0, "gather_gemm: empty problem M=%d Nc=%d", p.M, p.Nc);
+  gg_prepare(p);
   if (p.dtype == DT_BF16) {
-    {
-      const int dbg = R3M_ENV_INT("R3M_GG_DEBUG", 0);
-      p.debug = dbg;   // timing probes only (wrong results when != 0)
-    }
-    R3M_REQUIRE(p.ntaps >= 0 && p.ntaps <= MAX_TAPS, "gather_gemm: ntaps=%d", p.ntaps);
-    R3M_REQUIRE(p.M > 0 && p.Nc > 0, "gather_gemm: empty problem M=%d Nc=%d", p.M, p.Nc);
-    for (int t = 0; t < p.ntaps; ++t)
-      p.tap[t] = (int)((unsigned)(unsigned char)p.dy[t] | ((unsigned)(unsigned char)p.dx[t] << 8) | ((unsigned)p.wt[t] << 16));
-    if (t_route_out) {
-      if (t_route_n < t_route_cap) t_route_out[t_route_n] = gg16_route(p);    // 30 gather, 31 halo, 32 kernel-row (GG_ROUTE_BF16 + family)
-      ++t_route_n;
-      return 0;
-    }
+    if (t_route_out) return gg_route_record(gg16_route(p));    // 30 gather, 31 halo, 32 kernel-row (GG_ROUTE_BF16 + family)
     return launch_gather_gemm_bf16(p, s);
   }
   R3M_REQUIRE(p.Ci % 32 == 0, "gather_gemm: Ci=%d must be a multiple of 32", p.Ci);
   R3M_REQUIRE(p.Nc % 4 == 0, "gather_gemm: Nc=%d must be a multiple of 4", p.Nc);
-  R3M_REQUIRE(p.ntaps >= 0 && p.ntaps <= MAX_TAPS, "gather_gemm: ntaps=%d", p.ntaps);
-  R3M_REQUIRE(p.M > 0 && p.Nc > 0, "gather_gemm: empty problem M=%d Nc=%d", p.M, p.Nc);
   R3M_REQUIRE((reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.B) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(p.out) & 15) == 0,
               "gather_gemm: operands must be 16-byte aligned");
-  {
-    const int dbg = R3M_ENV_INT("R3M_GG_DEBUG", 0);
-    p.debug = dbg;   // timing probes only (wrong results when != 0)
-  }
-  for (int t = 0; t < p.ntaps; ++t)
-    p.tap[t] = (int)((unsigned)(unsigned char)p.dy[t] | ((unsigned)(unsigned char)p.dx[t] << 8) | ((unsigned)p.wt[t] << 16));
-  const double kdim = (double)p.ntaps * p.Ci;
-  const double flops = 2.0 * (double)p.M * (double)p.Nc * kdim;
   const int route = gg_route(p);
-  if (t_route_out) {
-    if (t_route_n < t_route_cap) t_route_out[t_route_n] = route;
-    ++t_route_n;
-    return 0;
-  }
-  if (gg_wide(p.Nc)) {
-    const int grid = ceil_div(p.M, 128) * ceil_div(p.Nc, 128);
-    prof_begin(KC_GEMM_WIDE, flops, p.M, p.Nc, p.Ci, p.ntaps, s);
-    {
-      if (route == GG_ROUTE_WIN) {
-        typedef WinCfg<128, 128, 192> Cfg;
+  if (t_route_out) return gg_route_record(route);
+  const bool wide = gg_wide(p.Nc);       // 128 x 128 tiles, or 256 x 64 for outputs that are no multiple of 128 wide
+  const int grid = wide ? ceil_div(p.M, 128) * ceil_div(p.Nc, 128) : ceil_div(p.M, 256) * ceil_div(p.Nc, 64);
+  const double flops = 2.0 * (double)p.M * (double)p.Nc * ((double)p.ntaps * p.Ci);
+  prof_begin(wide ? KC_GEMM_WIDE : KC_GEMM_NARROW, flops, p.M, p.Nc, p.Ci, p.ntaps, s);
+  const char* what = "gather_gemm";
+#define LAUNCH_GG(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(grid), dim3(256), 0, s, p)
+  switch (route) {
+    case GG_ROUTE_WIN: {
+      typedef WinCfg<128, 128, 192> Cfg;
 #define LAUNCH_WIN(E)                                                                                                        \
   do {                                                                                                                       \
     static DynLdsOptIn oi;                                                                                                   \
     if (int e = ensure_dyn_lds(oi, reinterpret_cast<const void*>(conv3x3_win_kernel<128, 128, 2, 2, 192, E>), Cfg::LDS, "conv3x3_win")) return e; \
     hipLaunchKernelGGL((conv3x3_win_kernel<128, 128, 2, 2, 192, E>), dim3(grid), dim3(256), Cfg::LDS, s, p);                 \
   } while (0)
-        switch (p.flags) {                       // inference forward (round 6): eval-mode BatchNorm (+ residual in `out`) + ReLU at the store
-          case EPI_AFFINE | EPI_RELU: LAUNCH_WIN(EPI_AFFINE | EPI_RELU); break;
-          case EPI_AFFINE | EPI_ACCUM | EPI_RELU: LAUNCH_WIN(EPI_AFFINE | EPI_ACCUM | EPI_RELU); break;
-          default:
-            GG_EPI_SWITCH(LAUNCH_WIN)
-        }
-#undef LAUNCH_WIN
-        prof_bytes(gather_gemm_alg_bytes(p, 4));
-        prof_end(s);
-        return check_launch("conv3x3_win");
+      switch (p.flags) {                       // inference forward (round 6): eval-mode BatchNorm (+ residual in `out`) + ReLU at the store
+        case EPI_AFFINE | EPI_RELU: LAUNCH_WIN(EPI_AFFINE | EPI_RELU); break;
+        case EPI_AFFINE | EPI_ACCUM | EPI_RELU: LAUNCH_WIN(EPI_AFFINE | EPI_ACCUM | EPI_RELU); break;
+        default:
+          GG_EPI_SWITCH(LAUNCH_WIN)
       }
+#undef LAUNCH_WIN
+      what = "conv3x3_win";
+      break;
     }
-    if (route > GG_ROUTE_PW && route < GG_ROUTE_K16) {   // dense or parity-strided output rows: persistent kernel (conv_pw.hip)
+    case GG_ROUTE_PW + 1:
+    case GG_ROUTE_PW + 2:
+    case GG_ROUTE_PW + 3:     // dense or parity-strided output rows: persistent kernel (conv_pw.hip), four-wave 128-wide or eight-wave 64-wide tile
       if (int e = launch_pw_gemm(p, s)) return e;
-      prof_bytes(gather_gemm_alg_bytes(p, 4));
-      prof_end(s);
-      return check_launch("pw_gemm");
-    }
-    if (route == GG_ROUTE_K16) {
-#define LAUNCH_K16(E) hipLaunchKernelGGL((gather_gemm_k16_kernel<E>), dim3(grid), dim3(256), 0, s, p)
+      what = "pw_gemm";
+      break;
+    case GG_ROUTE_K16: {
+#define LAUNCH_K16(E) LAUNCH_GG(gather_gemm_k16_kernel<E>)
       GG_EPI_SWITCH(LAUNCH_K16)
 #undef LAUNCH_K16
-    } else if (route == GG_ROUTE_GLDS2) {
-#define LAUNCH_GLDS2(E) hipLaunchKernelGGL((gather_gemm_glds2_kernel<128, 128, 2, 2, E>), dim3(grid), dim3(256), 0, s, p)
-      GG_EPI_SWITCH(LAUNCH_GLDS2)
+      break;
+    }
+    case GG_ROUTE_GLDS2: {
+#define LAUNCH_GLDS2(E) LAUNCH_GG(gather_gemm_glds2_kernel<128, 128, 2, 2, E>)
+#define LAUNCH_NARROW2(E) LAUNCH_GG(gather_gemm_glds2_kernel<256, 64, 4, 1, E>)
+      if (wide) { GG_EPI_SWITCH(LAUNCH_GLDS2) }
+      else { GG_EPI_SWITCH(LAUNCH_NARROW2) }
 #undef LAUNCH_GLDS2
-#ifdef R3M_PROBES
-    } else if (!gg_use_glds()) {   // register-staged 128x128 kernel: A/B only (R3M_GG_GLDS=0)
-#define LAUNCH_REG(E) hipLaunchKernelGGL((gather_gemm_kernel<128, 128, 2, 2, E>), dim3(grid), dim3(256), 0, s, p)
-      GG_EPI_SWITCH(LAUNCH_REG)
-#undef LAUNCH_REG
-#endif
-    } else {                       // odd Ci/32 (not a ResNet shape; reachable through r3m_conv2d_fwd / r3m_linear_fwd): generic direct-to-LDS kernel
-#define LAUNCH_GLDS(E) hipLaunchKernelGGL((gather_gemm_glds_kernel<E>), dim3(grid), dim3(256), 0, s, p)
-      GG_EPI_SWITCH(LAUNCH_GLDS)
-#undef LAUNCH_GLDS
-    }
-  } else {
-    const int grid = ceil_div(p.M, 256) * ceil_div(p.Nc, 64);
-    prof_begin(KC_GEMM_NARROW, flops, p.M, p.Nc, p.Ci, p.ntaps, s);
-    if (route > GG_ROUTE_PW && route < GG_ROUTE_K16) {   // 64-wide output: persistent kernel, eight-wave 256 x 64 tile
-      if (int e = launch_pw_gemm(p, s)) return e;
-      prof_bytes(gather_gemm_alg_bytes(p, 4));
-      prof_end(s);
-      return check_launch("pw_gemm");
-    }
-    if (route == GG_ROUTE_GLDS2) {
-#define LAUNCH_NARROW2(E) hipLaunchKernelGGL((gather_gemm_glds2_kernel<256, 64, 4, 1, E>), dim3(grid), dim3(256), 0, s, p)
-      GG_EPI_SWITCH(LAUNCH_NARROW2)
 #undef LAUNCH_NARROW2
-    } else {
-#define LAUNCH_NARROW(E) hipLaunchKernelGGL((gather_gemm_kernel<256, 64, 4, 1, E>), dim3(grid), dim3(256), 0, s, p)
-      GG_EPI_SWITCH(LAUNCH_NARROW)
+      break;
+    }
+    case GG_ROUTE_OTHER:
+    default: {                // gg_route returns nothing else; as before, a route that is none of the above runs a gather kernel
+#define LAUNCH_GLDS(E) LAUNCH_GG(gather_gemm_glds_kernel<E>)
+#define LAUNCH_NARROW(E) LAUNCH_GG(gather_gemm_kernel<256, 64, 4, 1, E>)
+#define LAUNCH_REG(E) LAUNCH_GG(gather_gemm_kernel<128, 128, 2, 2, E>)
+      switch (gg_other_kernel(wide)) {
+        case GG_OTHER_NARROW: GG_EPI_SWITCH(LAUNCH_NARROW) break;
+#ifdef R3M_PROBES
+        case GG_OTHER_REG: GG_EPI_SWITCH(LAUNCH_REG) break;
+#endif
+        default: GG_EPI_SWITCH(LAUNCH_GLDS) break;
+      }
+#undef LAUNCH_GLDS
 #undef LAUNCH_NARROW
+#undef LAUNCH_REG
+      break;
     }
   }
+#undef LAUNCH_GG
   prof_bytes(gather_gemm_alg_bytes(p, 4));
   prof_end(s);
-  return check_launch("gather_gemm");
+  return check_launch(what);
 }
 
-#ifdef R3M_PROBES   // register-staged predecessor of wgrad_glds_kernel: kept for A/B in probe builds (R3M_WG_GLDS=0), not shipped
-// =====================================================================================================
-// wgrad: dW[co, tap, ci] = sum_m dY[m, co] * X[pix(m) + off(tap), ci].  GEMM M' = Co tile, N' = Ci tile,
-// K' = rows m (split over blockIdx.y). Both operands arrive row(m)-major with channels contiguous, which is exactly
-// the [k][i] LDS image the 32x32x2 MFMA wants for conflict-free ds_read_b32 fragment reads.
-// Staging is branch-free (clamped addresses + select-to-zero at the LDS write); the (n, oy, ox) decode of the rows a thread
-// stages is advanced incrementally (+32 rows per K step) instead of dividing.
-// =====================================================================================================
-template <int BMt, int BNt>
-__global__ __launch_bounds__(256) void wgrad_kernel(const WgradParams p) {
-  constexpr int BK = 32;
-  constexpr int TM = BMt / 64, TN = BNt / 64;
-  constexpr int AJ = BMt / 32, BJ = BNt / 32;
-  constexpr int A_F4 = BMt / 4, B_F4 = BNt / 4;        // float4 per staged row
-  constexpr int A_RPP = 256 / A_F4, B_RPP = 256 / B_F4;  // rows per pass
-  __shared__ __attribute__((aligned(16))) float smem[BK * (BMt + BNt)];
-  float* sA = smem;
-  float* sB = smem + BK * BMt;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int T = p.KH * p.KW;
-  const int lid = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int bx = lid % p.gx, by = lid / p.gx;   // by = split index: consecutive logical blocks read the same rows
-  const int tap = bx % T;  // the taps of one (co, ci) tile are neighbours: they re-read the same dY rows
-  const int tile = bx / T;
-  const int tn_ = tile % p.tilesN, tm_ = tile / p.tilesN;
-  const int co0 = tm_ * BMt, ci0 = tn_ * BNt;
-  const int kh = tap / p.KW, kw = tap - kh * p.KW;
-  const int ms = by * p.rows_per_split;
-  const int me = min(p.M, ms + p.rows_per_split);
-
-  const int a_c = (tid % A_F4) * 4, a_r = tid / A_F4;
-  const int b_c = (tid % B_F4) * 4, b_r = tid / B_F4;
-  const bool a_cv = (co0 + a_c) < p.Co;
-  const bool b_cv = (ci0 + b_c) < p.Ci;
-  const int a_col = a_cv ? co0 + a_c : 0;
-  const int b_col = b_cv ? ci0 + b_c : 0;
-  const int hw = p.Ho * p.Wo;
-
-  const int q32 = 32 / p.Wo, r32 = 32 - q32 * p.Wo;
-  const bool fast_adv = (q32 + 1) <= p.Ho;        // one conditional subtract per axis is enough
-  const long long img = (long long)p.Hi * p.Wi * p.Ci;
-  long long xb[BJ];
-  int xoy[BJ], xox[BJ];
-#pragma unroll
-  for (int j = 0; j < BJ; ++j) {
-    const int m = ms + b_r + j * B_RPP;
-    if (p.simple_rows) {
-      xb[j] = 0; xoy[j] = 0; xox[j] = 0;
-    } else {
-      const int n = m / hw;
-      const int rem = m - n * hw;
-      xoy[j] = rem / p.Wo;
-      xox[j] = rem - xoy[j] * p.Wo;
-      xb[j] = (long long)n * img;
-    }
-  }
-
-  f32x4 ra[AJ], rb[BJ];
-  unsigned a_ok = 0, b_ok = 0;
-  auto load_tile = [&](int mk) {
-    unsigned oka = 0, okb = 0;
-#pragma unroll
-    for (int j = 0; j < AJ; ++j) {
-      const int m = mk + a_r + j * A_RPP;
-      const bool ok = (m < me) && a_cv;
-      oka |= (ok ? 1u : 0u) << j;
-      const int mc = min(m, me - 1);
-      ra[j] = ldg4(p.dY + (long long)mc * p.Co + a_col);
-    }
-#pragma unroll
-    for (int j = 0; j < BJ; ++j) {
-      const int m = mk + b_r + j * B_RPP;
-      const bool mok = (m < me) && b_cv;
-      long long off;
-      bool in = true;
-      if (p.simple_rows) {
-        off = (long long)min(m, me - 1) * p.Ci;
-      } else {
-        const int iy = xoy[j] * p.stride + kh - p.pad, ix = xox[j] * p.stride + kw - p.pad;
-        in = ((unsigned)iy < (unsigned)p.Hi) && ((unsigned)ix < (unsigned)p.Wi);
-        const int iyc = min(max(iy, 0), p.Hi - 1), ixc = min(max(ix, 0), p.Wi - 1);
-        off = xb[j] + ((long long)iyc * p.Wi + ixc) * p.Ci;
-        off = (m < me) ? off : 0;       // rows past the split: any valid address, masked below
-      }
-      okb |= ((mok && in) ? 1u : 0u) << j;
-      rb[j] = ldg4(p.X + off + b_col);
-    }
-    a_ok = oka; b_ok = okb;
-    if (!p.simple_rows) {               // advance the decode to the next K step (+32 rows)
-      if (fast_adv) {
-#pragma unroll
-        for (int j = 0; j < BJ; ++j) {
-          int ox = xox[j] + r32, oy = xoy[j] + q32;
-          const bool cx = ox >= p.Wo;
-          ox = cx ? ox - p.Wo : ox;
-          oy = cx ? oy + 1 : oy;
-          const bool cy = oy >= p.Ho;
-          oy = cy ? oy - p.Ho : oy;
-          xb[j] = cy ? xb[j] + img : xb[j];
-          xox[j] = ox; xoy[j] = oy;
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < BJ; ++j) {
-          const int m = mk + 32 + b_r + j * B_RPP;
-          const int n = m / hw;
-          const int rem = m - n * hw;
-          xoy[j] = rem / p.Wo;
-          xox[j] = rem - xoy[j] * p.Wo;
-          xb[j] = (long long)n * img;
-        }
-      }
-    }
-  };
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int a = 0; a < TM; ++a)
-#pragma unroll
-    for (int b = 0; b < TN; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-  const int lrow = lane & 31, lh = lane >> 5;
-  const float* fragA = sA + lh * BMt + wm * TM * 32 + lrow;
-  const float* fragB = sB + lh * BNt + wn * TN * 32 + lrow;
-
-  if (ms < me) load_tile(ms);
-  for (int mk = ms; mk < me; mk += BK) {
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < AJ; ++j)
-      *reinterpret_cast<f32x4*>(sA + (a_r + j * A_RPP) * BMt + a_c) = ((a_ok >> j) & 1u) ? ra[j] : zero4;
-#pragma unroll
-    for (int j = 0; j < BJ; ++j)
-      *reinterpret_cast<f32x4*>(sB + (b_r + j * B_RPP) * BNt + b_c) = ((b_ok >> j) & 1u) ? rb[j] : zero4;
-    __syncthreads();
-    if (mk + BK < me) load_tile(mk + BK);
-#pragma unroll
-    for (int kk = 0; kk < BK / 2; ++kk) {
-      float a[TM], b[TN];
-#pragma unroll
-      for (int t = 0; t < TM; ++t) a[t] = fragA[kk * 2 * BMt + t * 32];
-#pragma unroll
-      for (int t = 0; t < TN; ++t) b[t] = fragB[kk * 2 * BNt + t * 32];
-#pragma unroll
-      for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-          acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-
-  float* out = p.out + (long long)by * p.Co * T * p.Ci;
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (co >= p.Co) continue;
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        const int ci = ci0 + (wn * TN + tn) * 32 + lrow;
-        if (ci < p.Ci) out[((long long)co * T + tap) * p.Ci + ci] = acc[tm][tn][r];
-      }
-    }
-}
-
-#endif  // R3M_PROBES
-
-// =====================================================================================================
-// wgrad, direct-to-LDS staging through BUFFER addressing (round 3). Same GEMM as the register-staged probe kernel; the
-// [k][channel] LDS image is lane-linear (a row of 64 or 128 floats = 256/512 B, one DMA instruction covers 4 or 2 consecutive
-// k rows), so no swizzle is needed and the b32 fragment reads stay conflict-free. Two stages, one barrier per K step.
-//
-// Why buffer addressing: on gfx950 the f32-input MFMA shares the SIMD's fp32 lanes with the VALU, so every vector
-// instruction in the K loop costs matrix time. `global_load_lds` needs a 64-bit per-lane address, i.e. per DMA
-// piece a 64-bit add, the (oy, ox) walk, four compares and a pointer select in VALU — ~25 vector instructions per X piece of a
-// 3x3 convolution, ~125 per 64 MFMAs. `buffer_load_dwordx4 ... lds` takes a wave-uniform 128-bit descriptor (base, bytes) in
-// SGPRs plus a 32-bit per-lane offset, and lanes whose offset is >= the descriptor's byte count land ZEROS in LDS
-// (tools/micro/bufload.hip). So:
-//   * dY, and X of 1x1/stride-1 convolutions (rows are linear in m): the per-lane offset is a CONSTANT; a K step advances the
-//     descriptor base by 32 rows and shrinks its byte count with four scalar instructions — rows past the end of the split
-//     fall off the descriptor and read zeros. No vector instruction per piece at all.
-//   * X of 3x3 / strided convolutions: a DMA instruction covers only 2 (128-wide tile) or 4 (64-wide) consecutive rows m, and
-//     which rows is wave-uniform — the (frame, oy, ox) walk, the tap shift and the padding test of every staged row run on the
-//     SCALAR unit (in the shadow of the MFMAs); a padding row gets an out-of-range offset. Per lane: pick its row's scalar
-//     offset and add the channel offset = 3 (or 6) vector instructions per piece.
-// =====================================================================================================
-// NT = 3 ("kernel rows", round 3): one block owns the THREE taps (kh, 0..2) of one row of a 3-wide kernel for its (co, ci) tile,
-// with three accumulator sets: the dY rows of a K step are staged and read from LDS ONCE for the three taps, the scalar cursor
-// walk is shared (the taps differ by one pixel in x) — 2/3 of the DMA instructions and fragment reads per MFMA of the per-tap
-// form. K steps of 16 rows keep the two stages at 64 KB (128-wide tile: 2 blocks per CU as before).
-template <int BMt, int BNt, int BK = 32, int NT = 1, int IL = -1, int SR = -1>   // IL: DMA pieces spread between the MFMAs (1), in one burst (0), or p.interleave (-1); SR: 1x1 "simple rows" known at compile time (1 / 0) or p.simple_rows (-1)
-__global__ __launch_bounds__(256, (NT == 3 && BMt == 128) ? 2 : 1) void wgrad_glds_kernel(const WgradParams p) {
-  static_assert(BK == 32 || BK == 16, "K step of 32 or 16 rows");
-  static_assert(NT == 1 || NT == 3, "one tap, or the three taps of a kernel row");
-  // 128x128: waves 1 x 4, each 128 (co, interleaved: MFMA tile tm owns channels 4*i + tm) x 32 (ci) -> the A fragment of all
-  // four tiles is ONE ds_read_b128 per K pair; 64x64: waves 2 x 2, each 32 x 32.
-  constexpr bool WIDE = (BMt == 128);
-  constexpr int TM = WIDE ? 4 : BMt / 64, TN = WIDE ? 1 : BNt / 64;
-  constexpr int WR = BK / 4;                            // k rows staged per wave per stage
-  constexpr int A_RPI = 256 / BMt, B_RPI = 256 / BNt;   // k rows covered by one 1 KiB DMA instruction
-  constexpr int AJ = WR / A_RPI, BJ = WR / B_RPI;       // DMA pieces per wave per stage (a B piece = NT instructions)
-  static_assert(AJ >= 1 && BJ >= 1, "a wave stages whole DMA instructions");
-  constexpr int B_TILE = BK * BNt;                      // floats of one tap's X tile
-  constexpr int STAGE = BK * BMt + NT * B_TILE;
-  __shared__ __attribute__((aligned(128))) float smem[2 * STAGE];
-
-  const bool simple_rows = NT == 1 && (SR < 0 ? p.simple_rows != 0 : SR != 0);   // a kernel-row block (NT = 3) never has 1x1 "simple" rows
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = WIDE ? 0 : (wave_s >> 1), wn = WIDE ? wave_s : (wave_s & 1);
-  const int T = p.KH * p.KW;
-  const int TG = T / NT;                                // tap groups per tile (NT = 3: kernel rows)
-  const int lid = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int bx = lid % p.gx, by = lid / p.gx;   // by = split index: consecutive logical blocks read the same rows
-  const int tap0 = (bx % TG) * NT;
-  const int tile = bx / TG;
-  const int tn_ = tile % p.tilesN, tm_ = tile / p.tilesN;
-  const int co0 = tm_ * BMt, ci0 = tn_ * BNt;
-  const int kh = tap0 / p.KW, kw0 = tap0 - kh * p.KW;
-  const int ms = by * p.rows_per_split;
-  const int me = min(p.M, ms + p.rows_per_split);
-  const int hw = p.Ho * p.Wo;
-
-  // lane -> (k row within the instruction, first channel); the per-lane offsets below never change in the K loop
-  const int a_k = lane / (BMt / 4), a_c = (lane % (BMt / 4)) * 4;
-  const int b_k = lane / (BNt / 4), b_c = (lane % (BNt / 4)) * 4;
-  const unsigned a_chan = (co0 + a_c) < p.Co ? (unsigned)a_c * 4u : BUF_OOB;
-  const unsigned b_chan = (ci0 + b_c) < p.Ci ? (unsigned)b_c * 4u : BUF_OOB;
-
-  // A operand (dY): descriptor = [row ms + BK*step, end of the split) x channels from co0
-  const float* a_base = p.dY + (long long)ms * p.Co + co0;
-  int a_left = (int)(((long long)(me - ms) * p.Co - co0) * 4);      // bytes (host: a split spans < 2 GB)
-  const int a_stepb = BK * p.Co * 4;
-  unsigned a_voff[AJ];
-#pragma unroll
-  for (int j = 0; j < AJ; ++j) a_voff[j] = (unsigned)((wave_s * WR + j * A_RPI + a_k) * p.Co) * 4u + a_chan;
-
-  // B operand (X)
-  const long long img = (long long)p.Hi * p.Wi * p.Ci;
-  const float* b_base;
-  int b_left;
-  const int b_stepb = BK * p.Ci * 4;
-  unsigned b_voff[BJ];             // simple rows: constant per-lane offsets
-  // non-simple rows: ONE scalar cursor (frame offset, oy, ox) that walks the WR consecutive rows this wave stages per K step,
-  // then jumps the BK - WR rows to its rows of the next step; `c_left` = rows from the cursor to the end of the split
-  int c_ox = 0, c_oy = 0, c_left = 0;
-  unsigned c_f = 0;                // byte offset of the cursor row's frame from b_base
-  constexpr int JUMP = BK - WR;
-  const int qj = JUMP / p.Wo, rj = JUMP - qj * p.Wo;
-  const unsigned imgb = (unsigned)(img * 4);
-  const int pixb = p.Ci * 4;       // bytes between the X rows of neighbouring taps (one pixel)
-  const int kh_p = kh - p.pad, kw_p = kw0 - p.pad;
-  if (simple_rows) {
-    b_base = p.X + (long long)ms * p.Ci + ci0;
-    b_left = (int)(((long long)(me - ms) * p.Ci - ci0) * 4);
-#pragma unroll
-    for (int j = 0; j < BJ; ++j) b_voff[j] = (unsigned)((wave_s * WR + j * B_RPI + b_k) * p.Ci) * 4u + b_chan;
-  } else {
-    const int n0 = ms / hw;        // first frame of the split: 32-bit offsets are relative to it
-    b_base = p.X + (long long)n0 * img + ci0;
-    const long long rest = ((long long)(p.N - n0) * img - ci0) * 4;
-    b_left = rest < (long long)BUF_OOB ? (int)rest : (int)BUF_OOB;
-#pragma unroll
-    for (int j = 0; j < BJ; ++j) b_voff[j] = 0;
-    const int m = ms + wave_s * WR;
-    const int n = m / hw;
-    const int rem = m - n * hw;
-    c_oy = rem / p.Wo;
-    c_ox = rem - c_oy * p.Wo;
-    c_f = (unsigned)(n - n0) * imgb;
-    c_left = me - m;
-  }
-  bool b_is[B_RPI];                // lane masks: "my row is sub-row r of the instruction"
-#pragma unroll
-  for (int r = 0; r < B_RPI; ++r) b_is[r] = (b_k == r);
-
-  // one DMA piece (pc < AJ: dY rows, else X rows of all NT taps) into `stage`
-  auto issue_piece = [&](int stage, auto pc_c) __attribute__((always_inline)) {
-    constexpr int pc = decltype(pc_c)::value;
-    if (R3M_PROBE(p) & 1) return;                       // timing probes (probe builds only; wrong results)
-    if ((R3M_PROBE(p) & 2) && pc >= AJ) return;
-    if ((R3M_PROBE(p) & 4) && pc < AJ) return;
-    if constexpr (pc < AJ) {
-      constexpr int j = pc;
-      float* la = smem + stage * STAGE + wave_s * WR * BMt;
-      buf_dma16(a_base, a_left, la + j * A_RPI * BMt, a_voff[j]);
-    } else {
-      constexpr int j = pc - AJ;
-      float* lb = smem + stage * STAGE + BK * BMt + wave_s * WR * BNt + j * B_RPI * BNt;
-      if (simple_rows) {
-        buf_dma16(b_base, b_left, lb, b_voff[j]);
-      } else {
-        unsigned so[NT][B_RPI];
-#pragma unroll
-        for (int r = 0; r < B_RPI; ++r) {     // scalar unit: tap shift, padding tests, row offset, cursor to the next row
-          const int iy = c_oy * p.stride + kh_p, ix0 = c_ox * p.stride + kw_p;
-          const bool rowok = ((unsigned)iy < (unsigned)p.Hi) && (c_left > 0);
-          const unsigned off0 = c_f + (unsigned)((iy * p.Wi + ix0) * p.Ci) * 4u;
-#pragma unroll
-          for (int t = 0; t < NT; ++t)
-            so[t][r] = (rowok && (unsigned)(ix0 + t) < (unsigned)p.Wi) ? off0 + (unsigned)(t * pixb) : BUF_OOB;
-          c_left -= 1;
-          c_ox += 1;
-          if (c_ox == p.Wo) {
-            c_ox = 0;
-            c_oy += 1;
-            if (c_oy == p.Ho) { c_oy = 0; c_f += imgb; }
-          }
-        }
-        if constexpr (j == BJ - 1) {          // the wave's rows of this K step are issued: jump to its rows of the next one
-          c_left -= JUMP;
-          c_ox += rj;
-          if (c_ox >= p.Wo) { c_ox -= p.Wo; c_oy += 1; }
-          c_oy += qj;
-          while (c_oy >= p.Ho) { c_oy -= p.Ho; c_f += imgb; }
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          unsigned voff = so[t][0];
-#pragma unroll
-          for (int r = 1; r < B_RPI; ++r) voff = b_is[r] ? so[t][r] : voff;
-          buf_dma16(b_base, b_left, lb + t * B_TILE, voff + b_chan);
-        }
-      }
-    }
-  };
-  // after the last piece of a K step: both descriptors move on by BK rows (scalar)
-  auto advance = [&]() __attribute__((always_inline)) {
-    a_base += BK * p.Co;
-    a_left = a_left > a_stepb ? a_left - a_stepb : 0;
-    if (simple_rows) {
-      b_base += BK * p.Ci;
-      b_left = b_left > b_stepb ? b_left - b_stepb : 0;
-    }
-  };
-  auto issue = [&](int stage) __attribute__((always_inline)) {
-    static_for<AJ + BJ>([&](auto pc_c) __attribute__((always_inline)) { issue_piece(stage, pc_c); });
-    advance();
-  };
-
-  f32x16 acc[NT][TM][TN];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TN; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][a][b][r] = 0.f;
-
-  const int lrow = lane & 31, lh = lane >> 5;
-  const float* fragA = smem + lh * BMt + (WIDE ? 4 * lrow : wm * TM * 32 + lrow);
-  const float* fragB = smem + BK * BMt + lh * BNt + wn * TN * 32 + lrow;
-  // MFMAs of one stage; when dma_stage >= 0 the next K step's DMA pieces are spread between them so that their issue cost
-  // hides behind this wave's own MFMAs
-  auto mfma_stage = [&](const float* fa, const float* fb, int dma_stage) __attribute__((always_inline)) {
-    constexpr int NP = AJ + BJ;
-    constexpr int EVERY = (BK / 2) / NP;     // K pairs between two pieces
-    static_assert(EVERY >= 1, "at most one DMA piece per K pair");
-    static_for<BK / 2>([&](auto kk_c) __attribute__((always_inline)) {
-      constexpr int kk = decltype(kk_c)::value;
-      float a[TM];
-      if constexpr (WIDE) {
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(fa + kk * 2 * BMt);
-#pragma unroll
-        for (int t = 0; t < TM; ++t) a[t] = a4[t];
-      } else {
-#pragma unroll
-        for (int t = 0; t < TM; ++t) a[t] = fa[kk * 2 * BMt + t * 32];
-      }
-#pragma unroll
-      for (int tp = 0; tp < NT; ++tp) {
-        float b[TN];
-#pragma unroll
-        for (int t = 0; t < TN; ++t) b[t] = fb[tp * B_TILE + kk * 2 * BNt + t * 32];
-#pragma unroll
-        for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < TN; ++tn)
-            acc[tp][tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm], b[tn], acc[tp][tm][tn], 0, 0, 0);
-      }
-      if constexpr ((kk % EVERY) == EVERY - 1 && kk / EVERY < NP) {
-        if (dma_stage >= 0) {
-          __builtin_amdgcn_sched_barrier(0);
-          issue_piece(dma_stage, std::integral_constant<int, kk / EVERY>{});
-          if constexpr (kk / EVERY == NP - 1) advance();
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    });
-  };
-
-  const int nk = (me - ms + BK - 1) / BK;
-  if (nk > 0) issue(0);
-  int kt = 0;
-  const bool il = IL < 0 ? (p.interleave != 0) : (IL != 0);
-  for (; kt + 1 < nk; kt += 2) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (il) {
-      mfma_stage(fragA, fragB, 1);
-    } else {
-      issue(1);
-      mfma_stage(fragA, fragB, -1);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (il) {
-      mfma_stage(fragA + STAGE, fragB + STAGE, (kt + 2 < nk) ? 0 : -1);
-    } else {
-      if (kt + 2 < nk) issue(0);
-      mfma_stage(fragA + STAGE, fragB + STAGE, -1);
-    }
-  }
-  if (kt < nk) {   // odd tail
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    mfma_stage(fragA, fragB, -1);
-  }
-
-  float* out = p.out + (long long)by * p.Co * T * p.Ci;
-#pragma unroll
-  for (int tp = 0; tp < NT; ++tp)
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rho = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const int co = WIDE ? co0 + 4 * rho + tm : co0 + (wm * TM + tm) * 32 + rho;
-        if (co >= p.Co) continue;
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-          const int ci = ci0 + (wn * TN + tn) * 32 + lrow;
-          if (ci < p.Ci) out[((long long)co * T + tap0 + tp) * p.Ci + ci] = acc[tp][tm][tn][r];
-        }
-      }
-}
-
-// =====================================================================================================
-// Stem, direct: x/255 -> Normalize -> conv 7x7 stride 2 pad 3, 3 -> 64 channels (the reference's first three steps,
-// /root/reference/r3m/models/models_r3m.py:97-99 into torchvision's conv1), forward and weight gradient, straight from the
-// NCHW fp32 frames — no im2col matrix in HBM (that cost 8 MB written + 16 MB re-read per frame).
-// Geometry trick: for a fixed kernel row kh the 7 x 3 (kw, c) taps of one output pixel are 21 CONSECUTIVE floats of an
-// interleaved [x][c] image row, starting at 6*ox. So with the (normalised, zero-padded) input rows staged in LDS as
-// patch[y][(ix+3)*3 + c], the MFMA A-fragment of output pixel (oy, ox) for k = (kh, j) is patch[2*oy + kh][6*ox + j]:
-// a per-lane base plus an immediate — no address arithmetic in the K loop. K is walked as 7 x 22 (j = 21 multiplies a
-// zero weight), i.e. 154 instead of 147 MACs per output: 5 % padding instead of im2col's 160.
-// =====================================================================================================
-constexpr int ST_PS = 692;      // patch row stride (forward): 230 pixels x 3 channels (+2 pad)
-constexpr int ST_PSW = 694;     // patch row stride (weight gradient): == 22 (mod 32). There 32 lanes read patch[kh * stride + jj] for 32
-                                // CONSECUTIVE k = 22 kh + jj, which cross a kernel-row boundary; with 692 (== 20 mod 32) the lanes of
-                                // the next kernel row landed on the banks of jj = 20, 21 (2-way conflict on every B read: PMC
-                                // lds_conflict_frac 0.44, round 2); with 694 the bank is k mod 32 — conflict-free
-constexpr int ST_KS = 155;      // LDS weight row stride (odd: conflict-free fragment reads)
-constexpr int ST_K = 154;       // 7 kernel rows x 22
-
-// pre-pass: frames NCHW fp32 0..255 -> normalised, channel-interleaved rows xn[f][iy][ix*3 + c] (exactly the reference's
-// (x/255 - mean)/std with IEEE divisions, done once per frame; both stem kernels then stage plain row copies)
-__global__ __launch_bounds__(256) void stem_prep_kernel(const float* __restrict__ x, float* __restrict__ xn, long long total) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // one thread per (f, iy, ix)
-  if (i >= total) return;
-  const int ix = (int)(i % 224);
-  const long long t = i / 224;
-  const int iy = (int)(t % 224);
-  const long long f = t / 224;
-  float* o = xn + i * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) o[c] = stem_normalize(x[((f * 3 + c) * 224 + iy) * 224 + ix], c);
-}
-
-// the same pre-pass reading the RAW clips through their crop boxes (rc / rctraj on the GPU): the cropped fp32
-// frames [F,3,224,224] are never written — one gather-bilinear pass from uint8 (or float) straight into the normalised image
-template <typename T>
-__global__ __launch_bounds__(256) void stem_prep_crop_kernel(const T* __restrict__ raw, const int* __restrict__ boxes,
-                                                              float* __restrict__ xn, long long total, int Hi, int Wi, int fpb) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // one thread per (f, iy, ix)
-  if (i >= total) return;
-  const int ix = (int)(i % 224);
-  const long long t = i / 224;
-  const int iy = (int)(t % 224);
-  const long long f = t / 224;
-  const int* b = boxes + (f / fpb) * 4;
-  const int top = b[0], left = b[1], bh = b[2], bw = b[3];
-  float* o = xn + i * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-    o[c] = stem_normalize(bilinear_sample(raw + (f * 3 + c) * (long long)Hi * Wi, Wi, top, left, bh, bw, iy, ix, 0, 0, 224, 224), c);
-}
-
-int launch_stem_prep_crop(const FrameSource& src, float* xn, int F, hipStream_t s) {
-  const long long total = (long long)F * 224 * 224;
-  if (src.is_u8)
-    hipLaunchKernelGGL((stem_prep_crop_kernel<unsigned char>), dim3(ceil_div(total, 256)), dim3(256), 0, s,
-                       static_cast<const unsigned char*>(src.frames), src.boxes, xn, total, src.Hi, src.Wi, src.frames_per_box);
-  else
-    hipLaunchKernelGGL((stem_prep_crop_kernel<float>), dim3(ceil_div(total, 256)), dim3(256), 0, s,
-                       static_cast<const float*>(src.frames), src.boxes, xn, total, src.Hi, src.Wi, src.frames_per_box);
-  return check_launch("stem_prep_crop");
-}
-
-int launch_stem_prep(const float* x_nchw, float* xn, int F, hipStream_t s) {
-  const long long total = (long long)F * 224 * 224;
-  hipLaunchKernelGGL(stem_prep_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, x_nchw, xn, total);
-  return check_launch("stem_prep");
-}
-
-// stage `nrows` input rows iy0.. of frame f into patch[y][9 zeros | 672 data | zeros]: float4 row copies
-template <int PS = ST_PS>
-__device__ __forceinline__ void stem_load_patch(const float* __restrict__ xn, float* patch, long long f, int iy0, int nrows) {
-  constexpr int TAIL = PS - 681;      // zero floats behind the 672 data floats (9 in front)
-  for (int i = threadIdx.x; i < nrows * (9 + TAIL); i += 256) {
-    const int y = i / (9 + TAIL), e = i - y * (9 + TAIL);
-    patch[y * PS + (e < 9 ? e : 672 + e)] = 0.f;
-  }
-  for (int i = threadIdx.x; i < nrows * 168; i += 256) {
-    const int y = i / 168, q = i - y * 168;
-    const int iy = iy0 + y;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if ((unsigned)iy < 224u) v = ldg4(xn + ((f * 224 + iy) * 224) * 3 + q * 4);
-    float* d = patch + y * PS + 9 + q * 4;        // 9-float left border: not 16-byte aligned -> scalar LDS stores
-    d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
-  }
-}
-
-template <int EPI, class OT>
-__global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__ xn, const float* __restrict__ w,
-                                                        const GatherGemmParams p, int ntiles) {
-  constexpr int SMEM = 13 * ST_PS + 64 * ST_KS;
-  __shared__ __attribute__((aligned(16))) float smem[SMEM];
-  float* patch = smem;                 // also the epilogue's scratch (8704 floats < 13*ST_PS): the weights behind it survive
-  float* wl = smem + 13 * ST_PS;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  {   // weights once per (persistent) block
-    const int n = tid >> 2, q = tid & 3;            // 4 threads per output channel
-#pragma unroll
-    for (int kh = 0; kh < 7; ++kh)
-      for (int j = q; j < 22; j += 4) wl[n * ST_KS + kh * 22 + j] = (j < 21) ? w[n * 147 + kh * 21 + j] : 0.f;
-  }
-  const int lrow = lane & 31, lh = lane >> 5;
-  int b_base[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) b_base[t] = (t * 32 + lrow) * ST_KS + lh;
-
-  // Round 3: register prefetch — the 13 input rows of the NEXT tile (2184 float4, 9 per thread) are requested before this tile's
-  // MFMAs and written to LDS after its epilogue (whose slabs alias the patch), so their latency rides under the matrix work.
-  constexpr int PQ = (13 * 168 + 255) / 256;
-  f32x4 pre[PQ];
-  auto request = [&](int blk) __attribute__((always_inline)) {
-    const long long f = blk / 49;
-    const int iy0 = 2 * (((blk - (int)f * 49) * 256) / 112) - 3;
-#pragma unroll
-    for (int k = 0; k < PQ; ++k) {
-      const int i = tid + 256 * k;
-      const int y = i / 168, q = i - y * 168;
-      const int iy = iy0 + y;
-      pre[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (i < 13 * 168 && (unsigned)iy < 224u) pre[k] = ldg4(xn + ((f * 224 + iy) * 224) * 3 + q * 4);
-    }
-  };
-  auto commit = [&]() __attribute__((always_inline)) {
-    for (int i = tid; i < 13 * 20; i += 256) {       // zero borders: the epilogue's slabs overwrote them
-      const int y = i / 20, e = i - y * 20;
-      patch[y * ST_PS + (e < 9 ? e : 672 + e)] = 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < PQ; ++k) {
-      const int i = tid + 256 * k;
-      if (i < 13 * 168) {
-        const int y = i / 168, q = i - y * 168;
-        float* d = patch + y * ST_PS + 9 + q * 4;     // 9-float left border: not 16-byte aligned -> scalar LDS stores
-        d[0] = pre[k][0]; d[1] = pre[k][1]; d[2] = pre[k][2]; d[3] = pre[k][3];
-      }
-    }
-  };
-  if ((int)blockIdx.x < ntiles) {
-    request(blockIdx.x);
-    commit();
-  }
-  for (int blk = blockIdx.x; blk < ntiles; blk += gridDim.x) {
-    const long long f = blk / 49;
-    const int lm0 = (blk - (int)f * 49) * 256;    // first output pixel of this tile inside its frame (12544 = 49 * 256)
-    const int oy0 = lm0 / 112;
-    __syncthreads();                              // the patch of this tile (and, first time, the weights) is in LDS
-    const int nblk = blk + gridDim.x;
-    if (nblk < ntiles) request(nblk);
-    int a_base[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int lm = lm0 + wave * 64 + t * 32 + lrow;
-      const int oy = lm / 112, ox = lm - oy * 112;
-      a_base[t] = 2 * (oy - oy0) * ST_PS + 6 * ox + lh;
-    }
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-#pragma unroll
-    for (int kh = 0; kh < 7; ++kh)
-#pragma unroll
-      for (int jp = 0; jp < 11; ++jp) {
-        float a[2], b[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) a[t] = patch[a_base[t] + kh * ST_PS + 2 * jp];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) b[t] = wl[b_base[t] + kh * 22 + 2 * jp];
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < 2; ++tn)
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
-      }
-    __syncthreads();
-    gg_epilogue<256, 64, 4, 1, EPI, 13 * ST_PS, OT>(p, acc, smem, blk * 256, 0, blk);
-    __syncthreads();   // the epilogue slabs alias the patch that is refilled now
-    if (nblk < ntiles) commit();
-  }
-}
-
-int launch_stem_fwd(const float* x_nchw, const float* w147, void* y, float* stats, int F, int dt, hipStream_t s) {
-  GatherGemmParams p;
-  memset(&p, 0, sizeof p);
-  p.out = static_cast<float*>(y); p.stats = stats; p.dtype = dt;
-  p.M = F * 12544; p.Nc = 64; p.os = 1;
-  p.Hg = 112; p.Wg = 112; p.Ho = 112; p.Wo = 112;
-  const double flops = 2.0 * (double)p.M * 64.0 * 147.0;
-  prof_begin(KC_GEMM_NARROW, flops, p.M, 64, 147, 1, s);
-  prof_bytes((double)F * 224 * 224 * 3 * 4 + (double)p.M * 64 * (dt == DT_BF16 ? 2 : 4));
-  const int ntiles = F * 49;
-  const int grid = ntiles < 512 ? ntiles : 512;   // persistent blocks (2 per CU): the 39 KB weight image is staged once per block
-  if (dt == DT_BF16) {
-    if (stats) hipLaunchKernelGGL((stem_fwd_kernel<EPI_STATS, bf16_t>), dim3(grid), dim3(256), 0, s, x_nchw, w147, p, ntiles);
-    else hipLaunchKernelGGL((stem_fwd_kernel<0, bf16_t>), dim3(grid), dim3(256), 0, s, x_nchw, w147, p, ntiles);
-  } else {
-    if (stats) hipLaunchKernelGGL((stem_fwd_kernel<EPI_STATS, float>), dim3(grid), dim3(256), 0, s, x_nchw, w147, p, ntiles);
-    else hipLaunchKernelGGL((stem_fwd_kernel<0, float>), dim3(grid), dim3(256), 0, s, x_nchw, w147, p, ntiles);
-  }
-  prof_end(s);
-  return check_launch("stem_fwd");
-}
-
-// dW[co][kh*22 + j] partial of one block = sum over its output image rows of dY[m][co] * patch(m, kh, j).
-// One output image row (112 pixels = 56 K pairs) per iteration: 7 input rows + the dY row in LDS, per-lane bases plus
-// immediates (pixel step = 6 floats of the interleaved row). Waves: 2 (co halves) x 2 (k tiles {0,1,2} / {3,4}).
-template <class T>
-__global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ x, const T* __restrict__ dY,
-                                                          float* __restrict__ partial, int total_rows) {
-  __shared__ __attribute__((aligned(16))) float smem[112 * 64 + 7 * ST_PSW];
-  float* dys = smem;                  // 16-byte aligned (float4 stores); the patch takes scalar stores
-  float* patch = smem + 112 * 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 1, wj = wave & 1;
-  const int lrow = lane & 31, lh = lane >> 5;
-  const int jt0 = wj ? 3 : 0;
-  const int a_base = lh * 64 + wi * 32 + lrow;
-  int b_base[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    int j = (jt0 + t) * 32 + lrow;
-    if (j >= ST_K) j = 0;                       // columns 154..159 (and the unused third tile of the second wave column)
-    const int kh = j / 22, jj = j - kh * 22;
-    b_base[t] = kh * ST_PSW + jj + 6 * lh;
-  }
-  // two-level summation: `acc` covers one image row (112 products per element), `tot` adds the rows — short fp32 chains
-  f32x16 acc[3], tot[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) tot[t][r] = 0.f;
-
-  // Round 3: register prefetch. The next output row's operands (7 input rows = 1176 float4, the dY row = 1792 float4: 5 + 7 per
-  // thread) are requested BEFORE this row's MFMAs and written to LDS after them, so their global latency (~2 us of the ~6.5 us a
-  // row took) rides under the matrix work instead of in front of it. The zero borders of the patch rows never change: written once.
-  constexpr int PQ = (7 * 168 + 255) / 256, DQ = 112 * 16 / 256;     // 5, 7
-  f32x4 pre_p[PQ], pre_d[DQ];
-  auto request = [&](int row) __attribute__((always_inline)) {
-    const long long f = row / 112;
-    const int iy0 = 2 * (row - (int)f * 112) - 3;
-#pragma unroll
-    for (int k = 0; k < PQ; ++k) {
-      const int i = tid + 256 * k;
-      const int y = i / 168, q = i - y * 168;
-      const int iy = iy0 + y;
-      pre_p[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (i < 7 * 168 && (unsigned)iy < 224u) pre_p[k] = ldg4(x + ((f * 224 + iy) * 224) * 3 + q * 4);
-    }
-    const T* src = dY + (long long)row * 112 * 64;
-#pragma unroll
-    for (int k = 0; k < DQ; ++k) pre_d[k] = ld4t(src + (tid + 256 * k) * 4);
-  };
-  auto commit = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int k = 0; k < PQ; ++k) {
-      const int i = tid + 256 * k;
-      if (i < 7 * 168) {
-        const int y = i / 168, q = i - y * 168;
-        float* d = patch + y * ST_PSW + 9 + q * 4;     // 9-float left border: not 16-byte aligned -> scalar LDS stores
-        d[0] = pre_p[k][0]; d[1] = pre_p[k][1]; d[2] = pre_p[k][2]; d[3] = pre_p[k][3];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < DQ; ++k) *reinterpret_cast<f32x4*>(dys + (tid + 256 * k) * 4) = pre_d[k];
-  };
-  {
-    constexpr int TAIL = ST_PSW - 681;
-    for (int i = tid; i < 7 * (9 + TAIL); i += 256) {
-      const int y = i / (9 + TAIL), e = i - y * (9 + TAIL);
-      patch[y * ST_PSW + (e < 9 ? e : 672 + e)] = 0.f;
-    }
-  }
-  int row = blockIdx.x;
-  if (row < total_rows) {
-    request(row);
-    commit();
-  }
-  __syncthreads();
-  for (; row < total_rows; row += gridDim.x) {
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    const int next = row + gridDim.x;
-    if (next < total_rows) request(next);
-    if (wj == 0) {
-#pragma unroll
-      for (int q = 0; q < 56; ++q) {
-        const float a = dys[a_base + q * 128];
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, patch[b_base[t] + q * 12], acc[t], 0, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < 56; ++q) {
-        const float a = dys[a_base + q * 128];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, patch[b_base[t] + q * 12], acc[t], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 3; ++t) tot[t] += acc[t];
-    __syncthreads();                      // every wave is done reading this row's tiles
-    if (next < total_rows) commit();
-    __syncthreads();
-  }
-  float* out = partial + (long long)blockIdx.x * 64 * 160;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    if (t == 2 && wj) continue;                 // the second wave column owns k tiles 3 and 4 only
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      out[co * 160 + (jt0 + t) * 32 + lrow] = tot[t][r];
-    }
-  }
-}
-
-// persistent blocks: the kernel holds 130 VGPRs + 48 AGPRs -> TWO blocks per CU; 768 blocks (round 1) ran as one and a half rounds
-// of resident blocks with equal work each, i.e. the last third of the time at half occupancy
-#ifndef R3M_STEM_WG_BLOCKS
-#define R3M_STEM_WG_BLOCKS 512
-#endif
-constexpr int STEM_WG_BLOCKS = R3M_STEM_WG_BLOCKS;
-size_t stem_wgrad_ws_floats() { return (size_t)STEM_WG_BLOCKS * 64 * 160; }
-
-// dw147[co][kh*21 + j] (+)= dw160[co][kh*22 + j]
-__global__ void stem_unpack_dw22_kernel(const float* __restrict__ dw160, float* __restrict__ dw147, int accumulate) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 64 * 147) return;
-  const int co = i / 147, k = i - co * 147;
-  const int kh = k / 21, j = k - kh * 21;
-  const float v = dw160[co * 160 + kh * 22 + j];
-  dw147[i] = accumulate ? dw147[i] + v : v;
-}
-
-int launch_stem_wgrad(const float* x_nchw, const void* dY, float* dw147, float* ws /* stem_wgrad_ws_floats() + 64*160 */, int F,
-                      int accumulate, int dt, hipStream_t s) {
-  const int total_rows = F * 112;
-  const int nb = total_rows < STEM_WG_BLOCKS ? total_rows : STEM_WG_BLOCKS;
-  const double flops = 2.0 * (double)F * 12544.0 * 64.0 * 147.0;
-  prof_begin(KC_WGRAD_NARROW, flops, F * 12544, 64, 147, 1, s);
-  prof_bytes((double)F * 224 * 224 * 3 * 4 + (double)F * 12544 * 64 * (dt == DT_BF16 ? 2 : 4));
-  if (dt == DT_BF16)
-    hipLaunchKernelGGL((stem_wgrad_kernel<bf16_t>), dim3(nb), dim3(256), 0, s, x_nchw, static_cast<const bf16_t*>(dY), ws, total_rows);
-  else
-    hipLaunchKernelGGL((stem_wgrad_kernel<float>), dim3(nb), dim3(256), 0, s, x_nchw, static_cast<const float*>(dY), ws, total_rows);
-  prof_end(s);
-  if (int e = check_launch("stem_wgrad")) return e;
-  float* dw160 = ws + stem_wgrad_ws_floats();
-  if (int e = launch_wgrad_reduce(ws, dw160, 64 * 160, nb, 0, s)) return e;
-  hipLaunchKernelGGL(stem_unpack_dw22_kernel, dim3(ceil_div(64 * 147, 256)), dim3(256), 0, s, dw160, dw147, accumulate);
-  return check_launch("stem_unpack_dw22");
-}
-
-// debugging aid: resident blocks per CU the runtime predicts for the main kernel variants
+// debugging aid: resident blocks per CU the runtime predicts for the main kernel variants (the fourth is wgrad.hip's)
 int debug_occupancy(int* out4) {
   int n = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gather_gemm_glds2_kernel<128, 128, 2, 2, EPI_STATS>, 256, 0) != hipSuccess) return 1;
@@ -1905,157 +1112,7 @@ int debug_occupancy(int* out4) {
   out4[1] = n;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gather_gemm_glds2_kernel<256, 64, 4, 1, EPI_STATS>, 256, 0) != hipSuccess) return 1;
   out4[2] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, wgrad_glds_kernel<128, 128>, 256, 0) != hipSuccess) return 1;
-  out4[3] = n;
-  return 0;
-}
-
-#ifdef R3M_PROBES
-static bool wg_use_glds() {
-  const int v = R3M_ENV_INT("R3M_WG_GLDS", 1) != 0;
-  return v == 1;
-}
-#endif
-
-static inline bool wg_wide(int Co, int Ci) { return (Co % 128 == 0) && (Ci % 128 == 0); }
-// 3-wide kernels run one block per kernel row (wgrad_glds_kernel NT = 3). R3M_WG_ROWS=0 (probe builds): per-tap blocks.
-static bool wg_rows(int KW) {
-  const int v = R3M_ENV_INT("R3M_WG_ROWS", 1);
-  return v && KW == 3;
-}
-
-// Split-K factor: enough blocks for two full waves of resident blocks (128x128: 2 blocks/CU x 256 CUs; 64x64: 5/CU), as few
-// splits as that allows (every split writes and re-reads a full dW slab), never fewer than 8 K steps per block.
-int wgrad_pick_split(int M, int Co, int Ci, int T) {
-  const bool wide = wg_wide(Co, Ci);
-  const int bt = wide ? 128 : 64;
-  long long tiles = (long long)ceil_div(Co, bt) * ceil_div(Ci, bt) * T;
-  if (T == 9 && wg_rows(3)) tiles /= 3;     // kernel-row blocks cover three taps each
-  const int tgt = R3M_ENV_INT("R3M_WG_BLOCKS", 0);                       // probe builds: block target override
-  const long long target = tgt > 0 ? tgt : (wide ? 1024 : 2560);
-  long long split = target / tiles;   // floor: never spill a few blocks into an extra wave
-  const long long max_split = (M + 255) / 256;
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  long long rps = ((M + split - 1) / split + 31) / 32 * 32;
-  return ceil_div(M, rps);
-}
-
-int launch_wgrad(const WgradParams& p0, int splitK, hipStream_t s) {
-  WgradParams p = p0;
-  R3M_REQUIRE(p.Ci % 4 == 0 && p.Co % 4 == 0, "wgrad: channel counts must be multiples of 4 (Co=%d Ci=%d)", p.Co, p.Ci);
-  R3M_REQUIRE(splitK >= 1, "wgrad: splitK=%d", splitK);
-  p.rows_per_split = ((p.M + splitK - 1) / splitK + 31) / 32 * 32;
-  R3M_REQUIRE(ceil_div(p.M, p.rows_per_split) == splitK, "wgrad: splitK=%d does not tile M=%d", splitK, p.M);
-  {   // buffer addressing: a block's operands are reached through 32-bit offsets from the first row / frame of its split
-    const long long lim = 0x7FFFF000LL;
-    const long long a_span = (long long)p.rows_per_split * p.Co * 4;
-    const long long frames = (long long)p.rows_per_split / ((long long)p.Ho * p.Wo) + 2;
-    const long long b_span = p.simple_rows ? (long long)p.rows_per_split * p.Ci * 4 : frames * p.Hi * p.Wi * p.Ci * 4;
-    R3M_REQUIRE(a_span < lim && b_span < lim, "wgrad: one split spans %lld / %lld bytes (limit 2 GiB): raise splitK (%d)", a_span, b_span, splitK);
-  }
-  const int T = p.KH * p.KW;
-  {
-    // DMA pieces spread between the MFMAs (one per 2 K pairs) or issued in one burst before them. Round 3, buffer addressing,
-    // same box (profiles/r03_wgrad_buffer_ab.txt): spreading wins where a piece carries scalar work — the (oy, ox) walk of 3x3 /
-    // strided X rows on a 128-wide tile (115.8 -> 118-123 TFLOP/s) — and loses where it does not (1x1: 134 -> 130) and on the
-    // 64-wide tile (107.5 -> 100). Probe builds: R3M_WG_INTERLEAVE = 0 / 1 forces it.
-    const int il = R3M_ENV_INT("R3M_WG_INTERLEAVE", -1);
-    p.interleave = il >= 0 ? il : (!p.simple_rows && wg_wide(p.Co, p.Ci));
-    const int xc = R3M_ENV_INT("R3M_WG_XCD", 1);
-    p.xcd = xc;
-    p.debug = R3M_ENV_INT("R3M_WG_DEBUG", 0);       // probe builds only (R3M_ENV_INT is the default in shipped builds)
-  }
-  const double flops = 2.0 * (double)p.M * (double)p.Co * (double)T * p.Ci;
-  if (wg_wide(p.Co, p.Ci)) {
-    p.tilesN = ceil_div(p.Ci, 128);
-    const int tiles = ceil_div(p.Co, 128) * p.tilesN * T;
-    prof_begin(KC_WGRAD_WIDE, flops, p.M, p.Co, p.Ci, T, s);
-    p.gx = tiles;
-#ifdef R3M_PROBES
-    if (!wg_use_glds()) hipLaunchKernelGGL((wgrad_kernel<128, 128>), dim3(tiles * splitK), dim3(256), 0, s, p);
-    else
-#endif
-    if (wg_rows(p.KW) && R3M_ENV_INT("R3M_WG_WIN", 1) && wgrad_rowwin_eligible(p)) {   // 3x3 "same" convolutions: shared input window (wgrad_win.hip)
-      if (int e = launch_wgrad_rowwin(p, splitK, s)) return e;
-    } else if (wg_rows(p.KW)) {   // 3-wide kernels: one block per kernel row (three taps), K steps of 16 rows
-      p.gx = ceil_div(p.Co, 128) * p.tilesN * p.KH;
-      hipLaunchKernelGGL((wgrad_glds_kernel<128, 128, 16, 3, 1>), dim3(p.gx * splitK), dim3(256), 0, s, p);
-    } else
-    {
-#ifdef R3M_PROBES
-      hipLaunchKernelGGL((wgrad_glds_kernel<128, 128>), dim3(tiles * splitK), dim3(256), 0, s, p);
-#else
-      // shipped builds: the two switches of the per-tap kernel are fixed per launch kind -> two compile-time variants
-      if (p.simple_rows) hipLaunchKernelGGL((wgrad_glds_kernel<128, 128, 32, 1, 0, 1>), dim3(tiles * splitK), dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((wgrad_glds_kernel<128, 128, 32, 1, 1, 0>), dim3(tiles * splitK), dim3(256), 0, s, p);
-#endif
-    }
-  } else {
-    p.tilesN = ceil_div(p.Ci, 64);
-    const int tiles = ceil_div(p.Co, 64) * p.tilesN * T;
-    prof_begin(KC_WGRAD_NARROW, flops, p.M, p.Co, p.Ci, T, s);
-    p.gx = tiles;
-#ifdef R3M_PROBES
-    if (!wg_use_glds()) hipLaunchKernelGGL((wgrad_kernel<64, 64>), dim3(tiles * splitK), dim3(256), 0, s, p);
-    else
-#endif
-    if (wg_rows(p.KW) && R3M_ENV_INT("R3M_WG_WIN", 1) && wgrad_rowwin_eligible(p)) {
-      if (int e = launch_wgrad_rowwin(p, splitK, s)) return e;
-    } else if (wg_rows(p.KW)) {
-      p.gx = ceil_div(p.Co, 64) * p.tilesN * p.KH;
-      hipLaunchKernelGGL((wgrad_glds_kernel<64, 64, 16, 3, 0>), dim3(p.gx * splitK), dim3(256), 0, s, p);
-    } else
-    {
-#ifdef R3M_PROBES
-      hipLaunchKernelGGL((wgrad_glds_kernel<64, 64>), dim3(tiles * splitK), dim3(256), 0, s, p);
-#else
-      if (p.simple_rows) hipLaunchKernelGGL((wgrad_glds_kernel<64, 64, 32, 1, 0, 1>), dim3(tiles * splitK), dim3(256), 0, s, p);
-      else hipLaunchKernelGGL((wgrad_glds_kernel<64, 64, 32, 1, 0, 0>), dim3(tiles * splitK), dim3(256), 0, s, p);
-#endif
-    }
-  }
-  prof_bytes(4.0 * ((double)p.M * p.Co + (double)p.N * p.Hi * p.Wi * p.Ci + (double)splitK * p.Co * T * p.Ci));
-  prof_end(s);
-  return check_launch("wgrad");
-}
-
-// dW[i] (+)= sum_s partial[s][i]   — fixed summation order: deterministic gradients
-// dW[i] (+)= sum over split-K slices of partial[s][i], fixed order (deterministic). A block is TX float4 columns x TY slice
-// groups (TX * TY = 256): group g adds slices g, g+TY, ...; the groups are combined through LDS in group order. Small weight
-// tensors (e.g. 64x64x9: 9216 float4, 284 slices) get TY = 16 so that the launch has hundreds of blocks and short load chains
-// instead of 36 blocks walking 284 slices one after the other (that was up to 1 ms per launch).
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ partial, float* __restrict__ dW,
-                                                            long long n4, long long n, int splitK, int accumulate, int tx_log2) {
-  __shared__ f32x4 red[256];
-  const int TX = 1 << tx_log2, TY = 256 >> tx_log2;
-  const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> tx_log2;
-  const long long i = (long long)blockIdx.x * TX + tx;
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (i < n4)
-    for (int sidx = ty; sidx < splitK; sidx += TY) v += ldg4(partial + sidx * n + i * 4);
-  if (TY == 1) {
-    if (i < n4) {
-      if (accumulate) v += *reinterpret_cast<const f32x4*>(dW + i * 4);
-      *reinterpret_cast<f32x4*>(dW + i * 4) = v;
-    }
-    return;
-  }
-  red[threadIdx.x] = v;
-  __syncthreads();
-  if (ty == 0 && i < n4) {
-    for (int g = 1; g < TY; ++g) v += red[(g << tx_log2) + tx];
-    if (accumulate) v += *reinterpret_cast<const f32x4*>(dW + i * 4);
-    *reinterpret_cast<f32x4*>(dW + i * 4) = v;
-  }
-}
-int launch_wgrad_reduce(const float* partial, float* dW, long long n, int splitK, int accumulate, hipStream_t s) {
-  R3M_REQUIRE(n % 4 == 0, "wgrad_reduce: n=%lld must be a multiple of 4", n);
-  const long long n4 = n / 4;
-  int tx_log2 = 8;                                     // TX = 256, TY = 1
-  while (tx_log2 > 4 && ceil_div(n4, 1 << tx_log2) < 1024 && (256 >> tx_log2) * 2 <= splitK) --tx_log2;   // more slice groups for small tensors
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(n4, 1 << tx_log2)), dim3(256), 0, s, partial, dW, n4, n, splitK, accumulate, tx_log2);
-  return check_launch("wgrad_reduce");
+  return wgrad_debug_occupancy(&out4[3]);
 }
 
 // Wt[ci][t][co] = W[co][t][ci]   (dgrad wants the contraction index co contiguous)

@@ -1,4 +1,4 @@
-// r3m_amd — device helpers shared by the convolution translation units (conv.hip: fp32, conv_bf16.hip: bf16 activations).
+// r3m_amd — device helpers shared by the convolution translation units (conv.hip, wgrad.hip, stem.hip and their kin: fp32, conv_bf16.hip: bf16 activations).
 #pragma once
 #include "common.h"
 #include <utility>

@@ -553,7 +553,7 @@ static int conv_bn(Ctx& c, const ConvSpec& L, const float* X) {
   return bn_forward_coeffs(c, L);
 }
 
-// x/255 -> Normalize -> conv1 7x7/2 straight from the NCHW frames (csrc/conv.hip stem_fwd_kernel) -> BatchNorm + ReLU + MaxPool
+// x/255 -> Normalize -> conv1 7x7/2 straight from the NCHW frames (csrc/stem.hip stem_fwd_kernel) -> BatchNorm + ReLU + MaxPool
 static int stem_forward(Ctx& c, const float* x_nchw, const FrameSource* crop) {
   const Plan& P = c.P;
   const int F = P.F, dt = c.dt;

@@ -1,5 +1,5 @@
 // r3m_amd — the stem (x/255 -> Normalize -> conv 7x7 stride 2 pad 3, 3 -> 64; /root/reference/r3m/models/models_r3m.py:97-99 into
-// torchvision's conv1) on the bf16 MFMA, used by bf16 plans: with the fp32 kernels of conv.hip the stem was 8 % of the bf16
+// torchvision's conv1) on the bf16 MFMA, used by bf16 plans: with the fp32 kernels of stem.hip the stem was 8 % of the bf16
 // step at 35-60 % of the (16x slower) fp32 matrix rate.
 //
 // Same geometry trick as the fp32 stem: for a fixed kernel row kh the 7 x 3 (kw, c) taps of an output pixel are 21 CONSECUTIVE
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void stem_prep16_kernel(const float* __restric
   *reinterpret_cast<bf16x8*>(xn16 + i * 8) = o;
 }
 
-// the same image built from the RAW clips through their crop boxes (see stem_prep_crop_kernel in conv.hip)
+// the same image built from the RAW clips through their crop boxes (see stem_prep_crop_kernel in stem.hip)
 template <typename T>
 __global__ __launch_bounds__(256) void stem_prep16_crop_kernel(const T* __restrict__ raw, const int* __restrict__ boxes,
                                                                 bf16_t* __restrict__ xn16, long long total, int Hi, int Wi, int fpb) {

@@ -1,21 +1,21 @@
 // r3m_amd — the stem for frames of any H x W in [32, 512]: x/255 -> Normalize -> conv1 7x7/2 pad 3 (3 -> 64), its weight gradient and
 // its input gradient. torchvision's ResNet takes any input size (every layer uses floor((H + 2p - k) / s) + 1); the reference feeds the
 // frames at their own size when obs_shape is the default (/root/reference/r3m/models/models_r3m.py:84-100). The 224 x 224 kernels
-// (conv.hip stem_*, stem_bf16.hip, stem_dgrad.hip) stay what 224 frames run; these general forms take every other size, and 224 too
+// (stem.hip, stem_bf16.hip, stem_dgrad.hip) stay what 224 frames run; these general forms take every other size, and 224 too
 // under r3m_debug_set_generic_stem (tests, A/B).
 //
 // Normalised image: xn[f][iy][ix * 3 + c], fp32 for fp32 plans and bf16 for bf16 plans (the bf16 stem's operand rounding: the normalised
 // value rounded once). Both precisions run the exact fp32 MFMA (v_mfma_f32_32x32x2_f32): with bf16 operands every product is exact in
 // fp32, so the bf16 path computes what a bf16 MFMA with fp32 accumulation computes, up to the order of the fp32 sums.
 //
-// Forward: the 224 kernel's geometry (conv.hip stem_fwd_kernel) with the row width and the tile's row span made general. A tile is 256
+// Forward: the 224 kernel's geometry (stem.hip stem_fwd_kernel) with the row width and the tile's row span made general. A tile is 256
 // consecutive output pixels of the flattened [F, Ho, Wo] index; it may span several output rows, and the end of one frame and the start
 // of the next (Ho * Wo >= 256 for H, W >= 32, so at most two frames). It stages, per frame part, the 2 r + 5 input rows its r output
 // rows touch, at a padded width of (W + 6) * 3 floats (9 leading zeros, zeros behind the data): the MFMA A operand of pixel (oy, ox)
 // for k = (kh, j) is patch[2 (oy - oy_first) + kh][6 ox + j] — a per-lane base plus an immediate, no vector work in the K loop.
 // Pixels past M read a valid pixel and their accumulators are cleared after the K loop (the BatchNorm partials then see zeros).
 //
-// Weight gradient: conv.hip stem_wgrad_kernel with one output row of Wo pixels per iteration (K = pixels, rounded up to even with zero
+// Weight gradient: stem.hip stem_wgrad_kernel with one output row of Wo pixels per iteration (K = pixels, rounded up to even with zero
 // dY), 7 staged input rows at a row stride == 22 (mod 32) as ST_PSW documents.
 //
 // Input gradient: stem_dgrad.hip's per-row GEMM (M = pixels of one dZ row, N = 21 (kw, c) columns, K = kernel rows x 64 channels)
@@ -33,7 +33,7 @@ namespace {
 constexpr int SG_KS = 155;             // LDS weight row stride (odd: conflict-free fragment reads), as ST_KS
 constexpr int SG_K = 154;              // 7 kernel rows x 22
 constexpr int SG_EPI = 4 * 32 * 68;    // floats the shared epilogue's slabs take (gg_epilogue<256, 64, 4, 1>)
-constexpr int SG_WG_BLOCKS = 512;      // weight-gradient blocks: the partial workspace is conv.hip's stem_wgrad_ws_floats()
+constexpr int SG_WG_BLOCKS = 512;      // weight-gradient blocks: the partial workspace is stem.hip's stem_wgrad_ws_floats()
 constexpr int SD_WH = 1056;            // input gradient: LDS floats per (kernel row, channel half), as stem_dgrad.hip
 constexpr int SD_WK = 2 * SD_WH;
 

@@ -5,7 +5,7 @@
 // Reference call site: the backward of torchvision's conv2 (Bottleneck) / conv1, conv2 (BasicBlock) reached from
 // /root/reference/r3m/trainer.py:146 (`full_loss.backward()`).
 //
-// The kernel-row form of wgrad_glds_kernel (conv.hip, NT = 3) stages the X rows of a K step once PER TAP — three tiles of 16 rows,
+// The kernel-row form of wgrad_glds_kernel (wgrad.hip, NT = 3) stages the X rows of a K step once PER TAP — three tiles of 16 rows,
 // each DMA instruction preceded by the scalar (frame, oy, ox) walk and padding tests of its rows and three vector instructions.
 // Probe builds (tools/gpu_wg_probe.sh, R3M_WG_DEBUG=2): that X staging is 11 % of the launch (15 % on the 64-wide tile). But for a
 // "same" convolution (Hi = Ho, Wi = Wo) the input pixel of GEMM row m and tap (kh, kw) is FLAT pixel m + (kh - 1) Wi + (kw - 1) of
@@ -248,7 +248,7 @@ bool wgrad_rowwin_eligible(const WgradParams& p) {
   return 40LL * p.Ci * 4 < 0x7FFFF000LL && 40LL * p.Co * 4 < 0x7FFFF000LL;
 }
 
-// p: rows_per_split, tilesN, xcd set by launch_wgrad (conv.hip); sets p.gx. One block per (co tile, ci tile, kernel row, split).
+// p: rows_per_split, tilesN, xcd set by launch_wgrad (wgrad.hip); sets p.gx. One block per (co tile, ci tile, kernel row, split).
 int launch_wgrad_rowwin(WgradParams& p, int splitK, hipStream_t s) {
   const bool wide = (p.Co % 128 == 0) && (p.Ci % 128 == 0);
   if (wide) {

@@ -19,7 +19,7 @@ from .optim import FusedAdam
 
 epsilon = 1e-8
 
-IMAGENET_MEAN = (0.485, 0.456, 0.406)   # models_r3m.py:61 — baked into the stem kernel (csrc/conv.hip)
+IMAGENET_MEAN = (0.485, 0.456, 0.406)   # models_r3m.py:61 — baked into the stem kernels (csrc/stem.hip)
 IMAGENET_STD = (0.229, 0.224, 0.225)
 
 

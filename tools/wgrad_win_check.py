@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Bitwise A/B of the fp32 3x3 weight gradient: shared-window kernel (wgrad_win.hip) against the kernel-row form (conv.hip).
+"""Bitwise A/B of the fp32 3x3 weight gradient: shared-window kernel (wgrad_win.hip) against the kernel-row form (wgrad.hip).
 Probe build only (R3M_WG_WIN switches the dispatch):  wgrad_win_check.py save out.pt  /  wgrad_win_check.py cmp a.pt b.pt"""
 import os
 import sys
