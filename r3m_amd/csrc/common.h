@@ -160,12 +160,19 @@ int launch_stem_fwd(const float* xn, const float* w147, void* y, float* stats, i
 size_t stem_wgrad_ws_floats();
 int launch_stem_wgrad(const float* xn, const void* dY, float* dw147, float* ws, int F, int accumulate, int dt, hipStream_t s);
 
-// ---- launchers (conv_bf16.hip) ----
+// ---- launchers (conv_bf16.hip): bf16 forward / input-gradient gather-GEMM, the bf16 weight images ----
 int launch_gather_gemm_bf16(const GatherGemmParams& p, hipStream_t s);
-int launch_wgrad_bf16(const WgradParams& p, int splitK, hipStream_t s);
-int wgrad_bf16_pick_split(int M, int Co, int Ci, int T);
+bool gg16_route_builds(int route, int flags);           // whether bf16 route `route` has a kernel for epilogue `flags`
+int gg16_route(const GatherGemmParams& p);              // kernel family of a bf16 launch (r3m_debug_conv_route): 30 gather, 31 halo, 32 kernel-row, 33 probe-build persistent kernel
 int launch_convert_bf16(const float* src, void* dst, long long n, hipStream_t s);
-// conv_pw16.hip: persistent warp-specialised kernel of the bf16 plans (dense / parity-strided output rows)
+int launch_transpose_w_bf16(const float* W, void* Wt, int Co, int T, int Ci, hipStream_t s);
+
+// ---- launchers (conv_row16.hip, round 6): persistent kernel-row kernel of the 128-multiple-wide / 64-wide bf16 3x3 / stride-1 launches ----
+bool row16_eligible(const GatherGemmParams& p);
+int launch_conv3x3_row_bf16(const GatherGemmParams& p, hipStream_t s);
+int row16_set_mode(int mode);                           // diagnostic (r3m_debug_set_conv3x3_bf16): 0 = per-tile halo kernels; returns the old value
+
+// ---- launchers (conv_pw16.hip): persistent warp-specialised kernel of the bf16 plans (dense / parity-strided output rows), probe builds ----
 #ifdef R3M_PROBES
 int pw16_form(const GatherGemmParams& p);               // 0 none, 1 pointwise, 2 gather, 3 gather with strided output rows
 int launch_pw16(const GatherGemmParams& p, hipStream_t s);
@@ -175,13 +182,10 @@ static inline int pw16_form(const GatherGemmParams&) { return 0; }
 static inline int launch_pw16(const GatherGemmParams&, hipStream_t) { return 1; }
 static inline int pw16_set_mode(int) { return -1; }
 #endif
-bool gg16_route_builds(int route, int flags);            // conv_bf16.hip: whether bf16 route `route` has a kernel for epilogue `flags`
-int gg16_route(const GatherGemmParams& p);              // conv_bf16.hip: kernel family of a bf16 launch (r3m_debug_conv_route): 30 gather, 31 halo, 32 kernel-row, 33 probe-build persistent kernel
-// conv_row16.hip (round 6): persistent kernel-row kernel of the 128-multiple-wide bf16 3x3 / stride-1 launches
-bool row16_eligible(const GatherGemmParams& p);
-int launch_conv3x3_row_bf16(const GatherGemmParams& p, hipStream_t s);
-int row16_set_mode(int mode);                           // diagnostic (r3m_debug_set_conv3x3_bf16): 0 = per-tile halo kernels; returns the old value
-int launch_transpose_w_bf16(const float* W, void* Wt, int Co, int T, int Ci, hipStream_t s);
+
+// ---- launchers (wgrad_bf16.hip): bf16 weight gradient (fp32 split-K partials) ----
+int launch_wgrad_bf16(const WgradParams& p, int splitK, hipStream_t s);
+int wgrad_bf16_pick_split(int M, int Co, int Ci, int T);
 
 // ---- launchers (stem_bf16.hip): the stem on the bf16 MFMA, from a padded bf16 image of the normalised frames ----
 size_t stem_xn16_bytes(int F);

@@ -27,9 +27,10 @@
 //             gather_gemm_glds_kernel             wide
 //             gather_gemm_kernel<256,64,4,1>      narrow (global -> VGPR -> LDS, 36-float padded rows)
 //             gather_gemm_kernel<128,128,2,2>     probe builds with R3M_GG_GLDS=0 (A/B of the register-staged predecessor)
-//   30-33   conv_bf16.hip             bf16 plans: handed to launch_gather_gemm_bf16 before any fp32 requirement
+//   30-33   conv_bf16.hip gg16_route  bf16 plans, handed to launch_gather_gemm_bf16 before any fp32 requirement: 30 gather_gemm_bf16_kernel,
+//                                     31 conv3x3_halo_bf16_kernel, 32 conv_row16.hip (kernel rows), 33 conv_pw16.hip (probe builds)
 // Also here: the dgrad weight transposes (transpose_w_kernel, transpose_w_all_kernel) and debug_occupancy.
-// The weight gradients are in wgrad.hip / wgrad_win.hip, the 224 x 224 stem in stem.hip.
+// The weight gradients are in wgrad.hip / wgrad_win.hip (bf16: wgrad_bf16.hip), the 224 x 224 stem in stem.hip.
 //
 // All staging is branch-free: taps that fall outside the image and rows past the end read a valid dummy address (a
 // zero line / a clamped pixel) instead of being skipped, so the loader is straight-line code the compiler can interleave
@@ -1023,7 +1024,7 @@ int launch_gather_gemm(const GatherGemmParams& p_in, hipStream_t s) {
   R3M_REQUIRE(p.M > 0 && p.Nc > 0, "gather_gemm: empty problem M=%d Nc=%d", p.M, p.Nc);
   gg_prepare(p);
   if (p.dtype == DT_BF16) {
-    if (t_route_out) return gg_route_record(gg16_route(p));    // 30 gather, 31 halo, 32 kernel-row (GG_ROUTE_BF16 + family)
+    if (t_route_out) return gg_route_record(gg16_route(p));    // 30 gather, 31 halo, 32 kernel-row, 33 probe-build persistent (GG_ROUTE_BF16 + family)
     return launch_gather_gemm_bf16(p, s);
   }
   R3M_REQUIRE(p.Ci % 32 == 0, "gather_gemm: Ci=%d must be a multiple of 32", p.Ci);

@@ -1,4 +1,4 @@
-// r3m_amd — device helpers shared by the convolution translation units (conv.hip, wgrad.hip, stem.hip and their kin: fp32, conv_bf16.hip: bf16 activations).
+// r3m_amd — device helpers shared by the convolution translation units (conv.hip, wgrad.hip, stem.hip and their kin: fp32; conv_bf16.hip, conv_row16.hip, wgrad_bf16.hip: bf16 activations).
 #pragma once
 #include "common.h"
 #include <utility>
@@ -69,6 +69,35 @@ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int
 template <int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// The epilogue flag combinations the bf16 forward / dgrad kernels are built for — THE list: the launchers of conv_bf16.hip (gather,
+// halo) and conv_row16.hip (kernel-row) instantiate their kernels through it, and the eligibility tests and gather_gemm_fuses_affine
+// answer from it (gg16_epilogue_built). Calls f(std::integral_constant<int, E>{}) for E == flags and returns what it returns (0 / an
+// error code > 0); -1 when no kernel is built for `flags`. EPI_AFFINE alone (an inference forward without ReLU) is built by the
+// gather kernel only: AFFINE_ALONE.
+template <bool AFFINE_ALONE, class F>
+static inline int gg16_epi_switch(int flags, F&& f) {
+  switch (flags) {
+#define GG16_EPI(E) case (E): return f(std::integral_constant<int, (E)>{})
+    GG16_EPI(0);
+    GG16_EPI(EPI_STATS);
+    GG16_EPI(EPI_ACCUM);
+    GG16_EPI(EPI_MASKED_ADD);
+    GG16_EPI(EPI_BNRED);
+    GG16_EPI(EPI_BNRED | EPI_MASKED_ADD);
+    GG16_EPI(EPI_AFFINE | EPI_RELU);
+    GG16_EPI(EPI_AFFINE | EPI_ACCUM | EPI_RELU);
+    case EPI_AFFINE:
+      if constexpr (AFFINE_ALONE) return f(std::integral_constant<int, EPI_AFFINE>{});
+      else return -1;
+#undef GG16_EPI
+    default: return -1;
+  }
+}
+static inline bool gg16_epilogue_built(int flags, bool affine_alone) {
+  const auto built = [](auto) { return 0; };
+  return (affine_alone ? gg16_epi_switch<true>(flags, built) : gg16_epi_switch<false>(flags, built)) == 0;
 }
 
 // Blocks are dispatched round-robin over the 8 XCDs (block b -> XCD b % 8, observed; speed only). Remap so that

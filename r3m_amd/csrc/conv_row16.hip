@@ -394,17 +394,9 @@ int row16_launch_one(const GatherGemmParams& p, hipStream_t s) {
 
 template <int BN>
 int row16_launch(const GatherGemmParams& p, hipStream_t s) {
-  switch (p.flags) {
-    case 0: return row16_launch_one<BN, 0>(p, s);
-    case EPI_STATS: return row16_launch_one<BN, EPI_STATS>(p, s);
-    case EPI_ACCUM: return row16_launch_one<BN, EPI_ACCUM>(p, s);
-    case EPI_MASKED_ADD: return row16_launch_one<BN, EPI_MASKED_ADD>(p, s);
-    case EPI_BNRED: return row16_launch_one<BN, EPI_BNRED>(p, s);
-    case EPI_BNRED | EPI_MASKED_ADD: return row16_launch_one<BN, EPI_BNRED | EPI_MASKED_ADD>(p, s);
-    case EPI_AFFINE | EPI_RELU: return row16_launch_one<BN, EPI_AFFINE | EPI_RELU>(p, s);                               // inference forward
-    case EPI_AFFINE | EPI_ACCUM | EPI_RELU: return row16_launch_one<BN, EPI_AFFINE | EPI_ACCUM | EPI_RELU>(p, s);
-    default: set_last_error("conv3x3_row(bf16): unsupported epilogue flag combination %d", p.flags); return 1;
-  }
+  const int rc = gg16_epi_switch<false>(p.flags, [&](auto e) { return row16_launch_one<BN, decltype(e)::value>(p, s); });
+  if (rc < 0) { set_last_error("conv3x3_row(bf16): unsupported epilogue flag combination %d", p.flags); return 1; }
+  return rc;
 }
 
 int g_row16_mode = 1;     // r3m_debug_set_conv3x3_bf16: 0 = the per-tile halo kernels everywhere
@@ -423,9 +415,7 @@ bool row16_eligible(const GatherGemmParams& p) {
   if (p.Hg != p.Hi || p.Wg != p.Wi || p.Ho != p.Hi || p.Wo != p.Wi || (p.Ci & 63)) return false;
   if (!((p.Nc & 127) == 0 || p.Nc == 64)) return false;
   if (ceil_div((R_BM + 2 * p.Wi + 2) * 5, 64) * 1024 > ((p.Nc & 127) == 0 ? RowCfg<128>::ZOFF : RowCfg<64>::ZOFF)) return false;
-  if (p.flags != 0 && p.flags != EPI_STATS && p.flags != EPI_ACCUM && p.flags != EPI_MASKED_ADD && p.flags != EPI_BNRED &&
-      p.flags != (EPI_BNRED | EPI_MASKED_ADD) && p.flags != (EPI_AFFINE | EPI_RELU) && p.flags != (EPI_AFFINE | EPI_ACCUM | EPI_RELU))
-    return false;
+  if (!gg16_epilogue_built(p.flags, false)) return false;
   if ((long long)p.Nc * p.T * p.Ci * 2 >= (long long)BUF_OOB) return false;
   for (int k = 0; k < 9; ++k)
     if (p.dy[k] < -1 || p.dy[k] > 1 || p.dx[k] < -1 || p.dx[k] > 1) return false;

@@ -119,7 +119,7 @@ HW_BF16_GROUPS = {
     "real_maps": [c for c in HW_CONV_GROUPS["real_maps"] if c[3] % 64 == 0 and c[4] % 64 == 0],
     "extremes": [c for c in HW_CONV_GROUPS["extremes"] if c[3] % 64 == 0 and c[4] % 64 == 0],
     "mixed_dgrad": HW_CONV_GROUPS["mixed_dgrad"][:4],
-    # conv_bf16.hip all-taps weight gradient: (Wi & 7) == 0 && Wi >= 8 && Hi >= 4 -- Wi in {8, 16, 24} x Hi in {3, 4, 5}, and transposed
+    # wgrad_bf16.hip all-taps weight gradient: (Wi & 7) == 0 && Wi >= 8 && Hi >= 4 -- Wi in {8, 16, 24} x Hi in {3, 4, 5}, and transposed
     "wgrad_all_taps": [(2, h, w, 64, 128, 3, 1, 1) for w in (8, 16, 24) for h in (3, 4, 5)] +
                       [(2, w, h, 64, 128, 3, 1, 1) for w in (8, 16, 24) for h in (3, 4, 5)],
     # kernel-row weight gradient (128-wide): the FAST K-step path needs 32 / Wo + 1 <= Ho, i.e. Ho Wo > 32 -- symmetric in the two extents,
