@@ -139,13 +139,28 @@ int r3m_resnet_backward(r3m_resnet_t h, const float* dh, const float* params, fl
 /* r3m_resnet_backward with two optional outputs (r3m_resnet_backward(...) == r3m_resnet_backward_ex(..., grads, ..., NULL, 0, stream)):
  *   grads == NULL : no parameter gradient is written and no weight-gradient launch is enqueued (frozen encoder); the BatchNorm
  *                   backward sums that dz still needs go to plan scratch (reserved in the arena at create time)
- *   dx != NULL    : (only in the call that runs stage 3) d/d(frames) [frames,3,224,224] fp32 NCHW of the frames given to
- *                   r3m_resnet_forward, written (dx_accumulate = 0) or added to dx. Not available after r3m_resnet_forward_crop or an
- *                   inference-mode (training = 2) forward: returns non-zero.
+ *   dx != NULL    : d/d(frames) [frames,3,224,224] fp32 NCHW of the frames given to r3m_resnet_forward, written (dx_accumulate = 0)
+ *                   or added to dx by the call that runs stage 3. Not available after r3m_resnet_forward_crop or an
+ *                   inference-mode (training = 2) forward: returns non-zero. With frozen tensors (r3m_resnet_set_trainable) the
+ *                   call that runs stage 0 plans the whole backward, so it must be given dx too (any call may carry it; only stage 3
+ *                   writes it); with grads == NULL stage 0 assumes dx is wanted. A stage-3 call with a dx the plan of stage 0 did
+ *                   not provide for (the gradient chain stopped above the stem) returns non-zero.
  * What autograd computes for obs.grad through the reference's R3M.forward (models_r3m.py:84-100): the encoder as a frozen,
  * differentiable reward or perceptual loss. */
 int r3m_resnet_backward_ex(r3m_resnet_t h, const float* dh, const float* params, float* grads, void* arena, int stage_begin,
                            int stage_end, int accumulate, float* dx, int dx_accumulate, r3m_stream_t stream);
+/* Partial-freeze fine-tuning (requires_grad_(False) on a sub-tree of the reference's autograd graph, models_r3m.py:44-52,99): mask is
+ * a HOST array of n = r3m_resnet_num_tensors(h) bytes in r3m_resnet_tensor_info order, non-zero = the tensor wants a gradient (entries
+ * of kinds 3 and 4 are ignored); NULL restores "all trainable", the default. The backward then enqueues only what the trainable
+ * tensors (and dx) need: frozen weights get no weight-gradient launch and their range of grads is not written, frozen BatchNorm
+ * parameter sums go to plan scratch, and everything below the lowest trainable tensor is skipped (a stage without work enqueues
+ * nothing and returns 0). An all-zero mask behaves like grads == NULL. Host-only; takes effect at the next backward that begins with
+ * stage 0; between the stages of a running backward it returns non-zero. */
+int r3m_resnet_set_trainable(r3m_resnet_t h, const unsigned char* mask, int n);
+/* Diagnostic, runs without a GPU: the work a backward under the current mask does per convolution (r3m_resnet_conv_info order), from
+ * the predicate the backward itself executes. flags_out[i]: 1 = BatchNorm parameter sums (first pass), 2 = BatchNorm apply (dY is
+ * formed), 4 = dgrad, 8 = wgrad. want_dx: the input gradient is asked for. Returns the number of convolutions, -1 on error. */
+int r3m_debug_backward_plan(r3m_resnet_t h, int want_dx, int* flags_out, int cap);
 
 /* ---------------- single operators (parity-tested one by one) -------------------------------------------------
  * conv2d fwd / dgrad / wgrad: ATen conv2d + autograd under torchvision ResNet.forward (call site models_r3m.py:99). */
@@ -420,6 +435,18 @@ int r3m_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
  * (models_r3m.py:76); BASELINE.json's north_star names "the SGD/Adam step". */
 int r3m_sgd_step(float* params, const float* grads, float* momentum_buf, long long n, double lr, double momentum, double dampening,
                  double weight_decay, int nesterov, long long step, float grad_scale, r3m_stream_t stream);
+/* The same steps over n_ranges disjoint ranges [off[i], off[i] + count[i]) of the flat buffers, sorted by offset, each with its own
+ * step count (torch keeps `step` per parameter: a tensor frozen for some steps gets the bias correction of the steps it took).
+ * off / count / step are HOST arrays; offsets and counts are multiples of 4. One launch per 64 ranges (the range table travels in the
+ * kernel arguments: nothing is allocated or uploaded); n_ranges == 0 launches nothing. Elements inside a range get bit for bit what
+ * r3m_adam_step / r3m_sgd_step on that slice with that step gives them; elements outside are not touched. Misaligned, unsorted or
+ * overlapping ranges and step < 1 return non-zero before anything is launched. */
+int r3m_adam_step_ranges(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const long long* off,
+                         const long long* count, const long long* step, int n_ranges, double lr, double beta1, double beta2, double eps,
+                         float grad_scale, r3m_stream_t stream);
+int r3m_sgd_step_ranges(float* params, const float* grads, float* momentum_buf, const long long* off, const long long* count,
+                        const long long* step, int n_ranges, double lr, double momentum, double dampening, double weight_decay,
+                        int nesterov, float grad_scale, r3m_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,8 @@ SIGNATURES = {
     "r3m_resnet_create_hw": (C.c_void_p, [c_i, c_i, c_i, c_i, c_i]),
     "r3m_resnet_input_hw": (c_i, [C.c_void_p, C.POINTER(c_i), C.POINTER(c_i)]),
     "r3m_resnet_num_convs": (c_i, [C.c_void_p]),
+    "r3m_resnet_set_trainable": (c_i, [C.c_void_p, C.c_char_p, c_i]),
+    "r3m_debug_backward_plan": (c_i, [C.c_void_p, c_i, C.POINTER(c_i), c_i]),
     "r3m_resnet_conv_info": (c_i, [C.c_void_p, c_i] + [C.POINTER(c_i)] * 9),
     "r3m_debug_set_generic_stem": (c_i, [c_i]),
     "r3m_stem_gen_image_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
@@ -134,6 +136,8 @@ SIGNATURES = {
     "r3m_loss_finalize": (c_i, [c_f, c_sz, c_i, c_i, c_f, c_fl, c_fl, c_fl, c_fl, c_f]),
     "r3m_adam_step": (c_i, [c_f, c_f, c_f, c_f, c_ll, c_d, c_d, c_d, c_d, c_ll, c_fl, c_f]),
     "r3m_sgd_step": (c_i, [c_f, c_f, c_f, c_ll, c_d, c_d, c_d, c_d, c_i, c_ll, c_fl, c_f]),
+    "r3m_adam_step_ranges": (c_i, [c_f, c_f, c_f, c_f] + [C.POINTER(c_ll)] * 3 + [c_i, c_d, c_d, c_d, c_d, c_fl, c_f]),
+    "r3m_sgd_step_ranges": (c_i, [c_f, c_f, c_f] + [C.POINTER(c_ll)] * 3 + [c_i, c_d, c_d, c_d, c_d, c_i, c_fl, c_f]),
 }
 
 

@@ -266,6 +266,14 @@ int r3m_resnet_backward_ex(r3m_resnet_t h, const float* dh, const float* params,
   return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, S(stream), dx,
                        dx_accumulate);
 }
+int r3m_resnet_set_trainable(r3m_resnet_t h, const unsigned char* mask, int n) {
+  R3M_REQUIRE(h, "resnet_set_trainable: null handle");
+  return plan_set_trainable(PLAN(h), mask, n);
+}
+int r3m_debug_backward_plan(r3m_resnet_t h, int want_dx, int* flags_out, int cap) {
+  if (!h || !flags_out) { set_last_error("debug_backward_plan: null argument"); return -1; }
+  return plan_debug_backward(PLAN(h), want_dx, flags_out, cap);
+}
 
 int r3m_conv2d_stats_rows(int N, int Hi, int Wi, int Co, int k, int stride, int pad) {
   return gather_gemm_grid_m(ConvGeom{N, Hi, Wi, 0, Co, k, stride, pad}.M(), Co);
@@ -689,6 +697,18 @@ int r3m_sgd_step(float* p, const float* g, float* momentum_buf, long long n, dou
                  double weight_decay, int nesterov, long long step, float grad_scale, r3m_stream_t stream) {
   R3M_REQUIRE(p && g, "sgd_step: null argument");
   return launch_sgd(p, g, momentum_buf, n, lr, momentum, dampening, weight_decay, nesterov, step, grad_scale, S(stream));
+}
+
+int r3m_adam_step_ranges(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
+                         int n_ranges, double lr, double b1, double b2, double eps, float grad_scale, r3m_stream_t stream) {
+  return launch_adam_ranges(p, g, m, v, off, count, step, n_ranges, lr, b1, b2, eps, grad_scale, S(stream));
+}
+
+int r3m_sgd_step_ranges(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
+                        int n_ranges, double lr, double momentum, double dampening, double weight_decay, int nesterov, float grad_scale,
+                        r3m_stream_t stream) {
+  return launch_sgd_ranges(p, g, momentum_buf, off, count, step, n_ranges, lr, momentum, dampening, weight_decay, nesterov, grad_scale,
+                           S(stream));
 }
 
 }  // extern "C"

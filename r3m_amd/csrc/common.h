@@ -263,6 +263,12 @@ int launch_adam(float* p, const float* g, float* m, float* v, long long n, doubl
                 long long step, float grad_scale, hipStream_t s);
 int launch_sgd(float* p, const float* g, float* momentum_buf, long long n, double lr, double momentum, double dampening,
                double weight_decay, int nesterov, long long step, float grad_scale, hipStream_t s);
+// the same steps over disjoint, sorted [off, off + count) ranges of the flat buffers with a step count each (host arrays)
+int launch_adam_ranges(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
+                       int n_ranges, double lr, double beta1, double beta2, double eps, float grad_scale, hipStream_t s);
+int launch_sgd_ranges(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
+                      int n_ranges, double lr, double momentum, double dampening, double weight_decay, int nesterov, float grad_scale,
+                      hipStream_t s);
 
 // ---- augmentation (augment.hip) ----
 int launch_crop_resize(const void* in, int in_is_u8, const int* boxes, float* out, long long N, int C, int Hi, int Wi, int Ho,

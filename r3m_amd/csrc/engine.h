@@ -69,6 +69,11 @@ long long plan_arena_floats(Plan* P);
 int plan_num_tensors(Plan* P);
 int plan_tensor_info(Plan* P, int i, char* name, int cap, int* kind, long long* offset, int* ndim, int* shape4);
 int plan_stage_range(Plan* P, int stage, long long* off, long long* count);
+// partial freeze: one byte per tensor (plan_tensor_info order; nullptr = all trainable), and the per-convolution work of a backward
+// under it (BW_* bits) from the predicate plan_backward executes
+enum { BW_BN_SUMS = 1, BW_BN_APPLY = 2, BW_DGRAD = 4, BW_WGRAD = 8 };
+int plan_set_trainable(Plan* P, const unsigned char* mask, int n);
+int plan_debug_backward(Plan* P, int want_dx, int* flags_out, int cap);
 // per-plan options; each returns the old value
 int plan_set_bn_pair(Plan* P, int on);      // the two tail BatchNorms of a downsample block share their backward passes
 int plan_set_fuse_bnred(Plan* P, int on);   // 1 = BatchNorm-backward partials from the dgrad epilogues (EPI_BNRED), 0 = stand-alone reduce passes

@@ -102,6 +102,8 @@ struct RunState {
   int a_next = 0;           // which of A0/A1 the next dY goes to
   int dout_fused_rows = 0;  // > 0: the dgrad that wrote the running output gradient also wrote the BatchNorm-backward partials of the
                             // block that consumes it next (EPI_BNRED): that many partial rows wait in the partial buffer
+  std::vector<int> work;    // BW_* bits per convolution of the running backward (backward_work, fixed by the call that ran stage 0)
+  std::vector<unsigned char> mask;   // the trainable mask that backward runs under (one byte per tensor; empty: all trainable)
   WtEntry* d_wt_tab = nullptr;      // device copies of wt_tab / wt_tile0, made at the first backward (plan creation needs no GPU)
   int* d_wt_tile0 = nullptr;
   SideStream side;
@@ -135,6 +137,7 @@ struct Plan {
   long long wt_elems = 0;
   // options (plan_set_*)
   int fuse_bnred = 1;       // BatchNorm-backward partials from the producing dgrad's epilogue (EPI_BNRED); 0: stand-alone reduce pass
+  std::vector<unsigned char> trainable;   // plan_set_trainable: one byte per tensor, empty = all trainable (read by the next stage 0)
   int bn_pair = R3M_BN_PAIR_DEFAULT;   // the two tail BatchNorms of a downsample block share their backward passes (bn_backward_pair); 0: separate passes
   RunState run;
 };
@@ -477,6 +480,9 @@ size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt) { return (size_t)wgrad_sp
     if (int e_ = (x)) return e_; \
   } while (0)
 
+// add_conv pushes five tensors per convolution: weight, BatchNorm weight, bias, running_mean, running_var
+static size_t tensor_of(const Plan& P, const ConvSpec& L) { return 5 * (size_t)(&L - P.convs.data()); }
+
 // one forward or backward call: the plan's layout (read-only), its run state, and the caller's buffers
 struct Ctx {
   const Plan& P;
@@ -491,9 +497,12 @@ struct Ctx {
   int dt;
   // where BatchNorm backward puts d gamma / d beta of layer L: the flat gradient buffer, or plan scratch when no parameter gradient
   // is wanted (the sums themselves are still formed: train-mode dz needs c1 / c2 from the same pass)
-  float* dgamma(const ConvSpec& L) const { return grads ? grads + L.gamma_off : arena + P.gsc_off; }
-  float* dbeta(const ConvSpec& L) const { return grads ? grads + L.beta_off : arena + P.gsc_off + 2048; }
-  int bn_accumulate() const { return grads ? accumulate : 0; }
+  // (a frozen gamma / beta counts as unwanted: its range of the gradient buffer is never written)
+  bool wanted(const ConvSpec& L, int which) const { return grads && (R.mask.empty() || R.mask[tensor_of(P, L) + which]); }
+  float* dgamma(const ConvSpec& L) const { return wanted(L, 1) ? grads + L.gamma_off : arena + P.gsc_off; }
+  float* dbeta(const ConvSpec& L) const { return wanted(L, 2) ? grads + L.beta_off : arena + P.gsc_off + 2048; }
+  int bn_accumulate(const ConvSpec& L) const { return wanted(L, 1) || wanted(L, 2) ? accumulate : 0; }
+  int work(const ConvSpec& L) const { return R.work[&L - P.convs.data()]; }
   float* partial() const { return arena + P.partial_off; }
   double* acc() const { return reinterpret_cast<double*>(arena + P.acc_off); }
   float* coef(const ConvSpec& L, int which) const { return arena + L.coef_off + (long long)which * L.Co; }
@@ -683,7 +692,7 @@ int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const fl
 static int bn_backward_combine(Ctx& c, const ConvSpec& L, const float* partial, int prow, bool from_dgrad = false) {
   TRY(launch_bn_stats_reduce(partial, prow, L.Co, c.acc(), c.s));
   return launch_bn_bwd_finalize_rows(c.acc(), prow, (long long)c.P.F * L.Ho * L.Wo, c.R.last_training, c.dgamma(L), c.dbeta(L), c.coef(L, 4),
-                                     c.coef(L, 5), c.bn_accumulate(), L.Co, c.s, from_dgrad ? c.coef(L, 1) : nullptr);
+                                     c.coef(L, 5), c.bn_accumulate(L), L.Co, c.s, from_dgrad ? c.coef(L, 1) : nullptr);
 }
 // BatchNorm(+ReLU / residual mask) backward of layer L: dZ -> dY, parameter gradients into the flat gradient buffer
 // fused_rows > 0: the dgrad that produced dZ already wrote this BatchNorm's backward partials (EPI_BNRED) into the partial buffer:
@@ -695,8 +704,10 @@ static int bn_backward_sums(Ctx& c, const ConvSpec& L, const float* dZ, const un
                            L.Co, c.dt, c.s));
   return bn_backward_combine(c, L, c.partial(), bn_bwd_partial_rows(rows, L.Co, c.dt));
 }
-static int bn_backward(Ctx& c, const ConvSpec& L, const float* dZ, const unsigned* Zbits, float* dY, int fused_rows = 0) {
-  TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
+// work: BW_BN_SUMS / BW_BN_APPLY of this layer (a BatchNorm whose dY nobody reads only forms its parameter sums)
+static int bn_backward(Ctx& c, const ConvSpec& L, const float* dZ, const unsigned* Zbits, float* dY, int fused_rows, int work) {
+  if (work & BW_BN_SUMS) TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
+  if (!(work & BW_BN_APPLY)) return 0;
   const long long rows = (long long)c.P.F * L.Ho * L.Wo;
   return launch_bn_bwd_apply(dZ, nullptr, Zbits, c.arena + L.Y_off, c.coef(L, 2), c.coef(L, 3), c.coef(L, 0), c.coef(L, 1), c.coef(L, 4),
                              c.coef(L, 5), dY, rows, L.Co, c.dt, c.s);
@@ -704,8 +715,11 @@ static int bn_backward(Ctx& c, const ConvSpec& L, const float* dZ, const unsigne
 // The two BatchNorms that feed a downsample block's add + ReLU (its last convolution's and the downsample convolution's) see the SAME
 // masked output gradient: their second passes run as ONE launch that reads dOut and the mask bits once (bn.hip, bn_bwd_apply2).
 // The sums of the two are taken one after the other (they share the partial / accumulator scratch).
+// work / work_d: the BW_* bits of L / Ld. The joint launches run as long as either side needs them, so that the side that is wanted
+// sees the kernels and inputs of a full backward (bit-identical gradients); only the other side's combine is dropped, and its dY
+// (formed from stale c1 / c2) is never read.
 static int bn_backward_pair(Ctx& c, const ConvSpec& L, const ConvSpec& Ld, const float* dZ, const unsigned* Zbits, float* dY, float* dYd,
-                            int fused_rows) {
+                            int fused_rows, int work, int work_d) {
   R3M_REQUIRE(L.Co == Ld.Co && L.Ho == Ld.Ho && L.Wo == Ld.Wo && Zbits, "bn_backward_pair: the two BatchNorms must have one shape and mask bits");
   const long long rows = (long long)c.P.F * L.Ho * L.Wo;
   if (!fused_rows && bn_bwd_reduce2_available(L.Co, c.dt)) {
@@ -714,12 +728,13 @@ static int bn_backward_pair(Ctx& c, const ConvSpec& L, const ConvSpec& Ld, const
     const long long set = (long long)prow * 2 * L.Co;
     TRY(launch_bn_bwd_reduce2(dZ, Zbits, c.arena + L.Y_off, c.arena + L.coef_off, c.arena + Ld.Y_off, c.arena + Ld.coef_off, c.partial(), set,
                               rows, L.Co, c.dt, c.s));
-    TRY(bn_backward_combine(c, L, c.partial(), prow));
-    TRY(bn_backward_combine(c, Ld, c.partial() + set, prow));
+    if (work & BW_BN_SUMS) TRY(bn_backward_combine(c, L, c.partial(), prow));
+    if (work_d & BW_BN_SUMS) TRY(bn_backward_combine(c, Ld, c.partial() + set, prow));
   } else {
-    TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
-    TRY(bn_backward_sums(c, Ld, dZ, Zbits, 0));
+    if (work & BW_BN_SUMS) TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
+    if (work_d & BW_BN_SUMS) TRY(bn_backward_sums(c, Ld, dZ, Zbits, 0));
   }
+  if (!((work | work_d) & BW_BN_APPLY)) return 0;
   return launch_bn_bwd_apply2(dZ, Zbits, c.arena + L.Y_off, c.arena + L.coef_off, dY, c.arena + Ld.Y_off, c.arena + Ld.coef_off, dYd, rows,
                               L.Co, c.dt, c.s);
 }
@@ -855,49 +870,66 @@ static int block_backward(Ctx& c, int bi) {
   const BlockSpec* Bprev = bi > 0 ? &P.blocks[bi - 1] : nullptr;
   const ConvSpec* Lprev_last = Bprev ? &P.convs[Bprev->conv[Bprev->nconv - 1]] : nullptr;
   const unsigned* prev_bits = Bprev ? reinterpret_cast<const unsigned*>(arena + Bprev->mask_off) : nullptr;
-  int ai;
+  int ai = 0;
   // downsample block: both tail BatchNorms in one second pass, the downsample one's dY parked in E until the end of the block
   // (R3M_BN_PAIR=0 in probe builds: two separate passes, for A/B)
   const bool pair = B.ds >= 0 && P.E_off >= 0 && B.nconv >= 2 && P.bn_pair && R3M_ENV_INT("R3M_BN_PAIR", 1) != 0 && P.convs[B.ds].Co >= 8;
   float* const dYd_pair = pair ? arena + P.E_off : nullptr;
+  // Every step below runs iff its BW_* bit is set (backward_work). The bits are monotone along the main path — a convolution without
+  // work has none below it in the block — so a launch that is kept always finds its input written by a launch that was kept too.
+  const int wd = B.ds >= 0 ? c.work(P.convs[B.ds]) : 0;
+  float* dY = nullptr;
   for (int j = B.nconv - 1; j >= 1; --j) {
     const ConvSpec& L = P.convs[B.conv[j]];
     const ConvSpec& Lprev = P.convs[B.conv[j - 1]];
-    float* dY = c.next_A(&ai);
-    TRY(side.acquire(ai));
-    if (pair && j == B.nconv - 1) TRY(bn_backward_pair(c, L, P.convs[B.ds], dz, zmask, dY, dYd_pair, dz_fused));
-    else TRY(bn_backward(c, L, dz, zmask, dY, dz_fused));     // HBM-bound: overlaps the previous layer's wgrad
-    TRY(side.wait_wgrads());
-    TRY(dgrad(c, L, dY, Gb, 0, nullptr, nullptr, &Lprev, nullptr, &dz_fused));   // Gb = dz of Lprev's BatchNorm + its partials
-    TRY(side.wgrad_async(c, L, arena + Lprev.Z_off, dY, ai));
+    const int w = c.work(L);
+    const bool tail_pair = pair && j == B.nconv - 1;
+    if ((w | (tail_pair ? wd : 0)) & BW_BN_SUMS) {
+      dY = c.next_A(&ai);
+      TRY(side.acquire(ai));
+      if (tail_pair) TRY(bn_backward_pair(c, L, P.convs[B.ds], dz, zmask, dY, dYd_pair, dz_fused, w, wd));
+      else TRY(bn_backward(c, L, dz, zmask, dY, dz_fused, w));     // HBM-bound: overlaps the previous layer's wgrad
+    }
+    dz_fused = 0;
+    if (w & BW_DGRAD) {
+      TRY(side.wait_wgrads());
+      TRY(dgrad(c, L, dY, Gb, 0, nullptr, nullptr, &Lprev, nullptr, &dz_fused));   // Gb = dz of Lprev's BatchNorm + its partials
+    }
+    if (w & BW_WGRAD) TRY(side.wgrad_async(c, L, arena + Lprev.Z_off, dY, ai));
     dz = Gb; zmask = nullptr;   // Gb is consumed by the next bn_backward before a later dgrad rewrites it
   }
   const ConvSpec& L1 = P.convs[B.conv[0]];
-  float* dY1 = c.next_A(&ai);
-  TRY(side.acquire(ai));
-  TRY(bn_backward(c, L1, dz, zmask, dY1, dz_fused));
-  TRY(side.wait_wgrads());
+  const int w1 = c.work(L1);
+  float* dY1 = nullptr;
+  if (w1 & BW_BN_SUMS) {
+    dY1 = c.next_A(&ai);
+    TRY(side.acquire(ai));
+    TRY(bn_backward(c, L1, dz, zmask, dY1, dz_fused, w1));
+  }
+  if (w1 & BW_DGRAD) TRY(side.wait_wgrads());
   if (B.ds >= 0) {
     const ConvSpec& Ld = P.convs[B.ds];
-    TRY(dgrad(c, L1, dY1, Gc, 0, nullptr, nullptr));
-    TRY(side.wgrad_async(c, L1, Xin, dY1, ai));
+    if (w1 & BW_DGRAD) TRY(dgrad(c, L1, dY1, Gc, 0, nullptr, nullptr));      // (DGRAD(conv1) == DGRAD(downsample): Gc is written before it is added to)
+    if (w1 & BW_WGRAD) TRY(side.wgrad_async(c, L1, Xin, dY1, ai));
     if (pair) {                                     // dY of the downsample BatchNorm has been waiting in E since the block's first pass
-      TRY(dgrad(c, Ld, dYd_pair, Gc, EPI_ACCUM, nullptr, nullptr));
-      TRY(side.wgrad_async(c, Ld, Xin, dYd_pair, ai));      // (side stream: ordered behind conv1's wgrad, same event slot)
-    } else {
+      if (wd & BW_DGRAD) TRY(dgrad(c, Ld, dYd_pair, Gc, EPI_ACCUM, nullptr, nullptr));
+      if (wd & BW_WGRAD) TRY(side.wgrad_async(c, Ld, Xin, dYd_pair, ai));      // (side stream: ordered behind conv1's wgrad, same event slot)
+    } else if (wd) {
       int ad;
       float* dYd = c.next_A(&ad);
       TRY(side.acquire(ad));
-      TRY(bn_backward(c, Ld, dOut, Out, dYd));        // overlaps wgrad(conv1); always the stand-alone reduce (second consumer of dOut)
-      TRY(side.wait_wgrads());
-      TRY(dgrad(c, Ld, dYd, Gc, EPI_ACCUM, nullptr, nullptr));
-      TRY(side.wgrad_async(c, Ld, Xin, dYd, ad));
+      TRY(bn_backward(c, Ld, dOut, Out, dYd, 0, wd));   // overlaps wgrad(conv1); always the stand-alone reduce (second consumer of dOut)
+      if (wd & BW_DGRAD) {
+        TRY(side.wait_wgrads());
+        TRY(dgrad(c, Ld, dYd, Gc, EPI_ACCUM, nullptr, nullptr));
+      }
+      if (wd & BW_WGRAD) TRY(side.wgrad_async(c, Ld, Xin, dYd, ad));
     }
   } else {
     // Gc = dgrad + masked residual gradient = the previous block's COMPLETE output gradient: also emit the partials of the
     // BatchNorm that will consume it (the previous block's last one, masked by that block's output bits)
-    TRY(dgrad(c, L1, dY1, Gc, EPI_MASKED_ADD, dOut, Out, Lprev_last, prev_bits, &c.R.dout_fused_rows));
-    TRY(side.wgrad_async(c, L1, Xin, dY1, ai));
+    if (w1 & BW_DGRAD) TRY(dgrad(c, L1, dY1, Gc, EPI_MASKED_ADD, dOut, Out, Lprev_last, prev_bits, &c.R.dout_fused_rows));
+    if (w1 & BW_WGRAD) TRY(side.wgrad_async(c, L1, Xin, dY1, ai));
   }
   // C becomes the gradient of the previous block's output; the old D is free (only the main stream ever read it)
   std::swap(c.R.roles[0], c.R.roles[4]);
@@ -905,7 +937,8 @@ static int block_backward(Ctx& c, int bi) {
 }
 
 // stem: maxpool + BN/ReLU backward (fused) -> conv1 weight gradient [-> input gradient]
-static int stem_backward(Ctx& c, float* dx, int dx_accumulate) {
+// work: the stem's BW_* bits (BW_DGRAD = the input gradient)
+static int stem_backward(Ctx& c, float* dx, int dx_accumulate, int work) {
   const Plan& P = c.P;
   const int F = P.F, dt = c.dt;
   const ConvSpec& L0 = P.convs[0];
@@ -913,25 +946,62 @@ static int stem_backward(Ctx& c, float* dx, int dx_accumulate) {
   const float* Y = c.arena + L0.Y_off;
   // MaxPool backward gathered inside both BatchNorm-backward passes (no dZ0 tensor)
   const unsigned char* am = reinterpret_cast<const unsigned char*>(c.arena + P.amax_off);
-  TRY(launch_bn_bwd_reduce_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.partial(), F, P.H1, P.W1, 64, dt,
-                                c.s));
-  TRY(bn_backward_combine(c, L0, c.partial(), bn_bwd_pool_partial_rows(F, P.H1, P.W1, 64)));
-  TRY(launch_bn_bwd_apply_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.coef(L0, 4), c.coef(L0, 5), Gc, F,
-                               P.H1, P.W1, 64, dt, c.s));
+  if (work & BW_BN_SUMS) {
+    TRY(launch_bn_bwd_reduce_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.partial(), F, P.H1, P.W1, 64, dt,
+                                  c.s));
+    TRY(bn_backward_combine(c, L0, c.partial(), bn_bwd_pool_partial_rows(F, P.H1, P.W1, 64)));
+  }
+  if (work & BW_BN_APPLY)
+    TRY(launch_bn_bwd_apply_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.coef(L0, 4), c.coef(L0, 5), Gc, F,
+                                 P.H1, P.W1, 64, dt, c.s));
   TRY(c.R.side.join());   // the stem wgrad shares the split-K scratch with the side stream's wgrads
   const float* xn = c.arena + P.col_off;
   float* ws = c.arena + P.wgp_off;
-  if (c.grads) {
+  if (work & BW_WGRAD) {
     if (c.R.stem_gen) TRY(launch_stem_wgrad_gen(xn, Gc, c.grads + L0.w_off, ws, F, P.H, P.W, c.accumulate, dt, c.s));
     else if (dt == DT_BF16) TRY(launch_stem_wgrad16(xn, Gc, c.grads + L0.w_off, ws, F, c.accumulate, c.s));
     else TRY(launch_stem_wgrad(xn, Gc, c.grads + L0.w_off, ws, F, c.accumulate, dt, c.s));
   }
   // Gc = conv1's output gradient; the bf16 rounding of the normalised frames is taken as identity (as autocast does)
-  if (dx) {
+  if (work & BW_DGRAD) {
     if (c.R.stem_gen) TRY(launch_stem_input_grad_gen(Gc, dt, c.params + L0.w_off, dx, F, P.H, P.W, dx_accumulate, c.s));
     else TRY(launch_stem_input_grad(Gc, dt, c.params + L0.w_off, dx, F, dx_accumulate, c.s));
   }
   return 0;
+}
+
+// THE predicate of a partial backward: which work each convolution's backward does, given which tensors want a gradient (mask: one
+// byte per tensor in plan_tensor_info order, nullptr = all) and whether the input gradient is wanted. plan_backward executes these
+// bits and consults nothing else; plan_debug_backward reports them. With T(L) = L's weight is trainable and Tg(L) = gamma or beta of
+// L's BatchNorm is (the stem counts as "below block 0"):
+//   below(block)   = dx wanted, or any trainable tensor in an earlier block or the stem
+//   DGRAD(conv[0]) = DGRAD(downsample) = below(block); an identity block's masked residual add rides in DGRAD(conv[0])
+//   DGRAD(conv[j]) = below(block), or any trainable tensor in conv[0..j-1] of the block               (j >= 1)
+//   WGRAD(L) = T(L);  BN_APPLY(L) = DGRAD(L) | WGRAD(L) (someone reads dY);  BN_SUMS(L) = BN_APPLY(L) | Tg(L)
+//   stem: DGRAD = dx wanted, the rest as above (its BatchNorm passes are the pooled ones)
+// The bits are monotone: a block without work has no work below it, so the gradient of a block's output is needed iff the block
+// has any bit set, and plan_backward stops at the lowest block that has.
+static void backward_work(const Plan& P, const unsigned char* mask, bool want_dx, std::vector<int>& work) {
+  work.assign(P.convs.size(), 0);
+  auto T = [&](int ci) { return !mask || mask[5 * ci]; };                            // (tensor_of: five tensors per convolution)
+  auto Tg = [&](int ci) { return !mask || mask[5 * ci + 1] || mask[5 * ci + 2]; };
+  auto set = [&](int ci, bool dgrad) {
+    const bool wgrad = T(ci), apply = dgrad || wgrad, sums = apply || Tg(ci);
+    work[ci] = (sums ? BW_BN_SUMS : 0) | (apply ? BW_BN_APPLY : 0) | (dgrad ? BW_DGRAD : 0) | (wgrad ? BW_WGRAD : 0);
+    return wgrad || Tg(ci);
+  };
+  bool below = set(0, want_dx) || want_dx;
+  for (const BlockSpec& B : P.blocks) {
+    bool d = below;
+    for (int j = 0; j < B.nconv; ++j) d = set(B.conv[j], d) || d;
+    if (B.ds >= 0) d = set(B.ds, below) || d;
+    below = d;
+  }
+}
+static bool block_has_work(const Plan& P, const std::vector<int>& work, const BlockSpec& B) {
+  int w = B.ds >= 0 ? work[B.ds] : 0;
+  for (int j = 0; j < B.nconv; ++j) w |= work[B.conv[j]];
+  return w != 0;
 }
 
 // Backward stages: 0 = avgpool + layer4, 1 = layer3, 2 = layer2, 3 = layer1 + stem. The gradient w.r.t. the current
@@ -939,17 +1009,17 @@ static int stem_backward(Ctx& c, float* dx, int dx_accumulate) {
 // carried across calls so stages can be issued one by one (the data-parallel wrapper launches the RCCL all-reduce of a
 // finished stage's gradient slice in between).
 //
-// grads == nullptr: no parameter gradient (frozen encoder) — no weight-gradient launch is enqueued, the side stream stays idle and
-// the BatchNorm parameter sums go to plan scratch. dx != nullptr (only with stage 3 in range): d/d(frames) [F,3,H,W] fp32 NCHW
-// of the frames of the last forward (stem_dgrad.hip), written (dx_accumulate = 0) or added.
+// grads == nullptr: no parameter gradient (frozen encoder) — the backward of an all-zero trainable mask with dx wanted: no
+// weight-gradient launch is enqueued, the side stream stays idle and the BatchNorm parameter sums go to plan scratch.
+// dx != nullptr: d/d(frames) [F,3,H,W] fp32 NCHW of the frames of the last forward (stem_dgrad.hip), written (dx_accumulate = 0)
+// or added by stage 3. The call that runs stage 0 fixes the work of all four stages (backward_work) from the plan's trainable mask
+// and from whether it was given dx; a stage without work enqueues nothing.
 int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
                   int accumulate, hipStream_t s, float* dx, int dx_accumulate) {
   RunState& R = P.run;
   Ctx c{P, R, params, grads, nullptr, arena, s, R.last_training, accumulate, P.dtype};
   R3M_REQUIRE(stage_begin >= 0 && stage_end <= 4 && stage_begin < stage_end, "resnet_backward: stages [%d, %d) outside [0, 4)", stage_begin, stage_end);
   R3M_REQUIRE(R.next_stage != -3, "resnet_backward: the last forward on this plan ran in inference mode (training = 2): nothing was kept for a backward");
-  R3M_REQUIRE(!dx || stage_end == 4, "resnet_backward: dx (the input gradient) is formed by the stem, in stage 3; stages [%d, %d) do not "
-              "include it", stage_begin, stage_end);
   R3M_REQUIRE(!dx || !R.last_crop, "resnet_backward: no input gradient after r3m_resnet_forward_crop (the frames were resampled from raw "
               "clips inside the stem pre-pass; pass dx = NULL)");
   R3M_REQUIRE(R.next_stage != -1, "resnet_backward: no forward has run on this plan");
@@ -959,9 +1029,22 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
               "resnet_backward: stage %d requested but the plan expects stage %d (stages run 0..3 in order after each forward; "
               "stage 0 restarts)", stage_begin, R.next_stage);
   R.next_stage = -2;           // poisoned while in flight: after a failed call only stage 0 (a restart) is accepted
+  if (stage_begin == 0) {
+    R.mask = grads ? P.trainable : std::vector<unsigned char>(P.tensors.size(), 0);
+    backward_work(P, R.mask.empty() ? nullptr : R.mask.data(), dx || !grads, R.work);
+  }
+  int stem_work = R.work[0];
+  if (dx && stage_end == 4) {
+    // dx given only now (every caller before the trainable mask existed): fine as long as the gradient chain reaches the stem anyway
+    R3M_REQUIRE(R.work[P.blocks[0].conv[0]] & BW_DGRAD, "resnet_backward: dx asked of stage 3, but the backward planned at stage 0 stops "
+                "above the stem (frozen tensors, r3m_resnet_set_trainable): pass dx to the call that runs stage 0 too");
+    stem_work |= BW_DGRAD | BW_BN_APPLY | BW_BN_SUMS;
+  }
+  bool any_work = false;
+  for (int w : R.work) any_work = any_work || w;
   TRY(R.side.init());
   R.side.begin(s, grads != nullptr);
-  if (stage_begin == 0) {
+  if (stage_begin == 0 && any_work) {
     TRY(TileCounters::reset(c, TileCounters::BACKWARD));
     TRY(build_weight_images(c));
   }
@@ -972,11 +1055,11 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
       R.a_next = 0;
       R.side.restart();
       R.dout_fused_rows = 0;     // the last block's output gradient comes from the pool: its BatchNorm runs the stand-alone reduce
-      TRY(launch_avgpool_bwd(dh, c.G(0), P.F, last.Ho * last.Wo, last.Co, c.dt, s));
+      if (any_work) TRY(launch_avgpool_bwd(dh, c.G(0), P.F, last.Ho * last.Wo, last.Co, c.dt, s));
     }
     for (int bi = (int)P.blocks.size() - 1; bi >= 0; --bi)
-      if (P.blocks[bi].stage == 3 - st) TRY(block_backward(c, bi));
-    if (st == 3) TRY(stem_backward(c, dx, dx_accumulate));
+      if (P.blocks[bi].stage == 3 - st && block_has_work(P, R.work, P.blocks[bi])) TRY(block_backward(c, bi));
+    if (st == 3 && stem_work) TRY(stem_backward(c, dx, dx_accumulate, dx ? stem_work : stem_work & ~BW_DGRAD));
     TRY(R.side.join());     // a finished stage's gradients are complete on the main stream (all-reduce hook, Adam)
   }
   R.next_stage = stage_end == 4 ? 0 : stage_end;
@@ -1021,6 +1104,24 @@ int plan_stage_range(Plan* P, int stage, long long* off, long long* count) {
   if (off) *off = b;
   if (count) *count = e - b;
   return 0;
+}
+int plan_set_trainable(Plan* P, const unsigned char* mask, int n) {
+  R3M_REQUIRE(!(P->run.next_stage >= 1 && P->run.next_stage <= 3), "resnet_set_trainable: a backward is between its stages (stage %d is next); "
+              "the mask changes between backwards", P->run.next_stage);
+  if (!mask) { P->trainable.clear(); return 0; }
+  R3M_REQUIRE(n == (int)P->tensors.size(), "resnet_set_trainable: n=%d, the plan has %d tensors (r3m_resnet_num_tensors)", n,
+              (int)P->tensors.size());
+  P->trainable.resize(n);
+  for (int i = 0; i < n; ++i) P->trainable[i] = mask[i] ? 1 : 0;
+  return 0;
+}
+int plan_debug_backward(Plan* P, int want_dx, int* flags_out, int cap) {
+  const int n = (int)P->convs.size();
+  if (cap < n) { set_last_error("debug_backward_plan: cap=%d, the plan has %d convolutions", cap, n); return -1; }
+  std::vector<int> work;
+  backward_work(*P, P->trainable.empty() ? nullptr : P->trainable.data(), want_dx != 0, work);
+  for (int i = 0; i < n; ++i) flags_out[i] = work[i];
+  return n;
 }
 void plan_destroy(Plan* P) {
   P->run.side.destroy();

@@ -47,8 +47,8 @@ def _tensor_table(size):
 
 
 class _EncoderFn(torch.autograd.Function):
-    """h = encoder(x). Backward writes parameter gradients straight into the module's flat gradient buffer (none when no parameter
-    requires grad) and returns d/dx when x requires grad."""
+    """h = encoder(x). Backward writes the gradients of the parameters that require grad straight into the module's flat gradient
+    buffer (none when no parameter does) and returns d/dx when x requires grad."""
 
     @staticmethod
     def forward(ctx, x, anchor, module, training, crop=None):
@@ -175,6 +175,13 @@ class HipResNet(nn.Module):
         self._scratch = None          # _LiveSlot for forwards without a backward while every ring slot is live (_pick_slot)
         self._last_forward = (0, 0)   # (slot, generation) of the most recent forward
         self._grad_fresh = True
+        # per parameter tensor, in flat-buffer order (_param_ranges): its gradient was written since zero_grad() / its range of the
+        # flat gradient buffer may hold something other than zeros
+        self._param_ranges = [(off, int(math.prod(shape))) for _, kind, off, shape in table if kind <= 2]
+        self._g_written = [False] * len(self._param_ranges)
+        self._g_dirty = [False] * len(self._param_ranges)
+        self._g_viewed = [False] * len(self._param_ranges)      # flat_grads() has given this tensor its .grad view
+        self._plan_masks = {}     # native handle -> the trainable mask it was last given (absent: all trainable, the plan's default)
         self._stage_hook = None   # callable(stage, offset, count) after each backward stage (data-parallel wrapper)
         self.reset_parameters()
 
@@ -282,9 +289,8 @@ class HipResNet(nn.Module):
                         parent._buffers["num_batches_tracked"] = flat_nbt[bn_i]
                         bn_i += 1
         self._flat_p, self._flat_b, self._flat_nbt = flat_p, flat_b, flat_nbt
-        self._flat_g = None
+        self._drop_grads()
         self._arena = None
-        self._grad_fresh = True
 
     def _apply(self, fn, *a, **k):
         super()._apply(fn, *a, **k)
@@ -295,25 +301,116 @@ class HipResNet(nn.Module):
         self._ensure()
         return self._flat_p
 
+    def _drop_grads(self):
+        """forget the flat gradient buffer (re-flatten, copies): nothing written, nothing to accumulate onto"""
+        self._flat_g = None
+        self._g_viewed = [False] * len(self._param_ranges)
+        self._grad_fresh = True
+        self._g_written = [False] * len(self._param_ranges)
+        self._g_dirty = [False] * len(self._param_ranges)
+
+    def _params_in_order(self):
+        """the parameter tensors in flat-buffer order (the order of _param_ranges / _g_written)"""
+        return [t for _, kind, _, _, t in self._named_slots() if kind <= 2]
+
+    def _grad_view(self, t, off):
+        if t.dim() == 4:
+            O, I, kh, kw = t.shape
+            return self._flat_g[off:off + t.numel()].view(O, kh, kw, I).permute(0, 3, 1, 2)
+        return self._flat_g[off:off + t.numel()].view(t.shape)
+
     def flat_grads(self):
+        """The flat gradient buffer. `.grad` views into it are attached to the parameters that require grad (whoever fills the buffer
+        by hand sees the values through them) or whose gradient a backward has written since zero_grad(); a frozen parameter's .grad
+        stays None (unless the user left one there), as torch leaves it. Ranges no backward wrote hold zeros."""
         self._ensure()
         if self._flat_g is None:
             self._flat_g = torch.zeros_like(self._flat_p)
-            for name, kind, off, shape, t in self._named_slots():
-                if kind == 0:
-                    O, I, kh, kw = shape
-                    t.grad = self._flat_g[off:off + t.numel()].view(O, kh, kw, I).permute(0, 3, 1, 2)
-                elif kind <= 2:
-                    t.grad = self._flat_g[off:off + t.numel()].view(shape)
+        self._attach_grad_views()
         return self._flat_g
+
+    def _attach_grad_views(self, params=None):
+        viewed = self._g_viewed
+        if all(viewed):
+            return
+        params = params or self._params_in_order()
+        for i, (t, (off, _)) in enumerate(zip(params, self._param_ranges)):
+            if not viewed[i] and (self._g_written[i] or t.requires_grad):
+                if t.grad is None:
+                    t.grad = self._grad_view(t, off)
+                viewed[i] = True
+
+    def param_ranges(self):
+        """[(offset, count)] of every parameter tensor in the flat buffers, ascending and gap-free (optimizers: the units that can be
+        frozen one by one)"""
+        return self._param_ranges
+
+    def grads_written(self):
+        """per param_ranges() entry: a backward wrote this tensor's gradient since zero_grad() (torch: `p.grad is not None` after
+        zero_grad(set_to_none=True))"""
+        return self._g_written
 
     def _ensure(self):
         if not self._is_flat():
             self._reflatten()
 
     def mark_grads_stale(self):
-        """Called by the optimizer's zero_grad(): the next backward overwrites instead of accumulating."""
+        """Called by the optimizer's zero_grad(): the next backward overwrites instead of accumulating, and until one arrives no
+        parameter has a gradient."""
         self._grad_fresh = True
+        self._g_written = [False] * len(self._param_ranges)
+
+    def _zero_grad_ranges(self, idx):
+        """zero the flat-gradient ranges of the parameter tensors idx (ascending), neighbours in one fill"""
+        a = b = None
+        for i in idx:
+            off, n = self._param_ranges[i]
+            if b == off:
+                b = off + n
+                continue
+            if a is not None:
+                self._flat_g[a:b].zero_()
+            a, b = off, off + n
+        if a is not None:
+            self._flat_g[a:b].zero_()
+
+    def _begin_param_backward(self, h):
+        """Before stage 0 of a backward that writes parameter gradients: hand the plan the trainable mask (requires_grad of every
+        parameter) when it changed, and keep the rule 'gradient of a tensor = sum over the backwards since zero_grad() in which it was
+        trainable, never-written ranges are zero': a tensor that turns trainable inside an accumulation window starts from zero, a
+        tensor frozen since the last window loses its stale values (and its .grad view)."""
+        params = self._params_in_order()
+        req = [t.requires_grad for t in params]
+        mask = None
+        if not all(req):
+            it = iter(req)
+            mask = bytes((1 if next(it) else 0) if kind <= 2 else 0 for _, kind, _, _ in self._table)
+        if self._plan_masks.get(h) != mask:
+            _lib.check(_lib.lib().r3m_resnet_set_trainable(h, mask, 0 if mask is None else len(mask)), "resnet_set_trainable")
+            if mask is None:
+                self._plan_masks.pop(h, None)
+            else:
+                self._plan_masks[h] = mask
+        fresh, written, dirty = self._grad_fresh, self._g_written, self._g_dirty
+        if fresh:
+            stale = [i for i, r in enumerate(req) if not r and dirty[i]]
+            for i, r in enumerate(req):
+                if r or not (dirty[i] or self._g_viewed[i]):
+                    continue
+                dirty[i] = False
+                g = params[i].grad                   # frozen now: its view of the flat buffer goes, a .grad the user put there stays
+                if g is not None and g.device == self._flat_g.device and g.data_ptr() == self._flat_g.data_ptr() + self._param_ranges[i][0] * 4:
+                    params[i].grad = None
+                self._g_viewed[i] = False
+        else:
+            stale = [i for i, r in enumerate(req) if r and not written[i] and dirty[i]]
+        if stale:
+            self._zero_grad_ranges(stale)
+        for i, r in enumerate(req):
+            if r:
+                written[i] = dirty[i] = True
+        self._attach_grad_views(params)              # .grad views for the tensors this backward writes first
+        return mask is not None
 
     def stage_range(self, stage):
         L = _lib.lib()
@@ -384,7 +481,9 @@ class HipResNet(nn.Module):
         reference R3M deep-copies cleanly (plain nn.Module), so must this."""
         st = self.__dict__.copy()
         st.update(_ring=[_LiveSlot() for _ in self._ring], _ring_pos=0, _scratch=None, _last_forward=(0, 0), _flat_g=None,
-                  _stage_hook=None, _grad_fresh=True)
+                  _stage_hook=None, _grad_fresh=True, _plan_masks={}, _g_viewed=[False] * len(self._param_ranges),
+                  _g_written=[False] * len(self._param_ranges),
+                  _g_dirty=[False] * len(self._param_ranges))
         return st
 
     def __setstate__(self, st):
@@ -432,8 +531,10 @@ class HipResNet(nn.Module):
         return out
 
     def _run_backward(self, dh, generation, si=0, fire_hooks=True, params=True, input_grad=False):
-        """params: write parameter gradients into the flat gradient buffer (False: frozen encoder — no weight-gradient launch, the
-        buffer is neither created nor touched, no stage hook fires). input_grad: return d/d(frames) [F,3,H,W] fp32."""
+        """params: write the gradients of the parameters that require grad into the flat gradient buffer (False: frozen encoder — no
+        weight-gradient launch, the buffer is neither created nor touched, no stage hook fires). With some parameters frozen the
+        engine runs only what the trainable ones (and the input gradient) need; all four stage hooks still fire, in order.
+        input_grad: return d/d(frames) [F,3,H,W] fp32."""
         slot = self._slot(si)
         if generation != slot.generation or slot.arena is None:
             raise RuntimeError(f"r3m_amd: the encoder ran {len(self._ring)} other forward(s) before this backward; its saved "
@@ -443,6 +544,7 @@ class HipResNet(nn.Module):
         h = self._plan(slot.F, si, slot.hw)
         g = self.flat_grads() if params else None
         accumulate = 0 if self._grad_fresh else 1
+        partial = self._begin_param_backward(h) if params else False
         dx = torch.empty((slot.F, 3) + tuple(slot.hw), dtype=torch.float32, device=dh.device) if input_grad else None
         with _lib.on(dh):
             for stage in range(4):
@@ -451,7 +553,8 @@ class HipResNet(nn.Module):
                                                      stage, stage + 1, accumulate, _lib.stream_ptr(dh.device)), "resnet_backward")
                 else:
                     _lib.check(L.r3m_resnet_backward_ex(h, dh.data_ptr(), self._flat_p.data_ptr(), _lib.ptr(g), slot.arena.data_ptr(),
-                                                        stage, stage + 1, accumulate, _lib.ptr(dx) if stage == 3 else None, 0,
+                                                        # (frozen tensors: stage 0 plans the backward and must know dx is wanted)
+                                                        stage, stage + 1, accumulate, _lib.ptr(dx) if stage == 3 or partial else None, 0,
                                                         _lib.stream_ptr(dh.device)), "resnet_backward_ex")
                 if g is not None and self._stage_hook is not None and fire_hooks:
                     off, cnt = self.stage_range(stage)
@@ -488,6 +591,9 @@ class HipResNet(nn.Module):
         needs_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
                                                   or (crop is None and x.requires_grad))
         if needs_grad:
-            anchor = next(self.parameters())
+            # (what makes autograd record the node: a parameter that requires grad, when there is one — the first may be frozen)
+            anchor = next((p for p in self.parameters() if p.requires_grad), None)
+            if anchor is None:
+                anchor = next(self.parameters())
             return _EncoderFn.apply(None if crop is not None else x, anchor, self, self.training, crop)
         return self._run_forward(None if crop is not None else x, self.training, crop)

@@ -3,12 +3,76 @@
 Replaces torch.optim.Adam(params, lr=lr) built at /root/reference/r3m/models/models_r3m.py:76 and stepped at
 /root/reference/r3m/trainer.py:156-158 (defaults: betas (0.9, 0.999), eps 1e-8, weight_decay 0, amsgrad False).
 """
+import ctypes as C
+
 import torch
 
 from . import _lib
 
 
-class FusedAdam(torch.optim.Optimizer):
+def _ll(v):
+    return (C.c_longlong * len(v))(*v)
+
+
+class _PerTensorSteps:
+    """Step counts per parameter TENSOR of an owner, as torch.optim keeps them per parameter: a tensor that got no gradient (frozen,
+    requires_grad False) is not stepped and its count — hence its Adam bias correction — stays behind. Kept as each tensor's lag
+    behind the owner's count `_steps[i]` (None: no tensor lags, the state of every run that never froze anything), so code that sets
+    `_steps` by hand keeps meaning "every tensor at that step".
+
+    Owners that expose param_ranges() / grads_written() (HipResNet) are stepped tensor by tensor; the others (the language head,
+    whose tensors are not 4-aligned) stay all-or-nothing through has_grads()."""
+
+    def _advance(self, i, owner):
+        """Advance the counts of owner i's tensors that received a gradient since zero_grad(). Returns None when there is nothing to
+        step, "all" when the whole flat buffer steps with one count (self._steps[i], already advanced), else (offsets, counts, steps)
+        of the merged ranges: neighbouring tensors with equal counts form one range."""
+        if not hasattr(owner, "param_ranges"):
+            if not getattr(owner, "has_grads", lambda: True)():
+                return None
+            self._steps[i] += 1
+            return "all"
+        written = owner.grads_written()
+        if not any(written):
+            return None
+        lag = self._lag[i]
+        if lag is None and all(written):
+            self._steps[i] += 1
+            return "all"
+        ranges = owner.param_ranges()
+        base = self._steps[i]
+        steps = [base] * len(ranges) if lag is None else [base - l for l in lag]
+        steps = [s + 1 if w else s for s, w in zip(steps, written)]
+        base = max(steps)
+        self._steps[i] = base
+        lag = [base - s for s in steps]
+        self._lag[i] = lag if any(lag) else None
+        offs, counts, rsteps = [], [], []
+        for (off, n), s, w in zip(ranges, steps, written):
+            if not w:
+                continue
+            if offs and offs[-1] + counts[-1] == off and rsteps[-1] == s:
+                counts[-1] += n
+            else:
+                offs.append(off); counts.append(n); rsteps.append(s)
+        if len(offs) == 1 and offs[0] == 0 and counts[0] == owner.flat_params().numel():
+            return "all"
+        return offs, counts, rsteps
+
+    def tensor_steps(self, i):
+        """absolute step count per tensor of owner i (None: every tensor at self._steps[i])"""
+        return None if self._lag[i] is None else [self._steps[i] - l for l in self._lag[i]]
+
+    def _load_tensor_steps(self, sd):
+        ts = sd.get("tensor_steps")        # absent in snapshots from before per-tensor counts: every tensor at its owner's step
+        self._lag = [None] * len(self.owners)
+        for i, t in enumerate(ts or []):
+            if t is not None:
+                lag = [self._steps[i] - int(s) for s in t]
+                self._lag[i] = lag if any(lag) else None
+
+
+class FusedAdam(_PerTensorSteps, torch.optim.Optimizer):
     """`owners` are modules exposing flat_params() / flat_grads() / mark_grads_stale() (HipResNet, LanguageReward)."""
 
     def __init__(self, owners, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
@@ -18,13 +82,14 @@ class FusedAdam(torch.optim.Optimizer):
         self._steps = [0] * len(self.owners)   # torch.optim.Adam keeps `step` per parameter: an owner that receives its first
         self._m = [None] * len(self.owners)    # gradient later (the language head) starts its bias correction then
         self._v = [None] * len(self.owners)
+        self._lag = [None] * len(self.owners)  # per-tensor lag behind _steps (_PerTensorSteps)
         self.grad_scale = 1.0
 
     def __getstate__(self):
         # Optimizer.__getstate__ keeps defaults/state/param_groups only; deepcopy(R3M) and pickling must keep the owners
         # protocol and the moments too (the reference's torch.optim.Adam deep-copies with its state).
         st = super().__getstate__()
-        st.update(owners=self.owners, _steps=self._steps, _m=self._m, _v=self._v, grad_scale=self.grad_scale)
+        st.update(owners=self.owners, _steps=self._steps, _m=self._m, _v=self._v, _lag=self._lag, grad_scale=self.grad_scale)
         return st
 
     def zero_grad(self, set_to_none=True):
@@ -43,7 +108,8 @@ class FusedAdam(torch.optim.Optimizer):
             p = o.flat_params()
             if not p.is_cuda:
                 raise RuntimeError("r3m_amd.FusedAdam: parameters must live on the GPU (HIP kernel, no CPU fallback)")
-            if not getattr(o, "has_grads", lambda: True)():
+            todo = self._advance(i, o)         # what torch.optim.Adam steps: the tensors with a gradient since zero_grad()
+            if todo is None:
                 continue
             g = o.flat_grads()
             if self._m[i] is None or self._m[i].device != p.device or self._m[i].numel() != p.numel():
@@ -52,11 +118,16 @@ class FusedAdam(torch.optim.Optimizer):
             n = p.numel()
             pad = (-n) % 4
             assert pad == 0, "flat buffers are padded to multiples of 4 floats"
-            self._steps[i] += 1
             with _lib.on(p):
-                _lib.check(L.r3m_adam_step(p.data_ptr(), g.data_ptr(), self._m[i].data_ptr(), self._v[i].data_ptr(), n, float(lr),
-                                           float(b1), float(b2), float(eps), self._steps[i], float(self.grad_scale),
-                                           _lib.stream_ptr(p.device)), "adam_step")
+                if todo == "all":
+                    _lib.check(L.r3m_adam_step(p.data_ptr(), g.data_ptr(), self._m[i].data_ptr(), self._v[i].data_ptr(), n, float(lr),
+                                               float(b1), float(b2), float(eps), self._steps[i], float(self.grad_scale),
+                                               _lib.stream_ptr(p.device)), "adam_step")
+                else:                          # some tensors frozen, or at other step counts: one launch over the ranges
+                    offs, counts, steps = todo
+                    _lib.check(L.r3m_adam_step_ranges(p.data_ptr(), g.data_ptr(), self._m[i].data_ptr(), self._v[i].data_ptr(),
+                                                      _ll(offs), _ll(counts), _ll(steps), len(offs), float(lr), float(b1), float(b2),
+                                                      float(eps), float(self.grad_scale), _lib.stream_ptr(p.device)), "adam_step_ranges")
 
     def moments(self, param):
         """Read-only views (exp_avg, exp_avg_sq) of Adam's moments for one parameter, shaped and strided like it — what
@@ -78,7 +149,8 @@ class FusedAdam(torch.optim.Optimizer):
 
     # state: enough to resume (the reference never saved optimizer state, train_representation.py:123-130)
     def state_dict(self):
-        return {"step": self._steps[0], "steps": list(self._steps), "exp_avg": [None if m is None else m.cpu() for m in self._m],
+        return {"step": self._steps[0], "steps": list(self._steps), "tensor_steps": [self.tensor_steps(i) for i in range(len(self.owners))],
+                "exp_avg": [None if m is None else m.cpu() for m in self._m],
                 "exp_avg_sq": [None if v is None else v.cpu() for v in self._v], "param_groups": [
                     {k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
 
@@ -98,6 +170,7 @@ class FusedAdam(torch.optim.Optimizer):
                 raise ValueError(f"FusedAdam.load_state_dict: moments of owner {i} ({type(o).__name__}) have {m.numel()} elements, "
                                  f"its parameters {o.flat_params().numel()}")
         self._steps = steps
+        self._load_tensor_steps(sd)
         for i, o in enumerate(self.owners):
             if sd["exp_avg"][i] is not None:
                 dev = o.flat_params().device
@@ -107,7 +180,7 @@ class FusedAdam(torch.optim.Optimizer):
             g.update(s)
 
 
-class FusedSGD(torch.optim.Optimizer):
+class FusedSGD(_PerTensorSteps, torch.optim.Optimizer):
     """torch.optim.SGD semantics (momentum, dampening, weight_decay, nesterov) as one HIP kernel per flat buffer. The reference
     only ever builds Adam (models_r3m.py:76); this is the plain alternative on the same owners protocol."""
 
@@ -119,6 +192,7 @@ class FusedSGD(torch.optim.Optimizer):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov))
         self._steps = [0] * len(self.owners)
         self._buf = [None] * len(self.owners)
+        self._lag = [None] * len(self.owners)
         self.grad_scale = 1.0
 
     def zero_grad(self, set_to_none=True):
@@ -135,19 +209,26 @@ class FusedSGD(torch.optim.Optimizer):
             p = o.flat_params()
             if not p.is_cuda:
                 raise RuntimeError("r3m_amd.FusedSGD: parameters must live on the GPU (HIP kernel, no CPU fallback)")
-            if not getattr(o, "has_grads", lambda: True)():
+            todo = self._advance(i, o)
+            if todo is None:
                 continue
             g = o.flat_grads()
             if g0["momentum"] != 0 and (self._buf[i] is None or self._buf[i].device != p.device or self._buf[i].numel() != p.numel()):
                 self._buf[i] = torch.zeros_like(p)
             buf_ptr = None if self._buf[i] is None else self._buf[i].data_ptr()
-            self._steps[i] += 1
             with _lib.on(p):
-                _lib.check(L.r3m_sgd_step(p.data_ptr(), g.data_ptr(), buf_ptr, p.numel(), float(g0["lr"]), float(g0["momentum"]),
-                                          float(g0["dampening"]), float(g0["weight_decay"]), int(bool(g0["nesterov"])),
-                                          self._steps[i], float(self.grad_scale), _lib.stream_ptr(p.device)), "sgd_step")
+                if todo == "all":
+                    _lib.check(L.r3m_sgd_step(p.data_ptr(), g.data_ptr(), buf_ptr, p.numel(), float(g0["lr"]), float(g0["momentum"]),
+                                              float(g0["dampening"]), float(g0["weight_decay"]), int(bool(g0["nesterov"])),
+                                              self._steps[i], float(self.grad_scale), _lib.stream_ptr(p.device)), "sgd_step")
+                else:
+                    offs, counts, steps = todo
+                    _lib.check(L.r3m_sgd_step_ranges(p.data_ptr(), g.data_ptr(), buf_ptr, _ll(offs), _ll(counts), _ll(steps), len(offs),
+                                                     float(g0["lr"]), float(g0["momentum"]), float(g0["dampening"]),
+                                                     float(g0["weight_decay"]), int(bool(g0["nesterov"])), float(self.grad_scale),
+                                                     _lib.stream_ptr(p.device)), "sgd_step_ranges")
 
     def __getstate__(self):
         st = super().__getstate__()
-        st.update(owners=self.owners, _steps=self._steps, _buf=self._buf, grad_scale=self.grad_scale)
+        st.update(owners=self.owners, _steps=self._steps, _buf=self._buf, _lag=self._lag, grad_scale=self.grad_scale)
         return st
