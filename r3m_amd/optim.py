@@ -151,7 +151,7 @@ class FusedAdam(_PerTensorSteps, torch.optim.Optimizer):
     def state_dict(self):
         return {"step": self._steps[0], "steps": list(self._steps), "tensor_steps": [self.tensor_steps(i) for i in range(len(self.owners))],
                 "exp_avg": [None if m is None else m.cpu() for m in self._m],
-                "exp_avg_sq": [None if v is None else v.cpu() for v in self._v], "param_groups": [
+                "exp_avg_sq": [None if v is None else v.cpu() for v in self._v], "grad_scale": float(self.grad_scale), "param_groups": [
                     {k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
 
     def load_state_dict(self, sd):
@@ -178,6 +178,8 @@ class FusedAdam(_PerTensorSteps, torch.optim.Optimizer):
                 self._v[i] = sd["exp_avg_sq"][i].to(dev)
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
+        if "grad_scale" in sd:              # absent in older snapshots: the optimizer keeps the one it has
+            self.grad_scale = float(sd["grad_scale"])
 
 
 class FusedSGD(_PerTensorSteps, torch.optim.Optimizer):
@@ -232,3 +234,30 @@ class FusedSGD(_PerTensorSteps, torch.optim.Optimizer):
         st = super().__getstate__()
         st.update(owners=self.owners, _steps=self._steps, _buf=self._buf, _lag=self._lag, grad_scale=self.grad_scale)
         return st
+
+    # state: enough to resume, in the manner of FusedAdam's (torch's own state_dict would drop the momentum buffers, the step counts and
+    # grad_scale, which all live outside Optimizer.state)
+    def state_dict(self):
+        return {"steps": list(self._steps), "tensor_steps": [self.tensor_steps(i) for i in range(len(self.owners))],
+                "momentum_buffer": [None if b is None else b.cpu() for b in self._buf], "grad_scale": float(self.grad_scale),
+                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+
+    def load_state_dict(self, sd):
+        n = len(self.owners)
+        if len(sd["steps"]) != n or len(sd["momentum_buffer"]) != n:
+            raise ValueError(f"FusedSGD.load_state_dict: the snapshot holds optimizer state for {len(sd['steps'])} flat buffer(s), this "
+                             f"optimizer has {n} ({', '.join(type(o).__name__ for o in self.owners)})")
+        for i, o in enumerate(self.owners):
+            b = sd["momentum_buffer"][i]
+            if b is not None and b.numel() != o.flat_params().numel():
+                raise ValueError(f"FusedSGD.load_state_dict: the momentum buffer of owner {i} ({type(o).__name__}) has {b.numel()} elements, "
+                                 f"its parameters {o.flat_params().numel()}")
+        self._steps = [int(s) for s in sd["steps"]]
+        self._load_tensor_steps(sd)
+        for i, o in enumerate(self.owners):
+            b = sd["momentum_buffer"][i]
+            self._buf[i] = None if b is None else b.to(o.flat_params().device)
+        for g, s in zip(self.param_groups, sd["param_groups"]):
+            g.update(s)
+        if "grad_scale" in sd:
+            self.grad_scale = float(sd["grad_scale"])

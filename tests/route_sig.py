@@ -6,13 +6,16 @@ A signature is (dtype, dgrad, flags, mask_bits, routes, k, stride, Co % 128 == 0
 import ctypes as C
 
 STATS, ACCUM, MASKED_ADD, BNRED, AFFINE, RELU = 1, 2, 4, 64, 128, 16
+BIAS, MASK_OUT = 8, 32         # only the language-reward head asks these: Linear + bias + ReLU forward, ReLU mask on the stored input gradient
 # (dgrad, flags, mask_bits) the operator entry points of include/r3m_hip.h can ask for: r3m_conv2d_fwd[_dt] with / without statistics,
 # r3m_conv2d_dgrad[_dt], r3m_conv2d_dgrad_bnred_dt in its three modes, r3m_conv2d_dgrad_join_dt (accumulate onto a stored gradient;
 # masked join without partials -- its residual bits are not the mask_bits of a signature, which are the BatchNorm partials'),
-# r3m_conv2d_fwd_affine_dt (the three eval-BatchNorm stores of inference). Nothing the engine launches is left without one.
+# r3m_conv2d_fwd_affine_dt (the three eval-BatchNorm stores of inference). Nothing the engine launches is left without one. The last two
+# are the language-reward head's (csrc/lang.hip mlp_forward / mlp_backward), reached through r3m_langrew_* (head_launches below).
 OPERATOR_EPILOGUES = {(0, STATS, 0), (0, 0, 0), (1, 0, 0), (1, BNRED, 0), (1, BNRED, 1), (1, BNRED | MASKED_ADD, 1),
                       (1, ACCUM, 0), (1, MASKED_ADD, 0), (1, MASKED_ADD, 1),
-                      (0, AFFINE, 0), (0, AFFINE | RELU, 0), (0, AFFINE | ACCUM | RELU, 0)}
+                      (0, AFFINE, 0), (0, AFFINE | RELU, 0), (0, AFFINE | ACCUM | RELU, 0),
+                      (0, BIAS | RELU, 0), (1, MASK_OUT, 0)}
 BNRED_MODES = {"recompute": (BNRED, 0), "bits": (BNRED, 1), "bits+residual": (BNRED | MASKED_ADD, 1)}
 
 
@@ -61,6 +64,20 @@ def join_case_signatures(L, cases, dt):
             for bits in (0, 1):
                 out[signature(L, c, 1, MASKED_ADD, bits, dt)] = (c, mode)
     return out
+
+
+def head_launches(R, K1, H, dt):
+    """[(case, dgrad, flags)] of the GEMM launches of one language-reward head pass over R rows (csrc/lang.hip): a Linear(K -> H) is the
+    1x1 convolution of R one-pixel images. fp32: forward with bias + ReLU (24) for K1 -> H and H -> H, input gradient plain for layer 0
+    and with the ReLU mask of the layer below (32) for layers 1-3. The bf16 head asks plain stores (flags 0) throughout."""
+    lin = lambda K: (R, 1, 1, K, H, 1, 1, 0)
+    fwd = 0 if dt else BIAS | RELU
+    return [(lin(K1), 0, fwd), (lin(H), 0, fwd), (lin(K1), 1, 0), (lin(H), 1, 0 if dt else MASK_OUT)]
+
+
+def head_signature(L, case, dgrad, flags, dt):
+    """(dtype, dgrad, flags, routes, Co % 128 == 0) of one head launch: k, stride and the map are 1 x 1 for every one of them"""
+    return (dt, dgrad, flags, routes(L, case, dgrad, flags, 0, dt), case[4] % 128 == 0)
 
 
 def pw_queue_grids(L, case, dgrad, flags):

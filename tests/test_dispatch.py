@@ -347,3 +347,43 @@ def test_tile_queue_cases_pass_the_launchers_threshold():
             ("accumulate", True, 1)} <= kinds, kinds
     # the burst launches of 64-wide outputs run the 512 x 64 tile: 6 x 56 x 56 rows are 37 panels there, NOT a queue case
     assert route_sig.pw_queue_grids(L, (6, 56, 56, 64, 64, 3, 1, 1), 0, STATS) == ((37, 1),)
+
+
+# ---- the language-reward head's Linear layers (csrc/lang.hip through the conv GEMMs; tests/test_gpu_langrew_edges.py) -----------------------
+def test_head_launches_of_the_workload_have_an_operator_case():
+    """The head's Linear layers are conv launches with epilogues nothing else asks (forward 8 | 16 = bias + ReLU, input gradient 32 = ReLU
+    mask on the store). The workload runs them at R = 15 x 256 and 15 x 512 rows, K1 = 2 x 512 + 768 and 2 x 2048 + 768, H = 1024, in
+    both dtypes: every signature (dtype, dgrad, flags, routes, Co % 128 == 0) of those launches is the signature of a launch of a case
+    of tests/test_gpu_langrew_edges.py (batched and single-call lists), and the dispatch refuses none of either."""
+    from r3m_amd import _lib
+    import test_gpu_langrew_edges as T
+    L = _lib.lib()
+    have = {}
+    for (B, D, H, LD) in T.FP32_CASES:
+        for (case, dgrad, flags) in route_sig.head_launches(15 * B, 2 * D + LD, H, 0):
+            have.setdefault(route_sig.head_signature(L, case, dgrad, flags, 0), (B, D, H, LD))
+    for (B, D, H, LD) in T.BF16_CASES:
+        assert LD % 64 == 0
+        for (case, dgrad, flags) in route_sig.head_launches(15 * B, 2 * D + LD, H, 1):
+            have.setdefault(route_sig.head_signature(L, case, dgrad, flags, 1), (B, D, H, LD))
+    for R in T.CALL_ROWS:
+        D, H, LD = T.CALL_DIMS
+        for (case, dgrad, flags) in route_sig.head_launches(R, 2 * D + LD, H, 0):
+            have.setdefault(route_sig.head_signature(L, case, dgrad, flags, 0), ("call", R))
+    assert all(sig[3] for sig in have), [c for sig, c in have.items() if not sig[3]]
+    missing, seen = {}, set()
+    for R in (15 * 256, 15 * 512):
+        for K1 in (2 * 512 + 768, 2 * 2048 + 768):
+            for dt in (0, 1):
+                for (case, dgrad, flags) in route_sig.head_launches(R, K1, 1024, dt):
+                    sig = route_sig.head_signature(L, case, dgrad, flags, dt)
+                    assert sig[3], (case, dgrad, flags, dt, L.r3m_last_error())
+                    assert (dgrad, flags, 0) in route_sig.OPERATOR_EPILOGUES, (case, dgrad, flags)
+                    seen.add(sig)
+                    if sig not in have:
+                        missing.setdefault(sig, case)
+    assert not missing, "no case in tests/test_gpu_langrew_edges.py for:\n" + "\n".join(f"  signature {k}: e.g. {v}" for k, v in missing.items())
+    # what the workload's head runs today: gather GEMM with and without the LDS-direct loads forward, the persistent pointwise kernel and
+    # the gather GEMM for the input gradients; the bf16 gather kernel throughout
+    assert {s[3] for s in seen if s[0] == 0 and s[1] == 0} == {(21,), (22,)} and {s[3] for s in seen if s[0] == 0 and s[1] == 1} == {(PW_POINT,), (21,)}
+    assert {s[3] for s in seen if s[0] == 1} == {(BF16,)}

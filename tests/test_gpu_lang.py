@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import rel_err
+from util import infonce_torch as _infonce_torch, langrew_bf16_model, rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -108,33 +108,14 @@ def test_full_step_with_language_vs_oracle(hip):
 @pytest.mark.parametrize("B,D,H,LD", [(4, 64, 64, 32), (5, 512, 128, 768), (3, 2048, 1024, 768)])
 def test_langrew_c_abi_vs_torch(hip, B, D, H, LD):
     """r3m_langrew_forward/backward through the C ABI vs a torch-CPU MLP evaluated call by call (models_language.py:43-55)."""
-    import torch.nn as nn
-    from util import rnd
-    K1 = 2 * D + LD
-    layers = [nn.Linear(K1, H), nn.Linear(H, H), nn.Linear(H, H), nn.Linear(H, H), nn.Linear(H, 1)]
-    torch.manual_seed(0)
-    for l in layers:
-        nn.init.uniform_(l.weight, -1.0 / np.sqrt(l.in_features), 1.0 / np.sqrt(l.in_features))
-        nn.init.uniform_(l.bias, -0.1, 0.1)
+    from util import langrew_layers, langrew_scores_call_by_call, rnd
+    layers = langrew_layers(D, H, LD, seed=0)
     alle = torch.relu(rnd((B, 5, D), 1, -0.5, 1.0)).requires_grad_(True)
     feats = rnd((B, LD), 2, -0.6, 0.6)
     g = torch.Generator().manual_seed(3)
     perm = torch.stack([torch.randperm(B, generator=g) for _ in range(9)])
     dscore = rnd((15, B), 4, -1.0, 1.0)
-
-    def G(a, b):
-        x = torch.cat([a, b, feats], -1)
-        for l in layers[:-1]:
-            x = torch.relu(l(x))
-        return layers[-1](x).squeeze(-1)
-
-    e0, eg, es0, es1, es2 = [alle[:, i] for i in range(5)]
-    sc = [G(e0, eg), G(e0, es1), G(e0, es2), G(e0, e0), G(e0, es0), G(e0, es1)]
-    for k in range(3):
-        for j, other in enumerate((eg, es1, es2)):
-            p = perm[3 * k + j]
-            sc.append(G(e0[p], other[p]))
-    scores_ref = torch.stack(sc)
+    scores_ref = langrew_scores_call_by_call(layers, alle, feats, perm)
     (scores_ref * dscore).sum().backward()
 
     flat = torch.cat([t.detach().reshape(-1) for l in layers for t in (l.weight, l.bias)])
@@ -171,17 +152,6 @@ def test_langrew_c_abi_vs_torch(hip, B, D, H, LD):
             assert e < 1e-4, (tuple(t.shape), e)
             off += k
     assert gref.numel() == n
-
-
-def _infonce_torch(scores, mask):
-    """trainer.py:95-110 on a [15,B] score table in the batched row order (pos1-3, in-clip negs 1-3, then k-major permuted negs)."""
-    eps = 1e-8
-    tot = 0
-    for j in range(3):
-        pos = scores[j]
-        negs = torch.stack([scores[3 + j]] + [scores[6 + 3 * k + j] for k in range(3)], -1)
-        tot = tot - torch.log(eps + (torch.exp(pos) / (eps + torch.exp(pos) + torch.exp(negs).sum(-1))))
-    return ((tot / 3) * mask).mean()
 
 
 def test_reference_style_15_call_loop_equals_batched(hip, golden_dir):
@@ -383,24 +353,11 @@ def test_bf16_head_follows_fp32_head_and_its_own_rounding_model(hip, B, D):
     assert cos(da16, da32) >= 0.99 and cos(g16, g32) >= 0.99
 
     # checker 2: float64 MLP with the kernel's rounding points (straight-through in the backward pass)
-    def r16(t):
-        return t + (t.to(torch.bfloat16).to(torch.float64) - t).detach()
-    sd = {k: v.double().cpu().clone().requires_grad_(True) for k, v in rew32.state_dict().items()}
-    a64 = alle0.double().clone().requires_grad_(True)
-    bframe = [1, 3, 4, 0, 2, 3] + [1, 3, 4] * 3
-    rows = []
-    for q in range(15):
-        src = torch.arange(B) if q < 6 else perm[q - 6].cpu().long()
-        rows.append(torch.cat([a64[src, 0], a64[src, bframe[q]], feats.cpu().double()], dim=1))
-    x = r16(torch.cat(rows, dim=0))
-    for li in (0, 2, 4, 6):
-        x = r16(torch.relu(r16(x @ r16(sd[f"pred.{li}.weight"]).T) + sd[f"pred.{li}.bias"]))
-    s_model = (x @ sd["pred.8.weight"].T + sd["pred.8.bias"]).reshape(15, B)
-    (s_model * wts.cpu().double()).sum().backward()
-    err = float((s16 - s_model.detach()).abs().max())
-    g_model = torch.cat([sd[f"pred.{li}.{pn}"].grad.reshape(-1) for li in (0, 2, 4, 6, 8) for pn in ("weight", "bias")])
+    wb = [tuple(rew32.state_dict()[f"pred.{li}.{pn}"].double().cpu().clone().requires_grad_(True) for pn in ("weight", "bias")) for li in (0, 2, 4, 6, 8)]
+    s_model, da_model, g_model = langrew_bf16_model(wb, alle0, feats, perm, wts)
+    err = float((s16 - s_model).abs().max())
     n = g_model.numel()
-    print(f"bf16 head vs its float64 rounding model: scores max|d| {err:.3e}; cos dalle {cos(da16, a64.grad):.6f}, cos param grads "
-          f"{cos(g16[:n], g_model):.6f} (fp32 head vs the same model: {cos(da32, a64.grad):.6f} / {cos(g32[:n], g_model):.6f})")
-    assert err <= 2e-3 * max(1.0, float(s_model.detach().abs().max()))
-    assert cos(da16, a64.grad) >= 0.999 and cos(g16[:n], g_model) >= 0.999
+    print(f"bf16 head vs its float64 rounding model: scores max|d| {err:.3e}; cos dalle {cos(da16, da_model):.6f}, cos param grads "
+          f"{cos(g16[:n], g_model):.6f} (fp32 head vs the same model: {cos(da32, da_model):.6f} / {cos(g32[:n], g_model):.6f})")
+    assert err <= 2e-3 * max(1.0, float(s_model.abs().max()))
+    assert cos(da16, da_model) >= 0.999 and cos(g16[:n], g_model) >= 0.999
