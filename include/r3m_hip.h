@@ -66,7 +66,7 @@ int r3m_debug_conv_route(int N, int H, int W, int Ci, int Co, int k, int stride,
    output from the convolution itself; 0 when the engine runs that block's unfused sequence instead. r3m_debug_conv_route with the same
    flags (dgrad = 0) reports the route the fused launch takes. */
 int r3m_debug_conv_fuses_affine(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int flags, int dtype);
-/* Diagnostic, runs without a GPU: the launch geometry the BatchNorm passes of csrc/bn.hip pick for a [rows][C] tensor of `dtype` (C a
+/* Diagnostic, runs without a GPU: the launch geometry the streaming BatchNorm passes of csrc/bn.hip pick for a [rows][C] tensor of `dtype` (C a
    power of two >= 4) -- computed by the helpers the launchers themselves call, nothing is launched. out[0..13]:
      0-2   forward apply (r3m_bn_act_fwd_dt): elements per lane (4 | 8), items per block (span: 256 | 1024), blocks
      3-7   backward reduce (first pass of r3m_bn_bwd_dt): elements per lane, rows per block, rows per pass (rpp: the rows a block reads at

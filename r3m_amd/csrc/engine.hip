@@ -304,7 +304,7 @@ Plan* plan_create(int size, int F, int dtype, int H, int W) {
       if (welems * split > wgp_max) wgp_max = welems * split;
     }
   }
-  // stem: P0 (pooled) and the argmax bytes; the pre-pool activation Z0 is never materialised (bn.hip: fused stem tail)
+  // stem: P0 (pooled) and the argmax bytes; the pre-pool activation Z0 is never materialised (bn_pool.hip: fused stem tail)
   P.P0_off = take(act(Fll * P.Hp * P.Wp * 64));
   P.amax_off = take((Fll * P.Hp * P.Wp * 64 + 3) / 4);
   long long cur_in = P.P0_off;
@@ -713,7 +713,7 @@ static int bn_backward(Ctx& c, const ConvSpec& L, const float* dZ, const unsigne
                              c.coef(L, 5), dY, rows, L.Co, c.dt, c.s);
 }
 // The two BatchNorms that feed a downsample block's add + ReLU (its last convolution's and the downsample convolution's) see the SAME
-// masked output gradient: their second passes run as ONE launch that reads dOut and the mask bits once (bn.hip, bn_bwd_apply2).
+// masked output gradient: their second passes run as ONE launch that reads dOut and the mask bits once (bn.hip, bn_bwd_apply_kernel with NB = 2).
 // The sums of the two are taken one after the other (they share the partial / accumulator scratch).
 // work / work_d: the BW_* bits of L / Ld. The joint launches run as long as either side needs them, so that the side that is wanted
 // sees the kernels and inputs of a full backward (bit-identical gradients); only the other side's combine is dropped, and its dY

@@ -79,7 +79,7 @@ def test_case_list_has_every_boundary(L, dtype):
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_pair_case_list_has_every_tail_of_the_paired_second_pass(L, dtype):
-    """bn_bwd_apply2_kernel / bn_bwd_apply2_16_kernel walk their span on their own: per channel count the multi-block cases of the pair list
+    """bn_bwd_apply_kernel's NB = 2 instantiations walk their span on their own: per channel count the multi-block cases of the pair list
     end in exactly the tail kinds that can exist for that (C, dtype) (util.bn_possible_tails: up to all five for span 1024; full, one,
     all_but_one and part for span 256, only full where one row already fills the span); one row fits one block unless it is longer
     than the span; rows 1..3 and the large case are there"""

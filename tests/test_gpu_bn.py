@@ -200,7 +200,7 @@ PAIR_CASES = bn_pair_cases()          # every tail kind of the paired second pas
 
 @pytest.mark.parametrize("rows,C_,dtype", PAIR_CASES, ids=[f"{r}x{c}_{d}" for (r, c, d) in PAIR_CASES])
 def test_bn_backward_pair(hip, rows, C_, dtype):
-    """r3m_bn_bwd_pair_dt (bn_bwd_apply2[_16]_kernel, bn_bwd_reduce2_16_kernel) on out = relu(bn_a(y) + bn_b(y2)) against two r3m_bn_bwd_dt
+    """r3m_bn_bwd_pair_dt (bn_bwd_apply_kernel / bn_bwd_reduce_kernel with NB = 2) on out = relu(bn_a(y) + bn_b(y2)) against two r3m_bn_bwd_dt
     calls on the same inputs: dy bit for bit; dgamma / dbeta bit for bit in fp32 (first passes one after the other), within the
     ceilings in bf16 (joint first pass); both orders against float64. use_batch_stats 1 / 0 x accumulate 0 / 1."""
     inp = bn_inputs(rows, C_, dtype, "downsample")

@@ -285,7 +285,7 @@ def test_stem_tail_fused_vs_torch_hw(hip, H, W, dtype):
     p_ref.backward(nchw(dp).double())
     g = yr.grad / c[2]                          # dz routed by the pool and masked by the ReLU, as the kernel's first pass sees it
     if dt == 1:                                 # a pixel that is the maximum of up to four windows: the kernel rounds the sum of their
-        g = q_bf16(g.float()).double()          # pooled gradients to bf16, as the unfused sequence stores dz (csrc/bn.hip pool_quad)
+        g = q_bf16(g.float()).double()          # pooled gradients to bf16, as the unfused sequence stores dz (csrc/bn_pool.hip pool_quad)
     yhat = (y.double() - c[0]) * c[1]
     db_ref, dg_ref = g.sum(0), (g * yhat).sum(0)
     dy_ref = c[2] * (g - g.mean(0) - yhat * (g * yhat).mean(0))

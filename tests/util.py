@@ -359,6 +359,11 @@ def bn_cases():
     # a tail of literally one 16-byte vector needs one vector per row: C = 8 in bf16 (the launchers take it; no mask bits at these sizes)
     add(1025, 8, "bf16", "one_vector")
     add(2047, 8, "bf16", "one_vector")
+    # C = 4 is the one channel count at which bf16 runs the 4-wide kernels: a multiple of 32 elements (mask bits), and three blocks
+    # whose last one holds one vector (no bits)
+    for dtype in ("fp32", "bf16"):
+        add(512, 4, dtype, "narrow")
+        add(513, 4, dtype, "narrow")
     for dtype in ("fp32", "bf16"):
         add(BN_LARGE[0], BN_LARGE[1], dtype, "large")
     _bn_cases = out
@@ -376,8 +381,8 @@ def bn_possible_tails(C, vec, span):
 
 def bn_pair_cases():
     """[(rows, C, dtype)] for the paired tail kernels (C >= 64: a downsample block's tail): per channel count and dtype one multi-block
-    case of EVERY tail kind the paired second pass can end in (bn_span_tail of the backward-apply span: apply2 / apply2_16 walk their
-    span on their own), a single-block case, every case with rows <= 3, the large case, and every third case of the rest."""
+    case of EVERY tail kind the paired second pass can end in (bn_span_tail of the backward-apply span: the NB = 2 instantiations of
+    bn_bwd_apply_kernel walk their span on their own), a single-block case, every case with rows <= 3, the large case, and every third case of the rest."""
     L_ = None
     out, seen = [], set()
     for i, (rows, C, dtype, why) in enumerate(bn_cases()):
