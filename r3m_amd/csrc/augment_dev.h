@@ -1,5 +1,5 @@
 // r3m_amd — the bilinear sample of the rc / rctraj crop, shared by the stand-alone crop kernel (augment.hip) and the stem
-// pre-passes that read the raw clips directly (stem.hip stem_prep_crop_kernel, stem_bf16.hip stem_prep16_crop_kernel), so the
+// pre-passes that read the raw clips directly (stem_dev.h StemCrop: stem_prep_kernel, stem_bf16.hip stem_prep16_kernel), so the
 // fused path performs the SAME float operations in the same order as crop -> stem_prep and produces the same bits.
 #pragma once
 #include "common.h"

@@ -152,14 +152,6 @@ int wgrad_debug_occupancy(int* out);     // debug_occupancy's fourth output
 bool wgrad_rowwin_eligible(const WgradParams& p);
 int launch_wgrad_rowwin(WgradParams& p, int splitK, hipStream_t s);
 
-// ---- launchers (stem.hip): the fp32 stem of 224 x 224 frames ----
-int launch_stem_prep(const float* x_nchw, float* xn, int F, hipStream_t s);
-struct FrameSource;   // augment_dev.h: raw clips + crop boxes
-int launch_stem_prep_crop(const FrameSource& src, float* xn, int F, hipStream_t s);
-int launch_stem_fwd(const float* xn, const float* w147, void* y, float* stats, int F, int dt, hipStream_t s);
-size_t stem_wgrad_ws_floats();
-int launch_stem_wgrad(const float* xn, const void* dY, float* dw147, float* ws, int F, int accumulate, int dt, hipStream_t s);
-
 // ---- launchers (conv_bf16.hip): bf16 forward / input-gradient gather-GEMM, the bf16 weight images ----
 int launch_gather_gemm_bf16(const GatherGemmParams& p, hipStream_t s);
 bool gg16_route_builds(int route, int flags);           // whether bf16 route `route` has a kernel for epilogue `flags`
@@ -187,17 +179,26 @@ static inline int pw16_set_mode(int) { return -1; }
 int launch_wgrad_bf16(const WgradParams& p, int splitK, hipStream_t s);
 int wgrad_bf16_pick_split(int M, int Co, int Ci, int T);
 
-// ---- launchers (stem_bf16.hip): the stem on the bf16 MFMA, from a padded bf16 image of the normalised frames ----
+// ---- launchers of the stem (x/255 -> Normalize -> conv1 7x7/2 pad 3, 3 -> 64): three kernel sets, one device header (stem_dev.h);
+// the engine picks the set once per call (engine.hip, struct Stem). w147 / dw147: conv1's weights OHWI [64][7][7][3] ----
+struct FrameSource;   // augment_dev.h: raw clips + crop boxes
+// stem.hip: fp32 MFMA, 224 x 224 frames; xn = [F][224][224*3] fp32 normalised frames; y / dY fp32 or bf16 (dt)
+int launch_stem_prep(const float* x_nchw, float* xn, int F, hipStream_t s);
+int launch_stem_prep_crop(const FrameSource& src, float* xn, int F, hipStream_t s);
+int launch_stem_fwd(const float* xn, const float* w147, void* y, float* stats, int F, int dt, hipStream_t s);
+size_t stem_wgrad_ws_floats();           // the partials only: ws holds 64 * 160 floats more
+int launch_stem_wgrad(const float* xn, const void* dY, float* dw147, float* ws, int F, int accumulate, int dt, hipStream_t s);
+// stem_bf16.hip: bf16 MFMA, 224 x 224 frames, from a padded bf16 image of the normalised frames
 size_t stem_xn16_bytes(int F);
 int launch_stem_prep16(const float* x_nchw, void* xn16, int F, hipStream_t s);
 int launch_stem_prep16_crop(const FrameSource& src, void* xn16, int F, hipStream_t s);
 int launch_stem_fwd16(const void* xn16, const float* w147, void* y, float* stats, int F, hipStream_t s);
 size_t stem_wgrad16_ws_floats();
 int launch_stem_wgrad16(const void* xn16, const void* dY, float* dw147, float* ws, int F, int accumulate, hipStream_t s);
-// ---- launcher (stem_dgrad.hip): input gradient of the stem, dz [F,112,112,64] fp32 / bf16 -> dx [F,3,224,224] fp32 NCHW (= or +=) ----
+// stem_dgrad.hip: input gradient at 224 x 224, dz [F,112,112,64] fp32 / bf16 -> dx [F,3,224,224] fp32 NCHW (= or +=)
 int launch_stem_input_grad(const void* dz, int dt, const float* w147, float* dx, int F, int accumulate, hipStream_t s);
-// ---- launchers (stem_gen.hip): the stem for frames of any H x W in [STEM_GEN_MIN, STEM_GEN_MAX]; xn = [F][H][W*3] normalised frames,
-// fp32 (dt = DT_F32) or bf16 (DT_BF16) behind a float pointer ----
+// stem_gen.hip: frames of any H x W in [STEM_GEN_MIN, STEM_GEN_MAX]; xn = [F][H][W*3] normalised frames, fp32 (dt = DT_F32) or bf16
+// (DT_BF16) behind a float pointer
 constexpr int STEM_GEN_MIN = 32, STEM_GEN_MAX = 512;
 int stem_gen_check(int F, int H, int W);
 int launch_stem_prep_gen(const float* x_nchw, float* xn, int F, int H, int W, int dt, hipStream_t s);

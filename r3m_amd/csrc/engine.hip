@@ -174,6 +174,65 @@ static int add_conv(Plan& P, const std::string& name, const std::string& bn, int
 
 static int g_generic_stem = 0;      // r3m_debug_set_generic_stem
 int engine_set_generic_stem(int on) { const int old = g_generic_stem; g_generic_stem = on ? 1 : 0; return old; }
+
+// ---- the stem: the kernel set one call runs, its image and workspace sizes, and its four operations ----
+// 224 x 224 frames run stem.hip (fp32 plans) or stem_bf16.hip (bf16 plans) with stem_dgrad.hip; every other size, and 224 under
+// r3m_debug_set_generic_stem, the general kernels of stem_gen.hip. The sets keep different normalised images (xn), so the backward
+// runs the set its forward chose (RunState::stem_gen).
+enum StemSet { STEM_224_F32, STEM_224_BF16, STEM_GEN };
+struct Stem {
+  StemSet set;
+  int F, H, W, dt;
+  hipStream_t s;
+  Stem(const Plan& P, int dt, bool gen, hipStream_t s)
+      : set(gen ? STEM_GEN : dt == DT_BF16 ? STEM_224_BF16 : STEM_224_F32), F(P.F), H(P.H), W(P.W), dt(dt), s(s) {}
+  // arena floats of the normalised image: fp32 channel-interleaved rows, the padded bf16 image of stem_bf16.hip, or the general
+  // stem's plain [F][H][W*3] rows in the plan's precision
+  static long long image_floats(StemSet set, long long F, int H, int W, int dt) {
+    if (set == STEM_224_BF16) return (long long)((stem_xn16_bytes((int)F) + 3) / 4);
+    return set == STEM_GEN && dt == DT_BF16 ? (F * 3 * H * W + 1) / 2 : F * 3 * H * W;
+  }
+  static long long wgrad_ws_floats(StemSet set) {
+    if (set == STEM_GEN) return (long long)stem_wgrad_gen_ws_floats();
+    return set == STEM_224_BF16 ? (long long)stem_wgrad16_ws_floats() : (long long)stem_wgrad_ws_floats() + 64 * 160;
+  }
+  // what a plan reserves: the larger of what the sets it may run need — the general set always (at 224 under
+  // r3m_debug_set_generic_stem), the 224 set of the plan's precision at 224
+  static long long plan_image_floats(bool is224, long long F, int H, int W, int dt) {
+    const long long n = image_floats(STEM_GEN, F, H, W, dt);
+    return is224 ? std::max(n, image_floats(dt == DT_BF16 ? STEM_224_BF16 : STEM_224_F32, F, H, W, dt)) : n;
+  }
+  static long long plan_wgrad_ws_floats(bool is224, int dt) {
+    const long long n = wgrad_ws_floats(STEM_GEN);
+    return is224 ? std::max(n, wgrad_ws_floats(dt == DT_BF16 ? STEM_224_BF16 : STEM_224_F32)) : n;
+  }
+  // frames (or, 224 sets only, the raw clips through their crop boxes) -> xn
+  int prep(const float* x_nchw, const FrameSource* crop, float* xn) const {
+    switch (set) {
+      case STEM_GEN: return launch_stem_prep_gen(x_nchw, xn, F, H, W, dt, s);
+      case STEM_224_BF16: return crop ? launch_stem_prep16_crop(*crop, xn, F, s) : launch_stem_prep16(x_nchw, xn, F, s);
+      default: return crop ? launch_stem_prep_crop(*crop, xn, F, s) : launch_stem_prep(x_nchw, xn, F, s);
+    }
+  }
+  int forward(const float* xn, const float* w, float* Y, float* stats) const {
+    switch (set) {
+      case STEM_GEN: return launch_stem_fwd_gen(xn, w, Y, stats, F, H, W, dt, s);
+      case STEM_224_BF16: return launch_stem_fwd16(xn, w, Y, stats, F, s);
+      default: return launch_stem_fwd(xn, w, Y, stats, F, dt, s);
+    }
+  }
+  int wgrad(const float* xn, const float* dY, float* dw, float* ws, int accumulate) const {
+    switch (set) {
+      case STEM_GEN: return launch_stem_wgrad_gen(xn, dY, dw, ws, F, H, W, accumulate, dt, s);
+      case STEM_224_BF16: return launch_stem_wgrad16(xn, dY, dw, ws, F, accumulate, s);
+      default: return launch_stem_wgrad(xn, dY, dw, ws, F, accumulate, dt, s);
+    }
+  }
+  int input_grad(const float* dY, const float* w, float* dx, int accumulate) const {
+    if (set == STEM_GEN) return launch_stem_input_grad_gen(dY, dt, w, dx, F, H, W, accumulate, s);
+    return launch_stem_input_grad(dY, dt, w, dx, F, accumulate, s);
+  }
+};
 static int g_fused_inference = 1;   // r3m_debug_set_fused_inference
 int engine_set_fused_inference(int on) { const int old = g_fused_inference; g_fused_inference = on ? 1 : 0; return old; }
 
@@ -272,10 +331,8 @@ Plan* plan_create(int size, int F, int dtype, int H, int W) {
   const long long Fll = F;
   // arena offsets are in floats whatever the storage type; a bf16 tensor of n elements takes n/2 of them
   auto act = [&](long long n) { return dtype == DT_BF16 ? (n + 1) / 2 : n; };
-  // private normalised copy of the input frames (the stem's weight gradient re-reads it in backward): fp32 channel-interleaved
-  // rows, or for bf16 plans the padded bf16 image of stem_bf16.hip
-  // (the general stem, stem_gen.hip, keeps plain [F][H][W*3] rows: at 224 they fit in either image)
-  P.col_off = take(dtype == DT_BF16 ? (is224 ? (long long)((stem_xn16_bytes(F) + 3) / 4) : (Fll * 3 * H * W + 1) / 2) : Fll * 3 * H * W);
+  // private normalised copy of the input frames (the stem's weight gradient re-reads it in backward)
+  P.col_off = take(Stem::plan_image_floats(is224, Fll, H, W, dtype));
   long long gmax = 0, partial_max = 0, wmax = 0, wgp_max = 0;
   auto act_elems = [&](const ConvSpec& c) { return Fll * c.Ho * c.Wo * c.Co; };
   for (size_t i = 0; i < P.convs.size(); ++i) {
@@ -296,9 +353,7 @@ Plan* plan_create(int size, int F, int dtype, int H, int W) {
     const long long welems = (long long)c.Co * c.k * c.k * c.Ci;
     if (welems > wmax) wmax = welems;
     if (i == 0) {
-      long long need = (long long)stem_wgrad_gen_ws_floats();
-      if (is224) need = std::max(need, dtype == DT_BF16 ? (long long)stem_wgrad16_ws_floats() : (long long)stem_wgrad_ws_floats() + 64 * 160);
-      if (need > wgp_max) wgp_max = need;
+      wgp_max = std::max(wgp_max, Stem::plan_wgrad_ws_floats(is224, dtype));
     } else {
       const int split = dtype == DT_BF16 ? wgrad_bf16_pick_split(M, c.Co, c.Ci, c.k * c.k) : wgrad_pick_split(M, c.Co, c.Ci, c.k * c.k);
       if (welems * split > wgp_max) wgp_max = welems * split;
@@ -562,33 +617,20 @@ static int conv_bn(Ctx& c, const ConvSpec& L, const float* X) {
   return bn_forward_coeffs(c, L);
 }
 
-// x/255 -> Normalize -> conv1 7x7/2 straight from the NCHW frames (csrc/stem.hip stem_fwd_kernel) -> BatchNorm + ReLU + MaxPool
+// x/255 -> Normalize -> conv1 7x7/2 straight from the NCHW frames (Stem, above) -> BatchNorm + ReLU + MaxPool
 static int stem_forward(Ctx& c, const float* x_nchw, const FrameSource* crop) {
   const Plan& P = c.P;
   const int F = P.F, dt = c.dt;
   const ConvSpec& L0 = P.convs[0];
-  // frames other than 224 x 224 (and 224 under r3m_debug_set_generic_stem) run the general stem kernels (stem_gen.hip)
   const bool gen = !crop && (P.H != 224 || P.W != 224 || g_generic_stem);
   c.R.stem_gen = gen ? 1 : 0;
+  const Stem stem(P, dt, gen, c.s);
   // normalised, channel-interleaved copy of the frames (0.6 MB/frame): read by the stem forward now and by its weight
   // gradient in backward (the caller's tensor may be gone by then)
   float* xn = c.arena + P.col_off;
-  if (gen) {
-    TRY(launch_stem_prep_gen(x_nchw, xn, F, P.H, P.W, dt, c.s));
-  } else if (crop) {
-    if (dt == DT_BF16) TRY(launch_stem_prep16_crop(*crop, xn, F, c.s));
-    else TRY(launch_stem_prep_crop(*crop, xn, F, c.s));
-  } else if (dt == DT_BF16) {
-    TRY(launch_stem_prep16(x_nchw, xn, F, c.s));
-  } else {
-    TRY(launch_stem_prep(x_nchw, xn, F, c.s));
-  }
-  const float* w = c.params + L0.w_off;
+  TRY(stem.prep(x_nchw, crop, xn));
   float* Y = c.arena + L0.Y_off;
-  float* stats = c.training ? c.partial() : nullptr;
-  if (gen) TRY(launch_stem_fwd_gen(xn, w, Y, stats, F, P.H, P.W, dt, c.s));
-  else if (dt == DT_BF16) TRY(launch_stem_fwd16(xn, w, Y, stats, F, c.s));
-  else TRY(launch_stem_fwd(xn, w, Y, stats, F, dt, c.s));
+  TRY(stem.forward(xn, c.params + L0.w_off, Y, c.training ? c.partial() : nullptr));
   TRY(bn_forward_coeffs(c, L0));
   // BatchNorm + ReLU + MaxPool in one pass over Y0
   return launch_bn_relu_maxpool_fwd(Y, c.coef(L0, 2), c.coef(L0, 3), c.arena + P.P0_off, reinterpret_cast<unsigned char*>(c.arena + P.amax_off),
@@ -955,18 +997,10 @@ static int stem_backward(Ctx& c, float* dx, int dx_accumulate, int work) {
     TRY(launch_bn_bwd_apply_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.coef(L0, 4), c.coef(L0, 5), Gc, F,
                                  P.H1, P.W1, 64, dt, c.s));
   TRY(c.R.side.join());   // the stem wgrad shares the split-K scratch with the side stream's wgrads
-  const float* xn = c.arena + P.col_off;
-  float* ws = c.arena + P.wgp_off;
-  if (work & BW_WGRAD) {
-    if (c.R.stem_gen) TRY(launch_stem_wgrad_gen(xn, Gc, c.grads + L0.w_off, ws, F, P.H, P.W, c.accumulate, dt, c.s));
-    else if (dt == DT_BF16) TRY(launch_stem_wgrad16(xn, Gc, c.grads + L0.w_off, ws, F, c.accumulate, c.s));
-    else TRY(launch_stem_wgrad(xn, Gc, c.grads + L0.w_off, ws, F, c.accumulate, dt, c.s));
-  }
+  const Stem stem(P, dt, c.R.stem_gen != 0, c.s);
+  if (work & BW_WGRAD) TRY(stem.wgrad(c.arena + P.col_off, Gc, c.grads + L0.w_off, c.arena + P.wgp_off, c.accumulate));
   // Gc = conv1's output gradient; the bf16 rounding of the normalised frames is taken as identity (as autocast does)
-  if (work & BW_DGRAD) {
-    if (c.R.stem_gen) TRY(launch_stem_input_grad_gen(Gc, dt, c.params + L0.w_off, dx, F, P.H, P.W, dx_accumulate, c.s));
-    else TRY(launch_stem_input_grad(Gc, dt, c.params + L0.w_off, dx, F, dx_accumulate, c.s));
-  }
+  if (work & BW_DGRAD) TRY(stem.input_grad(Gc, c.params + L0.w_off, dx, dx_accumulate));
   return 0;
 }
 

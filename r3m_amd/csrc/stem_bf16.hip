@@ -12,10 +12,8 @@
 //   wgrad   : dW[n][kh][j]   = sum_pixels dY[pixel][n] * patch[2*oy+kh][6*ox+j]
 //             contraction over pixels: dY arrives [pixel][n], i.e. K-strided -> ds_read_b64_tr_b16 (as wgrad_bf16_kernel); the
 //             patch operand is 8 pixels at a 12-byte stride -> eight ds_read_u16 per operand, packed in registers.
-#include "common.h"
-#include "conv_dev.h"
-#include "augment_dev.h"
-#include <cstring>
+// The pre-pass value sources, the GatherGemmParams fill, the profiling bracket and the reduce + unpack tail are stem_dev.h's.
+#include "stem_dev.h"
 
 namespace r3m {
 
@@ -28,14 +26,16 @@ size_t stem_xn16_bytes(int F) { return (size_t)F * XN_ROWS * XN_ROWB; }
 
 typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));
 
-// frames NCHW fp32 0..255 -> padded, normalised, channel-interleaved bf16 rows (the reference's (x/255 - mean)/std, then rounded)
-__global__ __launch_bounds__(256) void stem_prep16_kernel(const float* __restrict__ x, bf16_t* __restrict__ xn16, long long total) {
+// frames -> padded, normalised, channel-interleaved bf16 rows (the reference's (x/255 - mean)/std, then rounded); the value source
+// (stem_dev.h) is the NCHW fp32 frames, or the RAW clips through their crop boxes
+template <class Src>
+__global__ __launch_bounds__(256) void stem_prep16_kernel(const Src src, bf16_t* __restrict__ xn16, long long total) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // one thread per 8-element chunk
   if (i >= total) return;
   const int ch = (int)(i % (XN_ROW / 8));
   long long t = i / (XN_ROW / 8);
   const int r = (int)(t % XN_ROWS);
-  const long long f = t / XN_ROWS;
+  const auto px = src.frame(t / XN_ROWS);
   bf16x8 o;
   const int iy = r - 3;
 #pragma unroll
@@ -44,38 +44,17 @@ __global__ __launch_bounds__(256) void stem_prep16_kernel(const float* __restric
     float v = 0.f;
     if ((unsigned)iy < 224u && (unsigned)idx < 672u) {
       const int ix = idx / 3, c = idx - ix * 3;
-      v = stem_normalize(x[((f * 3 + c) * 224 + iy) * 224 + ix], c);
+      v = stem_normalize(px(c, iy, ix), c);
     }
     o[e] = (bf16_t)v;
   }
   *reinterpret_cast<bf16x8*>(xn16 + i * 8) = o;
 }
-
-// the same image built from the RAW clips through their crop boxes (see stem_prep_crop_kernel in stem.hip)
-template <typename T>
-__global__ __launch_bounds__(256) void stem_prep16_crop_kernel(const T* __restrict__ raw, const int* __restrict__ boxes,
-                                                                bf16_t* __restrict__ xn16, long long total, int Hi, int Wi, int fpb) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // one thread per 8-element chunk
-  if (i >= total) return;
-  const int ch = (int)(i % (XN_ROW / 8));
-  long long t = i / (XN_ROW / 8);
-  const int r = (int)(t % XN_ROWS);
-  const long long f = t / XN_ROWS;
-  const int* b = boxes + (f / fpb) * 4;
-  const int top = b[0], left = b[1], bh = b[2], bw = b[3];
-  bf16x8 o;
-  const int iy = r - 3;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int idx = ch * 8 + e - 9;
-    float v = 0.f;
-    if ((unsigned)iy < 224u && (unsigned)idx < 672u) {
-      const int ix = idx / 3, c = idx - ix * 3;
-      v = stem_normalize(bilinear_sample(raw + (f * 3 + c) * (long long)Hi * Wi, Wi, top, left, bh, bw, iy, ix, 0, 0, 224, 224), c);
-    }
-    o[e] = (bf16_t)v;
-  }
-  *reinterpret_cast<bf16x8*>(xn16 + i * 8) = o;
+template <class Src>
+static int launch_stem_prep16_body(const Src& src, void* xn16, int F, hipStream_t s, const char* what) {
+  const long long total = (long long)F * XN_ROWS * (XN_ROW / 8);
+  hipLaunchKernelGGL((stem_prep16_kernel<Src>), dim3(ceil_div(total, 256)), dim3(256), 0, s, src, reinterpret_cast<bf16_t*>(xn16), total);
+  return check_launch(what);
 }
 
 // x / d for a CONSTANT divisor, bit-identical to the IEEE quotient for d in {255, 0.229, 0.224, 0.225} and every float of
@@ -191,26 +170,18 @@ __global__ __launch_bounds__(256) void stem_prep16_crop_u8_kernel(const unsigned
 }
 
 int launch_stem_prep16_crop(const FrameSource& src, void* xn16, int F, hipStream_t s) {
-  const long long total = (long long)F * XN_ROWS * (XN_ROW / 8);
   if (src.is_u8 && src.Wi >= 4) {     // (narrower clips — never a frame — take the generic kernel below: same values)
     const long long tg = (long long)F * XN_ROWS * XN_GROUPS;
     hipLaunchKernelGGL(stem_prep16_crop_u8_kernel, dim3(ceil_div(tg, 256)), dim3(256), 0, s, static_cast<const unsigned char*>(src.frames),
                        src.boxes, reinterpret_cast<bf16_t*>(xn16), tg, src.Hi, src.Wi, src.frames_per_box);
-  } else if (src.is_u8)
-    hipLaunchKernelGGL((stem_prep16_crop_kernel<unsigned char>), dim3(ceil_div(total, 256)), dim3(256), 0, s,
-                       static_cast<const unsigned char*>(src.frames), src.boxes, reinterpret_cast<bf16_t*>(xn16), total, src.Hi, src.Wi,
-                       src.frames_per_box);
-  else
-    hipLaunchKernelGGL((stem_prep16_crop_kernel<float>), dim3(ceil_div(total, 256)), dim3(256), 0, s,
-                       static_cast<const float*>(src.frames), src.boxes, reinterpret_cast<bf16_t*>(xn16), total, src.Hi, src.Wi,
-                       src.frames_per_box);
-  return check_launch("stem_prep16_crop");
+    return check_launch("stem_prep16_crop");
+  }
+  if (src.is_u8) return launch_stem_prep16_body(StemCrop<unsigned char>(src), xn16, F, s, "stem_prep16_crop");
+  return launch_stem_prep16_body(StemCrop<float>(src), xn16, F, s, "stem_prep16_crop");
 }
 
 int launch_stem_prep16(const float* x_nchw, void* xn16, int F, hipStream_t s) {
-  const long long total = (long long)F * XN_ROWS * (XN_ROW / 8);
-  hipLaunchKernelGGL(stem_prep16_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, s, x_nchw, reinterpret_cast<bf16_t*>(xn16), total);
-  return check_launch("stem_prep16");
+  return launch_stem_prep16_body(StemFrames{x_nchw}, xn16, F, s, "stem_prep16");
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -292,14 +263,8 @@ __global__ __launch_bounds__(256) void stem_fwd16_kernel(const bf16_t* __restric
 }
 
 int launch_stem_fwd16(const void* xn16, const float* w147, void* y, float* stats, int F, hipStream_t s) {
-  GatherGemmParams p;
-  memset(&p, 0, sizeof p);
-  p.out = static_cast<float*>(y); p.stats = stats; p.dtype = DT_BF16;
-  p.M = F * 12544; p.Nc = 64; p.os = 1;
-  p.Hg = 112; p.Wg = 112; p.Ho = 112; p.Wo = 112;
-  const double flops = 2.0 * (double)p.M * 64.0 * 147.0;
-  prof_begin(KC_GEMM_NARROW, flops, p.M, 64, 147, 1, s);
-  prof_bytes((double)stem_xn16_bytes(F) + (double)p.M * 64 * 2);
+  const GatherGemmParams p = stem_fwd_params(y, stats, DT_BF16, F, 112, 112);
+  stem_prof_begin(KC_GEMM_NARROW, p.M, (double)stem_xn16_bytes(F), DT_BF16, s);
   const int ntiles = F * 49;
   const int grid = ntiles < 512 ? ntiles : 512;   // persistent blocks (2 per CU): the weight image is converted once per block
   static DynLdsOptIn optin_stats, optin_plain;
@@ -320,9 +285,7 @@ int launch_stem_fwd16(const void* xn16, const float* w147, void* y, float* stats
 constexpr int SW_DY = 112 * 128;                 // dY row image: [pixel][64 channels] bf16
 constexpr int SW_PATCH = 10 * 1024;              // 7 padded rows = 9856 B, staged as 10 x 1 KiB
 constexpr int SW_STAGE = SW_DY + SW_PATCH;       // 24 576 B
-constexpr int STEM_WG16_BLOCKS = 768;
-
-size_t stem_wgrad16_ws_floats() { return (size_t)STEM_WG16_BLOCKS * 64 * 224 + 64 * 224; }
+size_t stem_wgrad16_ws_floats() { return stem_ws_floats(STEM_WG16_BLOCKS, ST_DW16); }
 
 typedef short s16x4v __attribute__((ext_vector_type(4)));
 typedef short s16x8v __attribute__((ext_vector_type(8)));
@@ -400,7 +363,7 @@ __global__ __launch_bounds__(256) void stem_wgrad16_kernel(const bf16_t* __restr
     }
     st ^= 1;
   }
-  float* out = partial + (long long)blockIdx.x * 64 * 224;
+  float* out = partial + (long long)blockIdx.x * 64 * ST_DW16;
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     if (t < ntile) {
@@ -413,30 +376,15 @@ __global__ __launch_bounds__(256) void stem_wgrad16_kernel(const bf16_t* __restr
   }
 }
 
-// dw147[n][kh*21 + j] (+)= dw224[n][kh*32 + j]
-__global__ void stem_unpack_dw32_kernel(const float* __restrict__ dw224, float* __restrict__ dw147, int accumulate) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 64 * 147) return;
-  const int n = i / 147, k = i - n * 147;
-  const int kh = k / 21, j = k - kh * 21;
-  const float v = dw224[(n * 7 + kh) * 32 + j];
-  dw147[i] = accumulate ? dw147[i] + v : v;
-}
-
 int launch_stem_wgrad16(const void* xn16, const void* dY, float* dw147, float* ws, int F, int accumulate, hipStream_t s) {
   const int total_rows = F * 112;
   const int nb = total_rows < STEM_WG16_BLOCKS ? total_rows : STEM_WG16_BLOCKS;
-  const double flops = 2.0 * (double)F * 12544.0 * 64.0 * 147.0;
-  prof_begin(KC_WGRAD_NARROW, flops, F * 12544, 64, 147, 1, s);
-  prof_bytes((double)stem_xn16_bytes(F) + (double)F * 12544 * 64 * 2);
+  stem_prof_begin(KC_WGRAD_NARROW, F * 12544, (double)stem_xn16_bytes(F), DT_BF16, s);
   hipLaunchKernelGGL(stem_wgrad16_kernel, dim3(nb), dim3(256), 0, s, static_cast<const bf16_t*>(xn16), static_cast<const bf16_t*>(dY), ws,
                      total_rows);
   prof_end(s);
   if (int e = check_launch("stem_wgrad16")) return e;
-  float* dw224 = ws + (size_t)STEM_WG16_BLOCKS * 64 * 224;
-  if (int e = launch_wgrad_reduce(ws, dw224, 64 * 224, nb, 0, s)) return e;
-  hipLaunchKernelGGL(stem_unpack_dw32_kernel, dim3(ceil_div(64 * 147, 256)), dim3(256), 0, s, dw224, dw147, accumulate);
-  return check_launch("stem_unpack_dw32");
+  return stem_wgrad_finish<ST_DW16, 32>(ws, nb, STEM_WG16_BLOCKS, dw147, accumulate, s, "stem_unpack_dw32");
 }
 
 }  // namespace r3m

@@ -16,31 +16,16 @@
 // wave, no padding on M), stages the 3 or 4 kernel rows of W it needs in LDS, and reads its A operands straight from dZ: per (kernel
 // row, M tile) each lane loads the 32 consecutive channels it owns of one pixel (one whole cache line; a first version that walked
 // the channels in 4-channel steps across all 7 tiles re-fetched every line 8 times and ran 11x slower than the stem forward),
-// prefetched one tile ahead of the 32 MFMAs that consume it (B comes from LDS, one read per MFMA).
-#include "common.h"
-#include "conv_dev.h"
+// prefetched one tile ahead of the 32 MFMAs that consume it (B comes from LDS, one read per MFMA). The weight staging, that MFMA step,
+// the bf16 widening and the per-channel scale are stem_dev.h's, shared with the general form (stem_gen.hip stem_dgrad_gen_kernel).
+#include "stem_dev.h"
 
 namespace r3m {
 
 namespace {
 
-constexpr int SD_WH = 1056;             // LDS floats per (kh, channel half): 32 channels x 32 columns + 32 (the two halves of a wave
-                                        // read banks 32 apart: conflict-free)
-constexpr int SD_WK = 2 * SD_WH;        // per kernel row
 constexpr int SD_U = 224 * 21;          // LDS floats of one wave's U (2 rows x 112 pixels x 21 columns)
 constexpr int SD_LDS = 4 * SD_U > 4 * SD_WK ? 4 * SD_U : 4 * SD_WK;   // U aliases the weights (dead after the K loop)
-
-template <class T> struct SdLoad;
-template <> struct SdLoad<float> {
-  static __device__ __forceinline__ f32x4 load4(const float* p) { return ldg4(p); }
-};
-template <> struct SdLoad<bf16_t> {
-  static __device__ __forceinline__ f32x4 load4(const bf16_t* p) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                 __uint_as_float(u.y & 0xffff0000u)};
-  }
-};
 
 template <int P, class T>
 __device__ __forceinline__ void stem_dgrad_item(const T* __restrict__ dz, const float* __restrict__ w, float* __restrict__ dx,
@@ -48,11 +33,7 @@ __device__ __forceinline__ void stem_dgrad_item(const T* __restrict__ dz, const 
   constexpr int NK = P ? 4 : 3;          // kernel rows with h + 3 - kh even: kh = (1 - P) + 2 kk
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lrow = lane & 31, lh = lane >> 5;
-  for (int i = tid; i < NK * 64 * 32; i += 256) {
-    const int n = i & 31, co = (i >> 5) & 63, kk = i >> 11;
-    const int kh = (1 - P) + 2 * kk;
-    smem[kk * SD_WK + (co >> 5) * SD_WH + (co & 31) * 32 + n] = n < 21 ? w[co * 147 + kh * 21 + n] : 0.f;
-  }
+  stem_dgrad_weights<P>(smem, w);
   // this wave's two input rows: h_r = 2 (2q + r) + P, q = 4 g + wave (0..55)
   const int q = 4 * g + wave;
   int h_of[2];
@@ -74,7 +55,7 @@ __device__ __forceinline__ void stem_dgrad_item(const T* __restrict__ dz, const 
     const bool ok = (unsigned)oy < 112u;
     const T* src = dz + ((f * 112 + (ok ? oy : 0)) * 112 + ox_t[t]) * 64 + lh * 32;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) a[j] = ok ? SdLoad<T>::load4(src + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 8; ++j) a[j] = ok ? stem_load4(src + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
   };
   f32x16 acc[7];
 #pragma unroll
@@ -85,13 +66,13 @@ __device__ __forceinline__ void stem_dgrad_item(const T* __restrict__ dz, const 
   load_a(cur, 0, 0);
   __syncthreads();                       // weights staged
   for (int kk = 0; kk < NK; ++kk) {
-    const float* wb = smem + kk * SD_WK + lh * SD_WH + lrow;   // B: W[co = lh*32 + i][kh][n = lane & 31] at wb[32 i]
+    const float* wb = smem + kk * SD_WK + lh * SD_WH + lrow;
 #pragma unroll
     for (int t = 0; t < 7; ++t) {
       if (t < 6) load_a(nxt, kk, t + 1);
       else if (kk + 1 < NK) load_a(nxt, kk + 1, 0);
 #pragma unroll
-      for (int i = 0; i < 32; ++i) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(cur[i >> 2][i & 3], wb[32 * i], acc[t], 0, 0, 0);
+      for (int j = 0; j < 8; ++j) acc[t] = stem_dgrad_mfma4(cur[j], wb + 128 * j, acc[t]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) cur[j] = nxt[j];
     }
@@ -117,7 +98,6 @@ __device__ __forceinline__ void stem_dgrad_item(const T* __restrict__ dz, const 
       const int h = h_of[r];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float scale = c == 0 ? 1.f / (255.f * 0.229f) : (c == 1 ? 1.f / (255.f * 0.224f) : 1.f / (255.f * 0.225f));
         f32x4 v;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -128,7 +108,7 @@ __device__ __forceinline__ void stem_dgrad_item(const T* __restrict__ dz, const 
             const int ox = (wcol + 3 - kw) >> 1;
             if ((unsigned)ox < 112u) sum += Ur[ox * 21 + kw * 3 + c];
           }
-          v[j] = sum * scale;
+          v[j] = sum * stem_dgrad_scale(c);
         }
         f32x4* o = reinterpret_cast<f32x4*>(dx + ((f * 3 + c) * 224 + h) * 224 + w0);
         if (accumulate) v += *o;

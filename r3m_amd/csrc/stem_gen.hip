@@ -8,34 +8,29 @@
 // value rounded once). Both precisions run the exact fp32 MFMA (v_mfma_f32_32x32x2_f32): with bf16 operands every product is exact in
 // fp32, so the bf16 path computes what a bf16 MFMA with fp32 accumulation computes, up to the order of the fp32 sums.
 //
-// Forward: the 224 kernel's geometry (stem.hip stem_fwd_kernel) with the row width and the tile's row span made general. A tile is 256
+// Forward: the 224 kernel's geometry (stem.hip stem_fwd_kernel; the K loop is stem_dev.h's, shared with it; the weight-image fill is
+// this kernel's own flat loop) with the row width and the tile's row span made general. A tile is 256
 // consecutive output pixels of the flattened [F, Ho, Wo] index; it may span several output rows, and the end of one frame and the start
 // of the next (Ho * Wo >= 256 for H, W >= 32, so at most two frames). It stages, per frame part, the 2 r + 5 input rows its r output
 // rows touch, at a padded width of (W + 6) * 3 floats (9 leading zeros, zeros behind the data): the MFMA A operand of pixel (oy, ox)
 // for k = (kh, j) is patch[2 (oy - oy_first) + kh][6 ox + j] — a per-lane base plus an immediate, no vector work in the K loop.
 // Pixels past M read a valid pixel and their accumulators are cleared after the K loop (the BatchNorm partials then see zeros).
 //
-// Weight gradient: stem.hip stem_wgrad_kernel with one output row of Wo pixels per iteration (K = pixels, rounded up to even with zero
-// dY), 7 staged input rows at a row stride == 22 (mod 32) as ST_PSW documents.
+// Weight gradient: stem_dev.h's lane geometry, row GEMM and partial layout (shared with stem.hip stem_wgrad_kernel, whose workspace
+// and block count it takes) with one output row of Wo pixels per iteration (K = pixels, rounded up to even with zero dY), 7 staged
+// input rows at a row stride == 22 (mod 32) as ST_PSW documents.
 //
-// Input gradient: stem_dgrad.hip's per-row GEMM (M = pixels of one dZ row, N = 21 (kw, c) columns, K = kernel rows x 64 channels)
-// with M tails, followed by the col2im gather out of LDS; one wave per input row, four rows of one parity per block.
-#include "common.h"
-#include "conv_dev.h"
-#include "augment_dev.h"
+// Input gradient: stem_dgrad.hip's per-row GEMM (M = pixels of one dZ row, N = 21 (kw, c) columns, K = kernel rows x 64 channels; weight
+// staging, MFMA step and scale in stem_dev.h) with M tails, followed by the col2im gather out of LDS; one wave per input row, four rows
+// of one parity per block.
+#include "stem_dev.h"
 #include <algorithm>
-#include <cstring>
 
 namespace r3m {
 
 namespace {
 
-constexpr int SG_KS = 155;             // LDS weight row stride (odd: conflict-free fragment reads), as ST_KS
-constexpr int SG_K = 154;              // 7 kernel rows x 22
 constexpr int SG_EPI = 4 * 32 * 68;    // floats the shared epilogue's slabs take (gg_epilogue<256, 64, 4, 1>)
-constexpr int SG_WG_BLOCKS = 512;      // weight-gradient blocks: the partial workspace is stem.hip's stem_wgrad_ws_floats()
-constexpr int SD_WH = 1056;            // input gradient: LDS floats per (kernel row, channel half), as stem_dgrad.hip
-constexpr int SD_WK = 2 * SD_WH;
 
 struct StemGeo {
   int F, H, W, Ho, Wo;
@@ -66,12 +61,13 @@ static StemGeo stem_geo(int F, int H, int W) {
   g.wl_off = (g.wl_off + 3) & ~3;
   return g;
 }
-static int stem_fwd_lds_bytes(const StemGeo& g) { return (g.wl_off + 64 * SG_KS) * 4; }
+static int stem_fwd_lds_bytes(const StemGeo& g) { return (g.wl_off + 64 * ST_KS) * 4; }
 static int stem_wgrad_psw(const StemGeo& g) { return sg_stride(std::max(3 * g.W + 9, 6 * g.Wo2 + 16), 22); }
 static int stem_wgrad_lds_bytes(const StemGeo& g) { return (g.Wo2 * 64 + 7 * stem_wgrad_psw(g)) * 4; }
 static int stem_dgrad_lds_bytes(const StemGeo& g) { return (4 * SD_WK + 4 * g.Wo * 21) * 4; }
 
-// ---- pre-pass: NCHW fp32 0..255 -> xn[f][iy][ix*3 + c] (the reference's (x/255 - mean)/std with IEEE divisions) ----
+// ---- pre-pass: NCHW fp32 0..255 -> xn[f][iy][ix*3 + c] (the reference's (x/255 - mean)/std with IEEE divisions). Its own kernel, not an
+// instantiation of stem_dev.h's stem_prep_kernel: that one measured 2 % slower here (profiles/stem_share_ab.txt) ----
 template <class OT>
 __global__ __launch_bounds__(256) void stem_prep_gen_kernel(const float* __restrict__ x, OT* __restrict__ xn, int H, int W, long long total) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // one thread per (f, iy, ix)
@@ -93,17 +89,16 @@ __global__ __launch_bounds__(256) void stem_fwd_gen_kernel(const IT* __restrict_
   float* patch = smem;                 // also the epilogue's scratch (SG_EPI floats <= wl_off): the weights behind it survive
   float* wl = smem + g.wl_off;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < 64 * SG_K; i += 256) {
-    const int n = i / SG_K, k = i - n * SG_K;
+  for (int i = tid; i < 64 * ST_K; i += 256) {      // this kernel's own fill (not shared with stem.hip: one flat loop)
+    const int n = i / ST_K, k = i - n * ST_K;
     const int kh = k / 22, j = k - kh * 22;
     float v = j < 21 ? w[n * 147 + kh * 21 + j] : 0.f;
     if (sizeof(IT) == 2) v = static_cast<float>(static_cast<bf16_t>(v));   // bf16 plans: the bf16 weight operand
-    wl[n * SG_KS + k] = v;
+    wl[n * ST_KS + k] = v;
   }
   const int lrow = lane & 31, lh = lane >> 5;
   int b_base[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) b_base[t] = (t * 32 + lrow) * SG_KS + lh;
+  stem_fwd_b_base(b_base, lrow, lh);
   const int HWo = g.Ho * g.Wo;
   const int PS = g.PS;
   const int rowlen = 3 * g.W;
@@ -144,22 +139,7 @@ __global__ __launch_bounds__(256) void stem_fwd_gen_kernel(const IT* __restrict_
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
 #pragma unroll
-    for (int kh = 0; kh < 7; ++kh) {
-      const float* pa0 = patch + a_base[0] + kh * PS;
-      const float* pa1 = patch + a_base[1] + kh * PS;
-#pragma unroll
-      for (int jp = 0; jp < 11; ++jp) {
-        const float a[2] = {pa0[2 * jp], pa1[2 * jp]};
-        float b[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) b[t] = wl[b_base[t] + kh * 22 + 2 * jp];
-#pragma unroll
-        for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-          for (int tn = 0; tn < 2; ++tn)
-            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm], b[tn], acc[tm][tn], 0, 0, 0);
-      }
-    }
+    for (int kh = 0; kh < 7; ++kh) stem_fwd_krow(patch + a_base[0] + kh * PS, patch + a_base[1] + kh * PS, wl, b_base, kh, acc);
     if (m0 + 256 > p.M) {              // the last tile: rows past M must hold zeros (BatchNorm partials)
 #pragma unroll
       for (int tm = 0; tm < 2; ++tm)
@@ -181,20 +161,9 @@ __global__ __launch_bounds__(256) void stem_wgrad_gen_kernel(const IT* __restric
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* dys = smem;                   // [Wo2][64]
   float* patch = smem + g.Wo2 * 64;    // 7 rows at stride PSW
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 1, wj = wave & 1;
-  const int lrow = lane & 31, lh = lane >> 5;
-  const int jt0 = wj ? 3 : 0;
-  const int a_base = lh * 64 + wi * 32 + lrow;
-  int b_base[3];
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    int j = (jt0 + t) * 32 + lrow;
-    if (j >= SG_K) j = 0;                       // columns 154..159 (and the unused third tile of the second wave column)
-    const int kh = j / 22, jj = j - kh * 22;
-    b_base[t] = kh * PSW + jj + 6 * lh;
-  }
-  f32x16 acc[3], tot[3];
+  const int tid = threadIdx.x;
+  const StemWgLane L = stem_wg_lane<0>(PSW);
+  f32x16 tot[3];
 #pragma unroll
   for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -220,72 +189,19 @@ __global__ __launch_bounds__(256) void stem_wgrad_gen_kernel(const IT* __restric
       *reinterpret_cast<f32x4*>(dys + i * 4) = v;
     }
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-    if (wj == 0) {
-      for (int q = 0; q < npairs; ++q) {
-        const float a = dys[a_base + q * 128];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, patch[b_base[t] + q * 12], acc[t], 0, 0, 0);
-      }
-    } else {
-      for (int q = 0; q < npairs; ++q) {
-        const float a = dys[a_base + q * 128];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, patch[b_base[t] + q * 12], acc[t], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 3; ++t) tot[t] += acc[t];
+    stem_wg_row<0>(dys, patch, L, npairs, tot);
   }
-  float* out = partial + (long long)blockIdx.x * 64 * 160;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    if (t == 2 && wj) continue;                 // the second wave column owns k tiles 3 and 4 only
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      out[co * 160 + (jt0 + t) * 32 + lrow] = tot[t][r];
-    }
-  }
-}
-
-// dw147[co][kh*21 + j] (+)= dw160[co][kh*22 + j]
-__global__ void stem_gen_unpack_kernel(const float* __restrict__ dw160, float* __restrict__ dw147, int accumulate) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 64 * 147) return;
-  const int co = i / 147, k = i - co * 147;
-  const int kh = k / 21, j = k - kh * 21;
-  const float v = dw160[co * 160 + kh * 22 + j];
-  dw147[i] = accumulate ? dw147[i] + v : v;
+  stem_wg_store(partial, L, tot);
 }
 
 // ---- input gradient: one wave per input row h (four rows of parity P per block) ----
-template <class T> struct SgLoad;
-template <> struct SgLoad<float> {
-  static __device__ __forceinline__ f32x4 load4(const float* p) { return ldg4(p); }
-};
-template <> struct SgLoad<bf16_t> {
-  static __device__ __forceinline__ f32x4 load4(const bf16_t* p) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                 __uint_as_float(u.y & 0xffff0000u)};
-  }
-};
-
 template <int P, class T>
 __device__ __forceinline__ void stem_dgrad_gen_item(const T* __restrict__ dz, const float* __restrict__ w, float* __restrict__ dx,
                                                     const StemGeo& g, int f, int grp, int accumulate, float* smem) {
   constexpr int NK = P ? 4 : 3;          // kernel rows with h + 3 - kh even: kh = (1 - P) + 2 kk
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lrow = lane & 31, lh = lane >> 5;
-  for (int i = tid; i < NK * 64 * 32; i += 256) {
-    const int n = i & 31, co = (i >> 5) & 63, kk = i >> 11;
-    const int kh = (1 - P) + 2 * kk;
-    smem[kk * SD_WK + (co >> 5) * SD_WH + (co & 31) * 32 + n] = n < 21 ? w[co * 147 + kh * 21 + n] : 0.f;
-  }
+  stem_dgrad_weights<P>(smem, w);
   float* U = smem + 4 * SD_WK + wave * g.Wo * 21;
   const int h = 2 * (4 * grp + wave) + P;
   const bool valid = h < g.H;            // wave-uniform
@@ -305,10 +221,10 @@ __device__ __forceinline__ void stem_dgrad_gen_item(const T* __restrict__ dz, co
         const T* src = dz + (((long long)f * g.Ho + (ok ? oy : 0)) * g.Wo + (ok ? ox : 0)) * 64 + lh * 32;
         f32x4 a[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = ok ? SgLoad<T>::load4(src + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
-        const float* wb = smem + kk * SD_WK + lh * SD_WH + lrow;   // B: W[co = lh*32 + i][kh][n = lane & 31] at wb[32 i]
+        for (int j = 0; j < 8; ++j) a[j] = ok ? stem_load4(src + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const float* wb = smem + kk * SD_WK + lh * SD_WH + lrow;
 #pragma unroll
-        for (int i = 0; i < 32; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i >> 2][i & 3], wb[32 * i], acc, 0, 0, 0);
+        for (int j = 0; j < 8; ++j) acc = stem_dgrad_mfma4(a[j], wb + 128 * j, acc);
       }
       if (lrow < 21) {
 #pragma unroll
@@ -324,14 +240,13 @@ __device__ __forceinline__ void stem_dgrad_gen_item(const T* __restrict__ dz, co
     for (int wcol = lane; wcol < g.W; wcol += 64) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float scale = c == 0 ? 1.f / (255.f * 0.229f) : (c == 1 ? 1.f / (255.f * 0.224f) : 1.f / (255.f * 0.225f));
         float sum = 0.f;
         for (int kw = (wcol + 1) & 1; kw < 7; kw += 2) {
           const int ox = (wcol + 3 - kw) >> 1;
           if ((unsigned)ox < (unsigned)g.Wo) sum += U[ox * 21 + kw * 3 + c];
         }
         float* o = dx + (((long long)f * 3 + c) * g.H + h) * g.W + wcol;
-        const float v = sum * scale;
+        const float v = sum * stem_dgrad_scale(c);
         *o = accumulate ? *o + v : v;
       }
     }
@@ -377,17 +292,11 @@ int launch_stem_prep_gen(const float* x_nchw, float* xn, int F, int H, int W, in
 int launch_stem_fwd_gen(const float* xn, const float* w147, void* y, float* stats, int F, int H, int W, int dt, hipStream_t s) {
   if (int e = stem_gen_check(F, H, W)) return e;
   const StemGeo g = stem_geo(F, H, W);
-  GatherGemmParams p;
-  memset(&p, 0, sizeof p);
-  p.out = static_cast<float*>(y); p.stats = stats; p.dtype = dt;
-  p.M = F * g.Ho * g.Wo; p.Nc = 64; p.os = 1;
-  p.Hg = g.Ho; p.Wg = g.Wo; p.Ho = g.Ho; p.Wo = g.Wo;
+  const GatherGemmParams p = stem_fwd_params(y, stats, dt, F, g.Ho, g.Wo);
   const int ntiles = ceil_div(p.M, 256);
   const int grid = ntiles < 512 ? ntiles : 512;
   const int lds = stem_fwd_lds_bytes(g);
-  const double flops = 2.0 * (double)p.M * 64.0 * 147.0;
-  prof_begin(KC_GEMM_NARROW, flops, p.M, 64, 147, 1, s);
-  prof_bytes((double)F * H * W * 3 * (dt == DT_BF16 ? 2 : 4) + (double)p.M * 64 * (dt == DT_BF16 ? 2 : 4));
+  stem_prof_begin(KC_GEMM_NARROW, p.M, (double)F * H * W * 3 * (dt == DT_BF16 ? 2 : 4), dt, s);
 #define SG_FWD(E, IT, OT)                                                                                                     \
   do {                                                                                                                        \
     static DynLdsOptIn oi;                                                                                                    \
@@ -413,11 +322,9 @@ int launch_stem_wgrad_gen(const float* xn, const void* dY, float* dw147, float* 
   const StemGeo g = stem_geo(F, H, W);
   const int PSW = stem_wgrad_psw(g);
   const int total_rows = F * g.Ho;
-  const int nb = total_rows < SG_WG_BLOCKS ? total_rows : SG_WG_BLOCKS;
+  const int nb = total_rows < STEM_WG_BLOCKS ? total_rows : STEM_WG_BLOCKS;
   const int lds = stem_wgrad_lds_bytes(g);
-  const double flops = 2.0 * (double)F * g.Ho * g.Wo * 64.0 * 147.0;
-  prof_begin(KC_WGRAD_NARROW, flops, F * g.Ho * g.Wo, 64, 147, 1, s);
-  prof_bytes((double)F * H * W * 3 * (dt == DT_BF16 ? 2 : 4) + (double)F * g.Ho * g.Wo * 64 * (dt == DT_BF16 ? 2 : 4));
+  stem_prof_begin(KC_WGRAD_NARROW, F * g.Ho * g.Wo, (double)F * H * W * 3 * (dt == DT_BF16 ? 2 : 4), dt, s);
 #define SG_WG(IT, T)                                                                                                          \
   do {                                                                                                                        \
     static DynLdsOptIn oi;                                                                                                    \
@@ -430,12 +337,9 @@ int launch_stem_wgrad_gen(const float* xn, const void* dY, float* dw147, float* 
 #undef SG_WG
   prof_end(s);
   if (int e = check_launch("stem_wgrad_gen")) return e;
-  float* dw160 = ws + (size_t)SG_WG_BLOCKS * 64 * 160;
-  if (int e = launch_wgrad_reduce(ws, dw160, 64 * 160, nb, 0, s)) return e;
-  hipLaunchKernelGGL(stem_gen_unpack_kernel, dim3(ceil_div(64 * 147, 256)), dim3(256), 0, s, dw160, dw147, accumulate);
-  return check_launch("stem_gen_unpack");
+  return stem_wgrad_finish<ST_DW, 22>(ws, nb, STEM_WG_BLOCKS, dw147, accumulate, s, "stem_gen_unpack");
 }
-size_t stem_wgrad_gen_ws_floats() { return (size_t)SG_WG_BLOCKS * 64 * 160 + 64 * 160; }
+size_t stem_wgrad_gen_ws_floats() { return stem_ws_floats(STEM_WG_BLOCKS, ST_DW); }
 
 int launch_stem_input_grad_gen(const void* dz, int dt, const float* w147, float* dx, int F, int H, int W, int accumulate, hipStream_t s) {
   if (int e = stem_gen_check(F, H, W)) return e;

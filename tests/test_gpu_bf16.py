@@ -74,7 +74,7 @@ def test_conv_bf16_is_transpose_safe(hip):
     torch.testing.assert_close(dwd.cpu().view(Co, Ci).double(), dw_ref, rtol=0, atol=0)
 
 
-@pytest.mark.parametrize("Fr", [1, 3])
+@pytest.mark.parametrize("Fr", [1, 3, 11])   # 11: every persistent loop of the 224 kernels takes a second trip
 def test_stem_bf16_out(hip, Fr):
     """stem conv: fp32 frames / weights in (exact fp32 MFMA), bf16 activation out; wgrad reads a bf16 dY"""
     x = torch.floor(rnd((Fr, 3, 224, 224), 5, 0.0, 256.0)).clamp(0, 255)
@@ -502,7 +502,7 @@ def test_train_steps_bf16_track_fp32(hip):
         assert abs(a - b) <= 5e-2 * abs(a), (losses["fp32"], losses["bf16"])
 
 
-@pytest.mark.parametrize("Fr", [1, 3])
+@pytest.mark.parametrize("Fr", [1, 3, 11])   # 11: every persistent loop of the 224 kernels takes a second trip
 def test_stem_on_bf16_mfma(hip, Fr):
     """the bf16 plan's stem: padded bf16 image of the normalised frames -> conv 7x7/2 forward (+ BatchNorm partials) and
     weight gradient on the bf16 MFMA, vs float64 on the bf16-rounded operands"""

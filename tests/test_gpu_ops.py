@@ -65,7 +65,7 @@ def test_conv_is_transpose_safe(hip):
     torch.testing.assert_close(nchw(yd.cpu()), y_ref, rtol=1e-6, atol=1e-5)
 
 
-@pytest.mark.parametrize("Fr", [1, 3])
+@pytest.mark.parametrize("Fr", [1, 3, 11])   # 11: every persistent loop of the 224 kernels takes a second trip
 def test_stem_direct_fwd_wgrad(hip, Fr):
     """The engine's stem: /255 -> Normalize -> conv 7x7/2 p3 straight from NCHW frames, forward (+BN partials) and wgrad."""
     x = torch.floor(rnd((Fr, 3, 224, 224), 5, 0.0, 256.0)).clamp(0, 255)
