@@ -66,6 +66,16 @@ int r3m_debug_conv_route(int N, int H, int W, int Ci, int Co, int k, int stride,
    output from the convolution itself; 0 when the engine runs that block's unfused sequence instead. r3m_debug_conv_route with the same
    flags (dgrad = 0) reports the route the fused launch takes. */
 int r3m_debug_conv_fuses_affine(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int flags, int dtype);
+/* Diagnostic, runs without a GPU: what the weight gradient of one convolution behind the stem (r3m_conv2d_wgrad_dt, the engine's
+   backward) runs -- the plan of csrc/wgrad.hip wgrad_plan, the one dispatch of that kernel family; nothing is launched. out[0..8]:
+     0  route: fp32 40 = one tap per block, rows linear in m (1x1 / stride 1), 41 = one tap per block, gathered rows, 42 = one kernel
+        row (three taps) per block, 43 = kernel row from a shared input window (3x3 / stride 1 / pad 1); bf16 50 = one tap per block,
+        51 = one kernel row per block, 52 = all nine taps per block
+     1  tile width (128 | 64)     2  rows per K step     3  route 51: 1 = the division-free coordinate walk
+     4  split-K factor (the workspace is split * Co * k * k * Ci floats)     5  GEMM rows per split
+     6  ci tiles     7  blocks per split (the grid is out[7] * out[4] blocks)     8  dynamic LDS bytes (0: static LDS)
+   Returns the number of ints written (9), -1 on error (cap < 9). */
+int r3m_debug_wgrad_route(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int dtype, int* out, int cap);
 /* Diagnostic, runs without a GPU: the launch geometry the streaming BatchNorm passes of csrc/bn.hip pick for a [rows][C] tensor of `dtype` (C a
    power of two >= 4) -- computed by the helpers the launchers themselves call, nothing is launched. out[0..13]:
      0-2   forward apply (r3m_bn_act_fwd_dt): elements per lane (4 | 8), items per block (span: 256 | 1024), blocks

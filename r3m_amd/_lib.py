@@ -30,6 +30,7 @@ SIGNATURES = {
     "r3m_debug_set_conv3x3_bf16": (c_i, [c_i]),
     "r3m_debug_set_fused_inference": (c_i, [c_i]),
     "r3m_debug_conv_route": (c_i, [c_i] * 12 + [C.POINTER(c_i), c_i]),
+    "r3m_debug_wgrad_route": (c_i, [c_i] * 9 + [C.POINTER(c_i), c_i]),
     "r3m_debug_conv_fuses_affine": (c_i, [c_i] * 10),
     "r3m_debug_bn_geometry": (c_i, [c_ll, c_i, c_i, C.POINTER(c_i), c_i]),
     "r3m_profile_enable": (None, [c_i]),

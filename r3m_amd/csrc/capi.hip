@@ -160,6 +160,13 @@ int r3m_debug_conv_route(int N, int H, int W, int Ci, int Co, int k, int stride,
   const int n = r3m::gg_route_record_end();
   return rc ? -1 : n;
 }
+int r3m_debug_wgrad_route(int N, int H, int W, int Ci, int Co, int k, int stride, int pad, int dtype, int* out, int cap) {
+  if (!out || cap < 9) { r3m::set_last_error("debug_wgrad_route: the output buffer needs 9 ints"); return -1; }
+  const r3m::WgradPlan r = r3m::conv_wgrad_plan({N, H, W, Ci, Co, k, stride, pad}, dtype);
+  const int v[9] = {r.route, r.tile, r.bk, r.fast, r.split, r.rows_per_split, r.tilesN, r.gx, r.lds_bytes};
+  for (int i = 0; i < 9; ++i) out[i] = v[i];
+  return 9;
+}
 void r3m_profile_enable(int on) {
   std::lock_guard<std::mutex> lk(g_prof_mu);
   g_prof_on.store(on != 0, std::memory_order_relaxed);

@@ -110,12 +110,12 @@ struct WgradParams {
   int Ho, Wo, Co;
   int KH, KW, stride, pad;
   int M;               // N*Ho*Wo
-  int rows_per_split;  // multiple of 32
   int simple_rows;     // 1x1 stride-1: X row offset = m*Ci
-  int tilesN;          // ceil(Ci / BN)
-  int interleave;      // 1: spread the next K step's DMA pieces between this step's MFMAs (set by the launcher)
   int dtype;           // DT_F32 / DT_BF16 storage of dY and X (out is always fp32)
-  int gx;              // (co tile, ci tile, tap) blocks per split; the launch is 1-D: gx * splitK blocks
+  // copied from the launch's WgradPlan by launch_wgrad:
+  int rows_per_split;  // multiple of 32
+  int tilesN;          // ceil(Ci / BN)
+  int gx;              // (co tile, ci tile, tap group) blocks per split; the launch is 1-D: gx * split blocks
   int xcd;             // 1: XCD-aware block order — all blocks of one split (same dY / X rows) run on ONE XCD and share its L2
   int debug;           // timing probes (probe builds, R3M_WG_DEBUG: 1 no DMA at all, 2 no X pieces, 4 no dY pieces); 0 in production
 };
@@ -142,15 +142,37 @@ bool pw_gemm_eligible(const GatherGemmParams& p);
 int pw_gemm_form(const GatherGemmParams& p);            // 0 none, 1 pointwise, 2 gather, 3 gather with strided output rows
 int launch_pw_gemm(const GatherGemmParams& p, hipStream_t s);
 
-// ---- launchers (wgrad.hip): fp32 weight gradient ----
-int launch_wgrad(const WgradParams& p, int splitK, hipStream_t s);
-int wgrad_pick_split(int M, int Co, int Ci, int T);
+// ---- the weight gradients behind the stem (wgrad.hip, wgrad_win.hip, wgrad_bf16.hip; shared device code: wgrad_dev.h) ----
+// One value per kernel form; public (r3m_debug_wgrad_route), numbered apart from the conv routes (1 - 33).
+enum : int {
+  WG_TAPS_SIMPLE = 40,   // fp32, one tap per block, rows linear in m (1x1 / stride 1)          wgrad_glds_kernel<.., 32, 1, 0, 1>
+  WG_TAPS_GATHER = 41,   // fp32, one tap per block, gathered rows (strided, 7x7, ...)          wgrad_glds_kernel<.., 32, 1, IL, 0>
+  WG_ROWS        = 42,   // fp32, one kernel row (three taps) per block                         wgrad_glds_kernel<.., 16, 3, IL>
+  WG_WINDOW      = 43,   // fp32 3x3 "same": kernel row from one shared input window            wgrad_rowwin_kernel
+  WG16_TAPS      = 50,   // bf16, one tap per block                                             wgrad_bf16_kernel<.., bk>
+  WG16_ROWS      = 51,   // bf16, one kernel row per block, 128 x 128 tile                      wgrad_bf16_kernel<128, 128, 32, 3, fast>
+  WG16_ALL_TAPS  = 52,   // bf16 3x3 "same" at widths that are multiples of 8: nine taps        wgrad3x3_halo_bf16_kernel
+};
+// What one launch runs. Template variants inside a form follow from tile (128: IL = 1 on the fp32 gathered / kernel-row forms), bk, fast.
+struct WgradPlan {
+  int route, tile, bk;           // kernel form, tile width (128 | 64), rows per K step
+  int fast;                      // WG16_ROWS: the division-free coordinate walk is enough
+  int split, rows_per_split;     // split-K factor, GEMM rows per split
+  int tilesN, gx;                // ci tiles, blocks per split: the grid is gx * split
+  int lds_bytes;                 // dynamic LDS (0: the kernel's LDS is static)
+  int xcd, debug;                // probe-build switches handed to the kernels (WgradParams)
+};
+WgradPlan wgrad_plan(const WgradParams& p);   // pure: geometry + dtype (+ the switches in probe builds); launches nothing, checks nothing
+int launch_wgrad(const WgradParams& p, const WgradPlan& r, hipStream_t s);   // requirements -> switch (r.route) -> one profiler / check_launch tail
 int launch_wgrad_reduce(const float* partial, float* dW, long long n, int splitK, int accumulate, hipStream_t s);
 int wgrad_debug_occupancy(int* out);     // debug_occupancy's fourth output
-
-// ---- launchers (wgrad_win.hip): 3x3 / stride 1 / pad 1, fp32, whole 64- or 128-wide tiles ----
-bool wgrad_rowwin_eligible(const WgradParams& p);
-int launch_wgrad_rowwin(WgradParams& p, int splitK, hipStream_t s);
+// predicates (called from wgrad_plan only) and "launch this instantiation with this plan" helpers (called from launch_wgrad only)
+bool wgrad_rowwin_eligible(const WgradParams& p);      // wgrad_win.hip: 3x3 / stride 1 / pad 1, fp32, whole 64- or 128-wide tiles
+int wgrad_rowwin_lds_bytes(int tile);
+int launch_wgrad_rowwin(const WgradParams& p, const WgradPlan& r, hipStream_t s);
+bool wgrad_halo_eligible(const WgradParams& p);        // wgrad_bf16.hip: 3x3 / stride 1 / pad 1 at widths that are multiples of 8
+int wgrad_halo_lds_bytes(int W);
+int launch_wgrad_bf16(const WgradParams& p, const WgradPlan& r, hipStream_t s);   // the three bf16 forms
 
 // ---- launchers (conv_bf16.hip): bf16 forward / input-gradient gather-GEMM, the bf16 weight images ----
 int launch_gather_gemm_bf16(const GatherGemmParams& p, hipStream_t s);
@@ -174,10 +196,6 @@ static inline int pw16_form(const GatherGemmParams&) { return 0; }
 static inline int launch_pw16(const GatherGemmParams&, hipStream_t) { return 1; }
 static inline int pw16_set_mode(int) { return -1; }
 #endif
-
-// ---- launchers (wgrad_bf16.hip): bf16 weight gradient (fp32 split-K partials) ----
-int launch_wgrad_bf16(const WgradParams& p, int splitK, hipStream_t s);
-int wgrad_bf16_pick_split(int M, int Co, int Ci, int T);
 
 // ---- launchers of the stem (x/255 -> Normalize -> conv1 7x7/2 pad 3, 3 -> 64): three kernel sets, one device header (stem_dev.h);
 // the engine picks the set once per call (engine.hip, struct Stem). w147 / dw147: conv1's weights OHWI [64][7][7][3] ----

@@ -45,7 +45,8 @@ int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* 
                       const ConvGeom& c, int flags, int dt, hipStream_t s, BnRedArgs* br = nullptr);
 int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, const ConvGeom& c, int accumulate, int dt,
                       hipStream_t s);
-size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt);
+size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt);     // split-K scratch of that launch: plan.split slabs
+WgradPlan conv_wgrad_plan(const ConvGeom& c, int dt);       // what conv_wgrad_launch would run (r3m_debug_wgrad_route)
 
 // ---- the plan ----
 struct Plan;

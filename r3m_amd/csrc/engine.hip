@@ -355,8 +355,7 @@ Plan* plan_create(int size, int F, int dtype, int H, int W) {
     if (i == 0) {
       wgp_max = std::max(wgp_max, Stem::plan_wgrad_ws_floats(is224, dtype));
     } else {
-      const int split = dtype == DT_BF16 ? wgrad_bf16_pick_split(M, c.Co, c.Ci, c.k * c.k) : wgrad_pick_split(M, c.Co, c.Ci, c.k * c.k);
-      if (welems * split > wgp_max) wgp_max = welems * split;
+      wgp_max = std::max(wgp_max, (long long)conv_wgrad_ws_floats(c.geom(F), dtype));
     }
   }
   // stem: P0 (pooled) and the argmax bytes; the pre-pool activation Z0 is never materialised (bn_pool.hip: fused stem tail)
@@ -509,11 +508,9 @@ int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* 
   return 0;
 }
 
-static int wgrad_split(const ConvGeom& c, int dt) {
-  return dt == DT_BF16 ? wgrad_bf16_pick_split(c.M(), c.Co, c.Ci, c.k * c.k) : wgrad_pick_split(c.M(), c.Co, c.Ci, c.k * c.k);
-}
-int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, const ConvGeom& c, int accumulate, int dt,
-                      hipStream_t s) {
+// The weight gradient of one convolution: fill the parameters, take the plan (wgrad.hip: route, tile, split-K factor — the one
+// dispatch of the family, both storage types), launch, reduce the split-K slabs.
+static WgradParams wgrad_params(const float* X, const float* dY, float* partial_ws, const ConvGeom& c, int dt) {
   WgradParams w;
   memset(&w, 0, sizeof w);
   w.dtype = dt;
@@ -523,11 +520,17 @@ int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial
   w.KH = w.KW = c.k; w.stride = c.stride; w.pad = c.pad;
   w.M = c.M();
   w.simple_rows = c.simple_rows();
-  const int split = wgrad_split(c, dt);
-  if (int e = dt == DT_BF16 ? launch_wgrad_bf16(w, split, s) : launch_wgrad(w, split, s)) return e;
-  return launch_wgrad_reduce(partial_ws, dW, c.w_elems(), split, accumulate, s);
+  return w;
 }
-size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt) { return (size_t)wgrad_split(c, dt) * c.Co * c.k * c.k * c.Ci; }
+int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial_ws, const ConvGeom& c, int accumulate, int dt,
+                      hipStream_t s) {
+  const WgradParams w = wgrad_params(X, dY, partial_ws, c, dt);
+  const WgradPlan r = wgrad_plan(w);
+  if (int e = launch_wgrad(w, r, s)) return e;
+  return launch_wgrad_reduce(partial_ws, dW, c.w_elems(), r.split, accumulate, s);
+}
+WgradPlan conv_wgrad_plan(const ConvGeom& c, int dt) { return wgrad_plan(wgrad_params(nullptr, nullptr, nullptr, c, dt)); }
+size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt) { return (size_t)conv_wgrad_plan(c, dt).split * c.w_elems(); }
 
 // ---------------------------------------------------------------------------------------------------------
 #define TRY(x)              \

@@ -8,11 +8,9 @@
 //       One tap per block, or (NT = 3) the three taps of a kernel row.
 //   wgrad3x3_halo_bf16_kernel : 3x3 / stride 1 / pad 1 at image widths that are multiples of 8: all nine taps per block from one
 //       staged X window.
-// launch_wgrad_bf16 = requirements -> wg16_form (which of the three) -> one launch -> one profiler / check_launch tail.
-#include "common.h"
-#include "conv_dev.h"
-#include <cstdlib>
-#include <cstring>
+// Which of the three a launch runs, its tile, K step, split and grid: wgrad_plan (wgrad.hip), the one dispatch of the weight-gradient
+// family. launch_wgrad_bf16 only launches the instantiation the plan names. Shared device code: wgrad_dev.h.
+#include "wgrad_dev.h"
 
 namespace r3m {
 
@@ -47,20 +45,13 @@ __device__ __forceinline__ void dma16(const char* src, unsigned char* lds) {
 // in x), and each tap still stages its own exactly-masked X rows (no register masks, any width / stride). Per tap this is 2/3 of
 // the L2 -> LDS bytes (the bf16 128 x 128 tile needs ~39 TB/s of that path at the matrix peak; the chip delivers ~17), 2/3 of
 // the DMA instructions and 2/3 of the LDS fragment reads of the per-tap form.
-// FAST = 1: the launcher has checked that one K step advances a row by less than one frame ((BK / Wo + 1) <= Ho — every layer of
+// FAST = 1: wgrad_plan has checked (plan.fast) that one K step advances a row by less than one frame ((BK / Wo + 1) <= Ho — every layer of
 // the networks here), so the division form of the coordinate walk is not even compiled in (registers, code size).
 template <int BMt, int BNt, int BK = 64, int NT = 1, int FAST = 0>   // BK = rows per K step: 64, or 32 (half the LDS: more blocks per CU)
 __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const WgradParams p) {
   static_assert(BK == 64 || BK == 32, "K step of 64 or 32 rows");
   static_assert(NT == 1 || NT == 3, "one tap, or the three taps of a kernel row");
-  // compile-time where the launcher's choice is fixed: a kernel-row block (NT = 3) never has 1x1 "simple" rows, and the
-  // interleaved DMA issue is a probe-build switch only (shipped builds issue all pieces right after the barrier)
-  const bool simple_rows = NT == 1 && p.simple_rows;
-#ifdef R3M_PROBES
-  const bool interleave = p.interleave != 0;
-#else
-  constexpr bool interleave = false;
-#endif
+  const bool simple_rows = NT == 1 && p.simple_rows;           // a kernel-row block (NT = 3) never has 1x1 "simple" rows
   constexpr int WR = BK / 4;                                   // k rows staged per wave per stage
   constexpr int TM = BMt / 64, TN = BNt / 64;
   constexpr int A_ROWB = BMt * 2, B_ROWB = BNt * 2;            // bytes per k row
@@ -75,18 +66,11 @@ __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int T = p.KH * p.KW;
-  const int TG = T / NT;                                       // tap groups per tile (NT = 3: kernel rows)
-  const int lid = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int bx = lid % p.gx, by = lid / p.gx;   // by = split index: consecutive logical blocks read the same rows
-  const int tap0 = (bx % TG) * NT;
-  const int tile = bx / TG;
-  const int tn_ = tile % p.tilesN, tm_ = tile / p.tilesN;
-  const int co0 = tm_ * BMt, ci0 = tn_ * BNt;
+  const WgBlock blk = wg_block<BMt, BNt, false>(p, T / NT);    // tap groups per tile (NT = 3: kernel rows)
+  const int tap0 = blk.grp * NT;
+  const int co0 = blk.co0, ci0 = blk.ci0, ms = blk.ms, me = blk.me;
   const int kh = tap0 / p.KW, kw0 = tap0 - kh * p.KW;
-  const int ms = by * p.rows_per_split;
-  const int me = min(p.M, ms + p.rows_per_split);
   const int hw = p.Ho * p.Wo;
-  const char* dYb = reinterpret_cast<const char*>(p.dY);
   const char* Xb = reinterpret_cast<const char*>(p.X);
 
   // swizzle key of a k row: 4 consecutive rows must land in 4 different 64-byte bank quarters
@@ -107,9 +91,7 @@ __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const 
   const unsigned a_chan = (unsigned)((co0 + (a_ps ^ (4 * a_key)) * 8) * 2);   // byte offset of this lane's 8 channels inside a dY row
   const unsigned b_chan = (unsigned)((ci0 + (b_ps ^ (4 * b_key)) * 8) * 2);
 
-  const char* a_base = dYb + (long long)ms * p.Co * 2;          // descriptor: rows [ms + BK * step, me) of dY
-  int a_left = (int)((long long)(me - ms) * p.Co * 2);
-  const int a_stepb = BK * p.Co * 2;
+  WgRows a = wg_rows<2>(p.dY, ms, me, p.Co, 0, BK);             // descriptor: rows [ms + BK * step, me) of dY, whole rows
   unsigned a_voff[AJ];
 #pragma unroll
   for (int j = 0; j < AJ; ++j) a_voff[j] = (unsigned)((wave * WR + j * A_RPI + a_k) * p.Co * 2) + a_chan;
@@ -119,13 +101,13 @@ __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const 
   const long long img = (long long)p.Hi * p.Wi * p.Ci * 2;
   const unsigned imgb = (unsigned)img;
   const int n0 = ms / hw;                                     // 3x3 / strided: offsets are relative to the split's first frame
-  const char* b_base = simple_rows ? Xb + (long long)ms * p.Ci * 2 : Xb + (long long)n0 * img;
-  int b_left;
+  WgRows b;
+  b.base = simple_rows ? Xb + (long long)ms * p.Ci * 2 : Xb + (long long)n0 * img;
   {
     const long long rest = simple_rows ? (long long)(me - ms) * p.Ci * 2 : (long long)(p.N - n0) * img;
-    b_left = rest < (long long)BUF_OOB ? (int)rest : (int)BUF_OOB;
+    b.left = rest < (long long)BUF_OOB ? (int)rest : (int)BUF_OOB;
   }
-  const int b_stepb = BK * p.Ci * 2;
+  b.stepb = BK * p.Ci * 2;
   const int pixb = p.Ci * 2;                                    // bytes between the X rows of neighbouring taps (one pixel)
   const int rowb = p.Wi * pixb;
   const int kh_p = kh - p.pad, kw_p = kw0 - p.pad;
@@ -167,12 +149,12 @@ __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const 
     if constexpr (pc < AJ) {
       constexpr int j = pc;
       unsigned char* la = smem + stage * STAGE + (wave * WR + j * A_RPI) * A_ROWB;
-      dma(a_base, a_left, la, a_voff[j]);
+      dma(a.base, a.left, la, a_voff[j]);
     } else {
       constexpr int j = pc - AJ;
       unsigned char* lb = smem + stage * STAGE + BK * A_ROWB + (wave * WR + j * B_RPI) * B_ROWB;
       if (simple_rows) {
-        dma(b_base, b_left, lb, b_off[j]);
+        dma(b.base, b.left, lb, b_off[j]);
       } else {
         const int iy = ys[j] + kh_p, ix0 = xs[j] + kw_p;
         const bool rowok = (unsigned)iy < (unsigned)p.Hi;
@@ -180,7 +162,7 @@ __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const 
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const bool in = rowok && ((unsigned)(ix0 + t) < (unsigned)p.Wi);
-          dma(b_base, b_left, lb + t * B_TILE, in ? off0 + (unsigned)(t * pixb) : BUF_OOB);
+          dma(b.base, b.left, lb + t * B_TILE, in ? off0 + (unsigned)(t * pixb) : BUF_OOB);
         }
         if (FAST || fast_adv) {
           int x = xs[j] + adv_xs, y = ys[j] + adv_ys, ps = pos[j] + adv_pos;
@@ -205,24 +187,13 @@ __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const 
       }
     }
     if constexpr (pc == NP - 1) {             // after the last piece of a K step: the linear descriptors move on (scalar unit)
-      a_base += a_stepb;
-      a_left = a_left > a_stepb ? a_left - a_stepb : 0;
-      if (simple_rows) {
-        b_base += b_stepb;
-        b_left = b_left > b_stepb ? b_left - b_stepb : 0;
-      }
+      a.advance();
+      if (simple_rows) b.advance();
     }
   };
 
   f32x16 acc[NT][TM][TN];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TN; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][a][b][r] = 0.f;
+  wg_clear(acc);
 
   // transpose-read addressing. Lane l: group-local q = l & 15 addresses k row 8*(l>>5) + (q>>2) (+16s + 4r as an immediate),
   // channels [16*((l>>4)&1) + 4*(q&3), +4) of its MFMA tile; the tile's 64-byte group index is XORed with the row key.
@@ -249,19 +220,13 @@ __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const 
   };
 
   auto mfma_stage = [&](const unsigned char* st, int dma_stage) __attribute__((always_inline)) {
-    // the next K step's DMA: all pieces right after the barrier (p.interleave = 1: spread between the MFMA groups instead)
-    if (dma_stage >= 0 && !interleave) static_for<NP>([&](auto pc) __attribute__((always_inline)) { issue_piece(dma_stage, pc); });
+    // the next K step's DMA: all pieces right after the barrier
+    if (dma_stage >= 0) static_for<NP>([&](auto pc) __attribute__((always_inline)) { issue_piece(dma_stage, pc); });
     static_for<BK / 16>([&](auto s_c) __attribute__((always_inline)) {
       constexpr int sidx = decltype(s_c)::value;
       bf16x8 a[TM];
 #pragma unroll
       for (int t = 0; t < TM; ++t) a[t] = frag(st + fa_off[t], A_ROWB, sidx);
-      if (dma_stage >= 0 && interleave) {
-        constexpr int P0 = sidx * NP / (BK / 16), P1 = (sidx + 1) * NP / (BK / 16);
-        static_for<P1 - P0>([&](auto q_c) __attribute__((always_inline)) {
-          issue_piece(dma_stage, std::integral_constant<int, P0 + decltype(q_c)::value>{});
-        });
-      }
 #pragma unroll
       for (int tp = 0; tp < NT; ++tp) {
         bf16x8 b[TN];
@@ -285,21 +250,7 @@ __global__ __launch_bounds__(256, NT == 3 ? 2 : 1) void wgrad_bf16_kernel(const 
     mfma_stage(smem + cur * STAGE, (kt + 1 < nk) ? (cur ^ 1) : -1);
   }
 
-  float* out = p.out + (long long)by * p.Co * T * p.Ci;
-  const int lrow = lane & 31, lh = lane >> 5;
-#pragma unroll
-  for (int tp = 0; tp < NT; ++tp)
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) {
-          const int ci = ci0 + (wn * TN + tn) * 32 + lrow;
-          out[((long long)co * T + tap0 + tp) * p.Ci + ci] = acc[tp][tm][tn][r];
-        }
-      }
+  wg_store<false, false>(p, blk, T, tap0, wm, wn, lane & 31, lane >> 5, acc);
 }
 
 // =====================================================================================================
@@ -322,12 +273,8 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_halo_bf16_kernel(const WgradP
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int lid = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int bx = lid % p.gx, by = lid / p.gx;          // by = split index: consecutive logical blocks read the same rows
-  const int tn_ = bx % p.tilesN, tm_ = bx / p.tilesN;
-  const int co0 = tm_ * 64, ci0 = tn_ * 64;
-  const int ms = by * p.rows_per_split;
-  const int me = min(p.M, ms + p.rows_per_split);
+  const WgBlock blk = wg_block<64, 64, false>(p, 1);   // one block per tile: all nine taps
+  const int co0 = blk.co0, ci0 = blk.ci0, ms = blk.ms, me = blk.me;
   const int W = p.Wi, H = p.Hi;
   const char* dYb = reinterpret_cast<const char*>(p.dY);
   const char* Xb = reinterpret_cast<const char*>(p.X);
@@ -362,11 +309,11 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_halo_bf16_kernel(const WgradP
     }
   };
 
-  f32x16 acc[9];
+  f32x16 acc[9][1][1];       // (cleared here: wg_clear together with wg_store costs this kernel 15 registers and 352 bytes of scratch)
 #pragma unroll
   for (int a = 0; a < 9; ++a)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[a][0][0][r] = 0.f;
 
   // transpose-read addressing (see wgrad_bf16_kernel): lane -> k row 8*(lane>>5) + (q>>2), 4 channels of its 32-channel group
   const int q16 = lane & 15;
@@ -447,7 +394,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_halo_bf16_kernel(const WgradP
           if constexpr (kw == 0) u[0] &= mL;
           if constexpr (kw == 2) u[3] &= mR;
         }
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, u), acc[t], 0, 0, 0);
+        acc[t][0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, u), acc[t][0][0], 0, 0, 0);
       });
     });
     // next K step: 64 pixels further
@@ -457,120 +404,36 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_halo_bf16_kernel(const WgradP
     while (oy >= H) oy -= H;
   }
 
-  float* out = p.out + (long long)by * p.Co * 9 * p.Ci;
-  const int lrow = lane & 31, lh = lane >> 5;
-#pragma unroll
-  for (int t = 0; t < 9; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      const int ci = ci0 + wn * 32 + lrow;
-      out[((long long)co * 9 + t) * p.Ci + ci] = acc[t][r];
-    }
+  wg_store<false, false>(p, blk, 9, 0, wm, wn, lane & 31, lane >> 5, acc);
 }
 
 // 3x3 stride-1 weight gradients at image widths that are multiples of 8 go through the all-taps kernel (56x56 x 64 channels at
-// 1280 frames: 0.834 -> 0.470 ms; ResNet-50 step -1.1 %, ResNet-34 -4.2 %). R3M_WG16_HALO=0: per-tap kernel
-static int wg16_halo() {
-  const int v = R3M_ENV_INT("R3M_WG16_HALO", 1);
-  return v;
-}
-
-static inline int wgrad_halo_lds_bytes(int W) { return 2 * (64 * 128 + ceil_div(64 + 2 * W + 2, 8) * 1024); }
-
-static bool wgrad_halo_eligible(const WgradParams& p) {
-  // widths that are multiples of 8 (56 x 56: the 64-channel layers, where the per-tap kernel is furthest from its roof)
+// 1280 frames: 0.834 -> 0.470 ms; ResNet-50 step -1.1 %, ResNet-34 -4.2 %): 56 x 56 is where the 64-channel layers are, and where the
+// per-tap kernel is furthest from its roof
+int wgrad_halo_lds_bytes(int W) { return 2 * (64 * 128 + ceil_div(64 + 2 * W + 2, 8) * 1024); }
+bool wgrad_halo_eligible(const WgradParams& p) {
   return p.KH == 3 && p.KW == 3 && p.stride == 1 && p.pad == 1 && p.Ho == p.Hi && p.Wo == p.Wi && (p.Wi & 7) == 0 && p.Wi >= 8 &&
          p.Hi >= 4 && p.Wi <= 1024 && wgrad_halo_lds_bytes(p.Wi) <= 80 * 1024;
 }
 
-static inline bool wg_wide(int Co, int Ci) { return (Co % 128 == 0) && (Ci % 128 == 0); }
-
-// Round 3: 3-wide kernels on the 128 x 128 tile run one block per KERNEL ROW (three taps, dY staged and read once): ResNet-34's
-// 128 / 256 / 512-channel 3x3 weight gradients, stride 1 and 2. R3M_WG16_ROWS=0 (probe builds): per-tap blocks.
-static bool wg16_rows(int KW, bool wide) {
-  const int v = R3M_ENV_INT("R3M_WG16_ROWS", 1);
-  return v && wide && KW == 3;
-}
-
-// split-K factor: enough blocks to fill the chip ~4 (wide) / ~10 (narrow) times, rows per split a multiple of 64
-int wgrad_bf16_pick_split(int M, int Co, int Ci, int T) {
-  const bool wide = wg_wide(Co, Ci);
-  const int tiles = wide ? (Co / 128) * (Ci / 128) * T : ceil_div(Co, 64) * ceil_div(Ci, 64) * T;
-  const int tgt = R3M_ENV_INT("R3M_WG16_BLOCKS", 0);
-  // the all-taps kernel runs one block per (tile, split) for all nine taps: 512 splits of the 64-channel layers fill the chip
-  const int narrow_target = (T == 9 && wg16_halo()) ? 512 * 9 : 2560;
-  int blocks_per_split = tiles > 0 ? tiles : 1;
-  int wide_target = 1024;
-  if (wg16_rows(T == 9 ? 3 : 0, wide)) {
-    blocks_per_split = tiles / 3;     // `tiles` counts taps; a kernel-row block covers three
-    wide_target = 512;                // exactly one round of the 2 blocks a CU holds (same box: 802 -> 835, 717 -> 750 TFLOP/s vs 1024)
-  }
-  int split = (wide ? (tgt > 0 ? tgt : wide_target) : narrow_target) / blocks_per_split;
-  const int max_split = ceil_div(M, 256);
-  if (split > max_split) split = max_split;
-  if (split < 1) split = 1;
-  return split;
-}
-
-// Which of the three forms a launch runs: all nine taps per block on the 64 x 64 tile (wgrad3x3_halo_bf16_kernel), one block per
-// kernel row (wgrad_bf16_kernel, NT = 3, 128 x 128 tile), or one block per tap (128 x 128 or 64 x 64 tile)
-enum : int { WG16_HALO, WG16_ROWS, WG16_TAPS };
-static int wg16_form(const WgradParams& p, bool wide) {
-  if (wg16_halo() && wgrad_halo_eligible(p)) return WG16_HALO;
-  return wg16_rows(p.KW, wide) ? WG16_ROWS : WG16_TAPS;
-}
-
-int launch_wgrad_bf16(const WgradParams& p0, int splitK, hipStream_t s) {
-  WgradParams p = p0;
-  R3M_REQUIRE(p.Co % 64 == 0 && p.Ci % 64 == 0, "wgrad(bf16): Co=%d, Ci=%d must be multiples of 64", p.Co, p.Ci);
-  const int T = p.KH * p.KW;
-  const bool wide = wg_wide(p.Co, p.Ci);
-  p.rows_per_split = ceil_div(ceil_div(p.M, splitK), 64) * 64;
-  const double flops = 2.0 * (double)p.M * p.Co * (double)p.Ci * T;
-  prof_begin(wide ? KC_WGRAD_WIDE : KC_WGRAD_NARROW, flops, p.M, p.Co, p.Ci, T, s);
-  {   // buffer addressing: a block's operands are reached through 32-bit offsets from the first row / frame of its split
-    const long long lim = 0x7FFFF000LL;
-    const long long a_span = (long long)p.rows_per_split * p.Co * 2;
-    const long long frames = (long long)p.rows_per_split / ((long long)p.Ho * p.Wo) + 2;
-    const long long b_span = p.simple_rows ? (long long)p.rows_per_split * p.Ci * 2 : frames * p.Hi * p.Wi * p.Ci * 2;
-    R3M_REQUIRE(a_span < lim && b_span < lim, "wgrad(bf16): one split spans %lld / %lld bytes (limit 2 GiB): raise splitK (%d)", a_span, b_span, splitK);
-  }
-  {
-    const int il = R3M_ENV_INT("R3M_WG_INTERLEAVE", 0);
-    p.interleave = il;
-    const int xc = R3M_ENV_INT("R3M_WG_XCD", 1);
-    p.xcd = xc;
-  }
-  const int form = wg16_form(p, wide);
-  const int tile = (wide && form != WG16_HALO) ? 128 : 64;
-  p.tilesN = p.Ci / tile;
-  p.gx = (p.Co / tile) * p.tilesN * (form == WG16_HALO ? 1 : form == WG16_ROWS ? p.KH : T);   // blocks per split
-  const dim3 grid(p.gx * splitK);
-  const char* what = "wgrad_bf16";
-  if (form == WG16_HALO) {
-    const int lds = wgrad_halo_lds_bytes(p.Wi);
+// Launches the instantiation the plan names: all nine taps per block on the 64 x 64 tile, one block per kernel row (round 3: 3-wide
+// kernels on the 128 x 128 tile, three taps, dY staged and read once — ResNet-34's 128 / 256 / 512-channel 3x3 layers, stride 1 and
+// 2), or one block per tap (128 x 128 tile with K steps of 32 rows, 64 x 64 with 64).
+int launch_wgrad_bf16(const WgradParams& p, const WgradPlan& r, hipStream_t s) {
+  const dim3 grid(r.gx * r.split);
+  if (r.route == WG16_ALL_TAPS) {
     static DynLdsOptIn optin;
-    if (int e = ensure_dyn_lds(optin, reinterpret_cast<const void*>(wgrad3x3_halo_bf16_kernel), lds, "wgrad3x3_halo(bf16)")) return e;
-    hipLaunchKernelGGL(wgrad3x3_halo_bf16_kernel, grid, dim3(256), lds, s, p, ceil_div(64 + 2 * p.Wi + 2, 8));
-    what = "wgrad3x3_halo_bf16";
-  } else if (form == WG16_ROWS) {   // FAST where one K step advances a row by less than one frame (see wgrad_bf16_kernel)
-    if ((32 / p.Wo + 1) <= p.Ho) hipLaunchKernelGGL((wgrad_bf16_kernel<128, 128, 32, 3, 1>), grid, dim3(256), 0, s, p);
+    if (int e = ensure_dyn_lds(optin, reinterpret_cast<const void*>(wgrad3x3_halo_bf16_kernel), r.lds_bytes, "wgrad3x3_halo(bf16)")) return e;
+    hipLaunchKernelGGL(wgrad3x3_halo_bf16_kernel, grid, dim3(256), r.lds_bytes, s, p, ceil_div(64 + 2 * p.Wi + 2, 8));
+  } else if (r.route == WG16_ROWS) {
+    if (r.fast) hipLaunchKernelGGL((wgrad_bf16_kernel<128, 128, 32, 3, 1>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((wgrad_bf16_kernel<128, 128, 32, 3>), grid, dim3(256), 0, s, p);
-    what = "wgrad_bf16 (kernel rows)";
+  } else if (r.tile == 128) {
+    hipLaunchKernelGGL((wgrad_bf16_kernel<128, 128, 32>), grid, dim3(256), 0, s, p);
   } else {
-    // K steps of 32 rows for the 128x128 tile (32 KB of stages instead of 64: -16 % measured over ResNet-50), 64 rows for the
-    // 64x64 tile (32 rows measured +5 % there). R3M_WG16_BK=64 / =32 forces one step size on both (experiments).
-    const int bk = R3M_ENV_INT("R3M_WG16_BK", 0);
-    const bool bk32 = bk == 32 || (bk != 64 && wide);
-    if (wide && bk32) hipLaunchKernelGGL((wgrad_bf16_kernel<128, 128, 32>), grid, dim3(256), 0, s, p);
-    else if (wide) hipLaunchKernelGGL((wgrad_bf16_kernel<128, 128>), grid, dim3(256), 0, s, p);
-    else if (bk32) hipLaunchKernelGGL((wgrad_bf16_kernel<64, 64, 32>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((wgrad_bf16_kernel<64, 64>), grid, dim3(256), 0, s, p);
+    hipLaunchKernelGGL((wgrad_bf16_kernel<64, 64>), grid, dim3(256), 0, s, p);
   }
-  prof_bytes(2.0 * ((double)p.M * p.Co + (double)p.N * p.Hi * p.Wi * p.Ci) + 4.0 * (double)splitK * p.Co * T * p.Ci);
-  prof_end(s);
-  return check_launch(what);
+  return 0;
 }
 
 }  // namespace r3m

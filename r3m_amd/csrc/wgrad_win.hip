@@ -22,8 +22,9 @@
 // Everything else (LDS image, MFMA order inside a K pair, split-K partial slabs, XCD-aware block order) is wgrad_glds_kernel's.
 // Summation order over m is unchanged (K steps of 32 instead of 16 rows do not reorder a split's rows): results are bit-identical
 // to the kernel-row form.
-#include "common.h"
-#include "conv_dev.h"
+// Which launches run here (route WG_WINDOW), their split and grid: wgrad_plan (wgrad.hip) through wgrad_rowwin_eligible below;
+// launch_wgrad_rowwin launches the instantiation the plan names. Block decode, dY descriptor and write-out: wgrad_dev.h.
+#include "wgrad_dev.h"
 
 namespace r3m {
 
@@ -69,24 +70,14 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 4) void wgrad_rowwin_kernel(co
   const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = WIDE ? 0 : (wave_s >> 1), wn = WIDE ? wave_s : (wave_s & 1);
   const int T = p.KH * p.KW;
-  const int lid = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
-  const int bx = lid % p.gx, by = lid / p.gx;      // by = split index: consecutive logical blocks read the same rows
-  // (block coordinates are uniform, but the divisions above are expanded on the vector unit: say so, or everything derived from
-  // them — descriptors, the padding-mask walk — stays in vector registers)
-  const int kh = __builtin_amdgcn_readfirstlane(bx % p.KH);
-  const int tile = bx / p.KH;
-  const int tn_ = tile % p.tilesN, tm_ = tile / p.tilesN;
-  const int co0 = __builtin_amdgcn_readfirstlane(tm_ * BT), ci0 = __builtin_amdgcn_readfirstlane(tn_ * BT);
-  const int ms = __builtin_amdgcn_readfirstlane(by * p.rows_per_split);
-  const int me = min(p.M, ms + p.rows_per_split);
+  const WgBlock blk = wg_block<BT, BT, true>(p, p.KH);      // one block per kernel row; coordinates pinned to scalar registers
+  const int kh = blk.grp, co0 = blk.co0, ci0 = blk.ci0, ms = blk.ms, me = blk.me;
 
   // lane -> (row within the instruction, first channel): loop constants
   const int l_k = lane / (BT / 4), l_c = (lane % (BT / 4)) * 4;
 
   // dY: descriptor = [row ms + BK step, end of the split) x channels from co0
-  const float* a_base = p.dY + (long long)ms * p.Co + co0;   // (scalar: ms, co0 are)
-  int a_left = (int)(((long long)(me - ms) * p.Co - co0) * 4);
-  const int a_stepb = BK * p.Co * 4;
+  WgRows a = wg_rows<4>(p.dY, ms, me, p.Co, co0, BK);        // (scalar: ms, co0 are)
   unsigned a_voff[AJ];
 #pragma unroll
   for (int j = 0; j < AJ; ++j) a_voff[j] = (unsigned)(((wave_s * WR + j * RPI + l_k) * p.Co + l_c) * 4);
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 4) void wgrad_rowwin_kernel(co
     constexpr int pc = decltype(pc_c)::value;
     if (R3M_PROBE(p) & 1) return;                       // timing probes (probe builds only; wrong results)
     if constexpr (pc < AJ) {
-      buf_dma16_uniform(a_base, a_left, smem + stage * STAGE + (wave_s * WR + pc * RPI) * BT, a_voff[pc]);
+      buf_dma16_uniform(a.base, a.left, smem + stage * STAGE + (wave_s * WR + pc * RPI) * BT, a_voff[pc]);
     } else {
       constexpr int q = pc - AJ;
       if constexpr (q == 0) {
@@ -124,8 +115,7 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 4) void wgrad_rowwin_kernel(co
     }
   };
   auto advance = [&]() __attribute__((always_inline)) {   // both descriptors move on by BK rows (scalar)
-    a_base += BK * p.Co;
-    a_left = a_left > a_stepb ? a_left - a_stepb : 0;
+    a.advance();
     xw0 += BK;
   };
 
@@ -161,13 +151,13 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 4) void wgrad_rowwin_kernel(co
     }
   };
 
-  f32x16 acc[3][TM];
+  f32x16 acc[3][TM][1];      // (cleared here: wg_clear together with wg_store costs this kernel 27 / 30 registers, the 64-wide one 3 waves per SIMD)
 #pragma unroll
   for (int t = 0; t < 3; ++t)
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][a][r] = 0.f;
+      for (int r = 0; r < 16; ++r) acc[t][a][0][r] = 0.f;
 
   const int lrow = lane & 31, lh = lane >> 5;
   const float* fragA = smem + lh * BT + (WIDE ? 4 * lrow : wm * 32 + lrow);
@@ -188,7 +178,7 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 4) void wgrad_rowwin_kernel(co
       for (int tp = 0; tp < 3; ++tp) {
         const float b = wgw_select<kk>(fb[(kk * 2 + tp) * BT], mk[tp]);
 #pragma unroll
-        for (int tm = 0; tm < TM; ++tm) acc[tp][tm] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm], b, acc[tp][tm], 0, 0, 0);
+        for (int tm = 0; tm < TM; ++tm) acc[tp][tm][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tm], b, acc[tp][tm][0], 0, 0, 0);
       }
       if constexpr (kk < NP) {
         if (dma_stage >= 0) {
@@ -224,48 +214,28 @@ __global__ __launch_bounds__(256, BT == 128 ? 2 : 4) void wgrad_rowwin_kernel(co
     mfma_stage(fragA, fragB, -1);
   }
 
-  float* out = p.out + (long long)by * p.Co * T * p.Ci;
-#pragma unroll
-  for (int tp = 0; tp < 3; ++tp)
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int rho = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const int co = WIDE ? co0 + 4 * rho + tm : co0 + wm * 32 + rho;
-        const int ci = ci0 + wn * 32 + lrow;
-        out[((long long)co * T + kh * p.KW + tp) * p.Ci + ci] = acc[tp][tm][r];
-      }
+  wg_store<WIDE, false>(p, blk, T, kh * p.KW, wm, wn, lrow, lh, acc);
 }
 
 // 3 x 3 "same" convolution (stride 1, pad 1: Ho = Hi, Wo = Wi), fp32, whole tiles
 bool wgrad_rowwin_eligible(const WgradParams& p) {
   if (p.dtype != DT_F32 || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.pad != 1 || p.Ho != p.Hi || p.Wo != p.Wi) return false;
   if (p.Wo < 2 || p.Ho < 1 || p.M != p.N * p.Ho * p.Wo) return false;
-  const bool wide = (p.Co % 128 == 0) && (p.Ci % 128 == 0);
-  if (!wide && ((p.Co % 64) || (p.Ci % 64))) return false;
+  if (!wg_wide(p.Co, p.Ci) && ((p.Co % 64) || (p.Ci % 64))) return false;
   // 32-bit offsets: a window / a dY tile spans 34 rows; one split's dY < 2 GiB is checked by the caller
   return 40LL * p.Ci * 4 < 0x7FFFF000LL && 40LL * p.Co * 4 < 0x7FFFF000LL;
 }
 
-// p: rows_per_split, tilesN, xcd set by launch_wgrad (wgrad.hip); sets p.gx. One block per (co tile, ci tile, kernel row, split).
-int launch_wgrad_rowwin(WgradParams& p, int splitK, hipStream_t s) {
-  const bool wide = (p.Co % 128 == 0) && (p.Ci % 128 == 0);
-  if (wide) {
-    constexpr int LDS = 2 * (32 + 34) * 128 * 4;
-    static DynLdsOptIn oi;
-    if (int e = ensure_dyn_lds(oi, reinterpret_cast<const void*>(wgrad_rowwin_kernel<128, 32>), LDS, "wgrad_rowwin")) return e;
-    p.tilesN = p.Ci / 128;
-    p.gx = (p.Co / 128) * p.tilesN * p.KH;
-    hipLaunchKernelGGL((wgrad_rowwin_kernel<128, 32>), dim3(p.gx * splitK), dim3(256), LDS, s, p);
-  } else {
-    constexpr int LDS = 2 * (32 + 36) * 64 * 4;
-    static DynLdsOptIn oi;
-    if (int e = ensure_dyn_lds(oi, reinterpret_cast<const void*>(wgrad_rowwin_kernel<64, 32>), LDS, "wgrad_rowwin")) return e;
-    p.tilesN = p.Ci / 64;
-    p.gx = (p.Co / 64) * p.tilesN * p.KH;
-    hipLaunchKernelGGL((wgrad_rowwin_kernel<64, 32>), dim3(p.gx * splitK), dim3(256), LDS, s, p);
-  }
+// dynamic LDS of a launch: two stages of BK dY rows + the allocated window rows (wgrad_rowwin_kernel's STAGE)
+int wgrad_rowwin_lds_bytes(int tile) { return 2 * (32 + (tile == 128 ? 34 : 36)) * tile * 4; }
+
+// one block per (co tile, ci tile, kernel row, split)
+int launch_wgrad_rowwin(const WgradParams& p, const WgradPlan& r, hipStream_t s) {
+  static DynLdsOptIn oi[2];
+  const void* fn = r.tile == 128 ? reinterpret_cast<const void*>(wgrad_rowwin_kernel<128, 32>) : reinterpret_cast<const void*>(wgrad_rowwin_kernel<64, 32>);
+  if (int e = ensure_dyn_lds(oi[r.tile == 128], fn, r.lds_bytes, "wgrad_rowwin")) return e;
+  if (r.tile == 128) hipLaunchKernelGGL((wgrad_rowwin_kernel<128, 32>), dim3(r.gx * r.split), dim3(256), r.lds_bytes, s, p);
+  else hipLaunchKernelGGL((wgrad_rowwin_kernel<64, 32>), dim3(r.gx * r.split), dim3(256), r.lds_bytes, s, p);
   return 0;
 }
 

@@ -3,6 +3,7 @@ tests/test_dispatch.py compares the engine's launches with the operator tests' c
 
 A signature is (dtype, dgrad, flags, mask_bits, routes, k, stride, Co % 128 == 0, wide | tall | square): everything the dispatch
 (csrc/conv.hip gg_route, conv_bf16.hip gg16_route) can tell apart, minus the sizes themselves."""
+import collections
 import ctypes as C
 
 STATS, ACCUM, MASKED_ADD, BNRED, AFFINE, RELU = 1, 2, 4, 64, 128, 16
@@ -176,4 +177,36 @@ def engine_launches(L, size, dt, F, H, W):
         fused = all(L.r3m_debug_conv_fuses_affine(F, c[5], c[6], c[0], c[1], c[2], c[3], c[4], fl, dt) == 1 for c, fl in want)
         for c, fl in want:
             add(c, 0, fl if fused else 0)
+    return out
+
+
+# ---- the weight gradients behind the stem (csrc/wgrad.hip wgrad_plan, through r3m_debug_wgrad_route) ------------------------------------------
+WG_TAPS_SIMPLE, WG_TAPS_GATHER, WG_ROWS, WG_WINDOW, WG16_TAPS, WG16_ROWS, WG16_ALL_TAPS = 40, 41, 42, 43, 50, 51, 52
+WG_ROUTES = {0: (WG_TAPS_SIMPLE, WG_TAPS_GATHER, WG_ROWS, WG_WINDOW), 1: (WG16_TAPS, WG16_ROWS, WG16_ALL_TAPS)}
+WgPlan = collections.namedtuple("WgPlan", "route tile bk fast split rows_per_split tilesN gx lds_bytes")
+
+
+def wgrad_plan(L, case, dt):
+    """the plan of one weight-gradient launch, case = (N, Hi, Wi, Ci, Co, k, stride, pad)"""
+    buf = (C.c_int * 9)()
+    assert L.r3m_debug_wgrad_route(*case, dt, buf, 9) == 9, L.r3m_last_error()
+    return WgPlan(*buf)
+
+
+def wgrad_variant(r):
+    """the kernel instantiation a plan names: the route and the fields that pick a template variant inside it"""
+    return (r.route, r.tile, r.bk, r.fast)
+
+
+def wgrad_operator_cases():
+    """[(origin, case, dtype)] of every weight gradient the GPU operator tests run and compare (tests/test_gpu_ops.py, test_gpu_ops_hw.py,
+    test_gpu_fuzz.py): fp32 against F.conv2d autograd, bf16 against float64 / exact integers"""
+    import test_gpu_fuzz as Z
+    import test_gpu_ops as O
+    import test_gpu_ops_hw as T
+    sq = lambda c: (c[0], c[1], c[1]) + tuple(c[2:])
+    out = [("ops", sq(c), 0) for c in O.CONV_CASES]
+    out += [("ops_hw", c, 0) for c in T.HW_CONV_CASES] + [("ops_hw", c, 1) for c in T.HW_BF16_CASES + T.HW_ROW16_CASES]
+    out += [("ops_hw", (2, 5, 9, 64, 128, 3, s, 1), dt) for s in (1, 2) for dt in (0, 1)]       # test_conv3x3_pixel_codes_are_exact_hw
+    out += [("fuzz", sq(c), 0) for c in Z.FP32_CASES] + [("fuzz", sq(c), 1) for c in Z.BF16_CASES]
     return out

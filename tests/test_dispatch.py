@@ -254,11 +254,16 @@ def test_operator_case_groups_hold_what_they_are_there_for():
         assert -(-M // 128) * (Co // 128) > 512 and M % 128, (N, Hi, Wi, M)
         assert fwd((N, Hi, Wi, Ci, Co, k, s, p))[0] in (PW_POINT, PW_GATHER)
     # bf16: all-taps weight gradient needs (Wi & 7) == 0, Wi >= 8, Hi >= 4: both answers on the wide maps (Hi = 3 against 4, 5), and the
-    # transposes (Wi = 3, 4, 5 with Hi = 8, 16, 24) must all stay off it; FAST K steps need Ho Wo > 32
-    ok = lambda c: c[2] % 8 == 0 and c[2] >= 8 and c[1] >= 4
+    # transposes (Wi = 3, 4, 5 with Hi = 8, 16, 24) must all stay off it; FAST K steps need Ho Wo > 32 -- the library's own answers
+    wg = lambda c, dt=1: route_sig.wgrad_plan(L, c, dt)
+    ok = lambda c: wg(c).route == route_sig.WG16_ALL_TAPS
     assert {ok(c) for c in H16["wgrad_all_taps"] if c[2] > c[1]} == {True, False}
     assert {ok(c) for c in H16["wgrad_all_taps"] if c[1] > c[2]} == {False} and len(H16["wgrad_all_taps"]) == 18
-    assert {c[1] * c[2] > 32 for c in H16["wgrad_fast_path"]} == {True, False} and all(c[3] % 128 == 0 and c[4] % 128 == 0 for c in H16["wgrad_fast_path"])
+    assert all(wg(c).route == route_sig.WG16_ROWS for c in H16["wgrad_fast_path"])
+    assert {wg(c).fast for c in H16["wgrad_fast_path"]} == {1, 0} and all(c[3] % 128 == 0 and c[4] % 128 == 0 for c in H16["wgrad_fast_path"])
+    # fp32 shared-window weight gradient: Wo = 2 is on it, the 9 x 1 maps of one_pixel are not
+    assert all(wg(c, 0).route == route_sig.WG_WINDOW for c in G["wgrad_window_width"])
+    assert {wg(c, 0).route for c in G["one_pixel"] if c[2] == 1 and c[5:] == (3, 1, 1)} == {route_sig.WG_ROWS}
     # kernel-row and halo kernel, wide and tall, 64- and 128-wide outputs, all on the kernel-row route by default
     assert all(fwd(c, 1) == (BF16_ROW,) for c in T.HW_ROW16_CASES)
     assert {(c[2] > c[1], c[4] % 128 == 0) for c in T.HW_ROW16_CASES} == {(a, b) for a in (True, False) for b in (True, False)}
@@ -387,3 +392,96 @@ def test_head_launches_of_the_workload_have_an_operator_case():
     # the gather GEMM for the input gradients; the bf16 gather kernel throughout
     assert {s[3] for s in seen if s[0] == 0 and s[1] == 0} == {(21,), (22,)} and {s[3] for s in seen if s[0] == 0 and s[1] == 1} == {(PW_POINT,), (21,)}
     assert {s[3] for s in seen if s[0] == 1} == {(BF16,)}
+
+
+# ---- the weight gradients behind the stem (csrc/wgrad.hip wgrad_plan through r3m_debug_wgrad_route) -----------------------------------------
+def _wgrad_want(dt, Hin, Ci, Co, k, s):
+    """(route, tile) the weight gradient of a ResNet layer at a 224 x 224 frame must run -- as profiles/wgrad_unify_routes.txt lists them.
+    A layer that fell off the window kernel or the all-taps kernel would only show as lost throughput on the GPU."""
+    R = route_sig
+    wide = Ci % 128 == 0 and Co % 128 == 0
+    if dt == 0:
+        tile = 128 if wide else 64
+        if k == 1:
+            return (R.WG_TAPS_SIMPLE if s == 1 else R.WG_TAPS_GATHER), tile
+        return (R.WG_WINDOW if s == 1 else R.WG_ROWS), tile
+    if k == 3 and s == 1 and Hin % 8 == 0:          # 56 x 56 and 28 x 28 (and 14 x 14 has no multiple of 8: kernel rows / taps)
+        return R.WG16_ALL_TAPS, 64
+    if k == 3 and wide:
+        return R.WG16_ROWS, 128
+    return R.WG16_TAPS, (128 if wide else 64)
+
+
+@pytest.mark.parametrize("dt", [0, 1], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("size,frames", [(50, 1280), (34, 2560), (18, 2560), (18, 8)])
+def test_weight_gradient_route_of_every_layer(size, frames, dt):
+    """per network and precision the route and tile of every layer's weight gradient: fp32 3x3 / stride-1 layers on the shared-window
+    kernel, 3x3 / stride 2 on kernel rows, 1x1 / stride 1 on simple rows, strided 1x1 on gathered rows; bf16 3x3 / stride-1 layers at widths
+    that are multiples of 8 on the all-taps kernel, the other 3x3 layers of 128-multiple channel counts on kernel rows (the division-free
+    walk everywhere), the rest per tap with K steps of 32 rows on the 128-wide tile and 64 on the 64-wide one. And the grid and the
+    workspace follow from the plan: gx = tiles x tap groups, workspace = split x Co x k^2 x Ci floats, the splits cover M."""
+    from r3m_amd import _lib
+    L = _lib.lib()
+    R = route_sig
+    seen = set()
+    for (name, H, Ci, Co, k, s, p, _, _) in _layers(size):
+        case = (frames, H, H, Ci, Co, k, s, p)
+        r = R.wgrad_plan(L, case, dt)
+        assert (r.route, r.tile) == _wgrad_want(dt, H, Ci, Co, k, s), (size, name, r)
+        assert r.bk == {R.WG_ROWS: 16, R.WG16_ALL_TAPS: 64, R.WG16_TAPS: 32 if r.tile == 128 else 64}.get(r.route, 32), (name, r)
+        assert r.fast == (r.route == R.WG16_ROWS), (name, r)
+        groups = {R.WG_TAPS_SIMPLE: k * k, R.WG_TAPS_GATHER: k * k, R.WG16_TAPS: k * k, R.WG16_ALL_TAPS: 1}.get(r.route, k)
+        assert r.tilesN == -(-Ci // r.tile) and r.gx == -(-Co // r.tile) * r.tilesN * groups, (name, r)
+        assert (r.lds_bytes > 0) == (r.route in (R.WG_WINDOW, R.WG16_ALL_TAPS)) and r.lds_bytes <= 160 * 1024, (name, r)
+        Ho = (H + 2 * p - k) // s + 1
+        M = frames * Ho * Ho
+        assert r.split >= 1 and r.rows_per_split % (64 if dt else 32) == 0 and r.split * r.rows_per_split >= M, (name, r)
+        assert dt == 1 or (r.split - 1) * r.rows_per_split < M, (name, r)                      # fp32: no empty split
+        assert L.r3m_conv2d_wgrad_workspace_bytes_dt(*case, dt) == 4 * r.split * Co * k * k * Ci, (name, r)
+        seen.add(r.route)
+    want = {0: {R.WG_WINDOW, R.WG_ROWS} | ({R.WG_TAPS_SIMPLE, R.WG_TAPS_GATHER} if size == 50 else {R.WG_TAPS_GATHER}),
+            1: {R.WG16_ALL_TAPS, R.WG16_TAPS, R.WG16_ROWS}}[dt]
+    assert seen == want, (size, dt, seen)
+
+
+def test_every_weight_gradient_route_and_variant_has_an_operator_case():
+    """every route value, and inside a route every kernel instantiation (tile 128 / 64, K step, FAST) that a layer of the networks, the
+    reward head or ANY listed case takes, is run by a case of the GPU operator lists, which compare dW with autograd / float64; each
+    precision has a case of more than one split whose last split is shorter than the others, and workspace = split x |dW| throughout"""
+    from r3m_amd import _lib
+    L = _lib.lib()
+    R = route_sig
+    ops = R.wgrad_operator_cases()
+    have = {}
+    for (origin, case, dt) in ops:
+        r = R.wgrad_plan(L, case, dt)
+        have.setdefault(R.wgrad_variant(r), (origin, case))
+        N, Hi, Wi, Ci, Co, k, s, p = case
+        assert L.r3m_conv2d_wgrad_workspace_bytes_dt(*case, dt) == 4 * r.split * Co * k * k * Ci, (case, dt, r)
+    for dt in (0, 1):
+        assert {v[0] for v in have if v[0] in R.WG_ROUTES[dt]} == set(R.WG_ROUTES[dt]), (dt, sorted(have))
+    assert set(have) == {(40, 128, 32, 0), (40, 64, 32, 0), (41, 128, 32, 0), (41, 64, 32, 0), (42, 128, 16, 0), (42, 64, 16, 0),
+                         (43, 128, 32, 0), (43, 64, 32, 0), (50, 128, 32, 0), (50, 64, 64, 0), (51, 128, 32, 0), (51, 128, 32, 1),
+                         (52, 64, 64, 0)}, sorted(have)
+    engine = set()
+    for (size, frames) in ((50, 1280), (34, 2560), (18, 2560), (18, 8)):
+        for (name, H, Ci, Co, k, s, p, _, _) in _layers(size):
+            engine |= {R.wgrad_variant(R.wgrad_plan(L, (frames, H, H, Ci, Co, k, s, p), dt)) for dt in (0, 1)}
+    for Rows in (15 * 256, 15 * 512):
+        for K in (2 * 512 + 768, 2 * 2048 + 768, 1024):
+            engine |= {R.wgrad_variant(R.wgrad_plan(L, (Rows, 1, 1, K, 1024, 1, 1, 0), dt)) for dt in (0, 1)}
+    assert engine <= set(have), engine - set(have)
+    rows = lambda c: c[0] * ((c[1] + 2 * c[7] - c[5]) // c[6] + 1) * ((c[2] + 2 * c[7] - c[5]) // c[6] + 1)
+    for dt in (0, 1):
+        ragged = [(c, r) for (_, c, d) in ops if d == dt for r in [R.wgrad_plan(L, c, dt)]
+                  if r.split > 1 and 0 < rows(c) - (r.split - 1) * r.rows_per_split < r.rows_per_split]
+        assert ragged, dt
+        assert {r.route for (_, r) in ragged} >= ({R.WG_TAPS_SIMPLE, R.WG_ROWS, R.WG_WINDOW} if dt == 0 else {R.WG16_TAPS, R.WG16_ALL_TAPS}), dt
+
+
+def test_debug_wgrad_route_refuses_a_short_buffer():
+    from r3m_amd import _lib
+    L = _lib.lib()
+    buf = (C.c_int * 9)()
+    assert L.r3m_debug_wgrad_route(2, 9, 7, 64, 64, 3, 1, 1, 0, buf, 8) == -1
+    assert L.r3m_debug_wgrad_route(2, 9, 7, 64, 64, 3, 1, 1, 0, buf, 9) == 9 and buf[0] == route_sig.WG_WINDOW

@@ -35,7 +35,11 @@ def _cases(n, seed):
     return out
 
 
-@pytest.mark.parametrize("case", _cases(36, 20260928), ids=lambda c: "N{}_H{}_{}to{}_k{}s{}p{}".format(*c))
+FP32_CASES = _cases(36, 20260928)
+BF16_CASES = [c for c in _cases(60, 7) if c[2] % 64 == 0 and c[3] % 64 == 0][:14]
+
+
+@pytest.mark.parametrize("case", FP32_CASES, ids=lambda c: "N{}_H{}_{}to{}_k{}s{}p{}".format(*c))
 def test_random_conv_geometry_fwd_dgrad_wgrad(hip, case):
     N, H, Ci, Co, k, s, p = case
     g = torch.Generator().manual_seed(hash(case) & 0xFFFF)
@@ -71,7 +75,7 @@ def test_random_conv_geometry_fwd_dgrad_wgrad(hip, case):
     assert rel_err(dwd.cpu().permute(0, 3, 1, 2).numpy(), wr.grad.numpy())[0] < 5e-5
 
 
-@pytest.mark.parametrize("case", [c for c in _cases(60, 7) if c[2] % 64 == 0 and c[3] % 64 == 0][:14],
+@pytest.mark.parametrize("case", BF16_CASES,
                          ids=lambda c: "N{}_H{}_{}to{}_k{}s{}p{}".format(*c))
 def test_random_conv_geometry_bf16(hip, case):
     """The bf16 entry points on the same kind of geometry: against float64 on the bf16-rounded operands, one rounding of the output
