@@ -172,6 +172,35 @@ int r3m_resnet_set_trainable(r3m_resnet_t h, const unsigned char* mask, int n);
  * formed), 4 = dgrad, 8 = wgrad. want_dx: the input gradient is asked for. Returns the number of convolutions, -1 on error. */
 int r3m_debug_backward_plan(r3m_resnet_t h, int want_dx, int* flags_out, int cap);
 
+/* Spatial feature maps: what the reference's users take from convnet.layer1 .. convnet.layer4 of the torchvision module built at
+ * models_r3m.py:44-52 (a forward hook on convnet.layerk, nn.Sequential(*list(convnet.children())[:-2]), or calling the layers by hand).
+ * Feature map k (1..4) is the output of torchvision's layer`k`: the activated output of that stage's last residual block, after the
+ * add and the ReLU. It leaves the library as fp32 NCHW [frames, C, H, W] and its gradient enters as fp32 NCHW, for fp32 and bf16
+ * plans alike (bf16 activations widen exactly; the gradient is added in fp32 and rounded once to the plan's storage type).
+ *
+ * Geometry of feature map `layer` for this plan. Needs no GPU. Non-zero for a layer outside 1..4. */
+int r3m_resnet_feature_info(r3m_resnet_t h, int layer, int* C, int* H, int* W);
+/* r3m_resnet_forward + fp32 NCHW copies of the requested stage outputs: feats[k-1] != NULL receives feature map k (feats is a HOST
+ * array of four device pointers; NULL entries = not wanted; feats == NULL is r3m_resnet_forward, launch for launch). Every training
+ * mode; in inference mode (training = 2) the copy is taken before a later block overwrites the map in place. */
+int r3m_resnet_forward_features(r3m_resnet_t h, const float* x, const float* params, float* buffers, void* arena, float* h_out,
+                                float* const feats[4], int training, r3m_stream_t stream);
+/* r3m_resnet_backward_ex + the gradients w.r.t. those outputs: dfeats[k-1] != NULL (HOST array of four device pointers, fp32 NCHW) is
+ * added to the running output gradient where autograd adds it, immediately before the backward of that stage's last block — what
+ * loss.backward() does for a loss that reads convnet.layerk's output. dh == NULL: no gradient reaches the embedding (zeros flow down
+ * from the pool). Staged calls carry the same dfeats array; the stage that owns an entry (stage 4 - k) reads it. An entry whose
+ * block has no work under the trainable mask (frozen prefix, no dx) is dropped. After an inference-mode forward: non-zero. */
+int r3m_resnet_backward_features(r3m_resnet_t h, const float* dh, const float* const dfeats[4], const float* params, float* grads,
+                                 void* arena, int stage_begin, int stage_end, int accumulate, float* dx, int dx_accumulate,
+                                 r3m_stream_t stream);
+/* The two kernels one by one (tests, tools/feature_bench.py). z / g: NHWC [N,H,W,C] fp32 (dtype 0) or bf16 (dtype 1); out / d: fp32
+ * NCHW [N,C,H,W]. export: out = z.permute(0,3,1,2).float(), bit for bit. grad_add: g = (g.float() + d.permute(0,2,3,1)).to(dtype),
+ * one fp32 add and one rounding per element, no atomics. C must be a multiple of 64, N, H, W >= 1. z / g must be 16-byte aligned;
+ * out / d need only float alignment, except for H * W = 1 (both layouts are the same bytes and both sides move 16 bytes at a
+ * time), where they must be 16-byte aligned too. Bad arguments return non-zero before any launch. */
+int r3m_feature_export_dt(const void* z_nhwc, float* out_nchw, int N, int H, int W, int C, int dtype, r3m_stream_t stream);
+int r3m_feature_grad_add_dt(const float* d_nchw, void* g_nhwc, int N, int H, int W, int C, int dtype, r3m_stream_t stream);
+
 /* ---------------- single operators (parity-tested one by one) -------------------------------------------------
  * conv2d fwd / dgrad / wgrad: ATen conv2d + autograd under torchvision ResNet.forward (call site models_r3m.py:99). */
 int r3m_conv2d_stats_rows(int N, int Hi, int Wi, int Co, int k, int stride, int pad);

@@ -54,6 +54,11 @@ SIGNATURES = {
     "r3m_resnet_set_bn_pair": (c_i, [C.c_void_p, c_i]),
     "r3m_resnet_backward": (c_i, [C.c_void_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f]),
     "r3m_resnet_backward_ex": (c_i, [C.c_void_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f]),
+    "r3m_resnet_feature_info": (c_i, [C.c_void_p, c_i] + [C.POINTER(c_i)] * 3),
+    "r3m_resnet_forward_features": (c_i, [C.c_void_p, c_f, c_f, c_f, c_f, c_f, C.POINTER(C.c_void_p), c_i, c_f]),
+    "r3m_resnet_backward_features": (c_i, [C.c_void_p, c_f, C.POINTER(C.c_void_p), c_f, c_f, c_f, c_i, c_i, c_i, c_f, c_i, c_f]),
+    "r3m_feature_export_dt": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_feature_grad_add_dt": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_conv2d_stats_rows": (c_i, [c_i] * 7),
     "r3m_conv2d_fwd": (c_i, [c_f, c_f, c_f, c_f] + [c_i] * 8 + [c_f]),
     "r3m_conv2d_dgrad_workspace_bytes": (c_sz, [c_i, c_i, c_i]),

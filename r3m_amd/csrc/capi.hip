@@ -273,6 +273,30 @@ int r3m_resnet_backward_ex(r3m_resnet_t h, const float* dh, const float* params,
   return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, S(stream), dx,
                        dx_accumulate);
 }
+int r3m_resnet_feature_info(r3m_resnet_t h, int layer, int* C, int* H, int* W) {
+  R3M_REQUIRE(h, "resnet_feature_info: null handle");
+  return plan_feature_info(PLAN(h), layer, C, H, W);
+}
+int r3m_resnet_forward_features(r3m_resnet_t h, const float* x, const float* params, float* buffers, void* arena, float* h_out,
+                                float* const feats[4], int training, r3m_stream_t stream) {
+  R3M_REQUIRE(h && x && params && buffers && arena && h_out, "resnet_forward_features: null argument");
+  R3M_REQUIRE(training >= 0 && training <= 2, "resnet_forward_features: training=%d (0 eval, 1 train, 2 inference)", training);
+  return plan_forward(*PLAN(h), x, nullptr, params, buffers, static_cast<float*>(arena), h_out, training, S(stream), feats);
+}
+int r3m_resnet_backward_features(r3m_resnet_t h, const float* dh, const float* const dfeats[4], const float* params, float* grads,
+                                 void* arena, int stage_begin, int stage_end, int accumulate, float* dx, int dx_accumulate,
+                                 r3m_stream_t stream) {
+  R3M_REQUIRE(h && params && arena, "resnet_backward_features: null argument");
+  R3M_REQUIRE(0 <= stage_begin && stage_begin <= stage_end && stage_end <= 4, "resnet_backward_features: stages [%d,%d)", stage_begin, stage_end);
+  return plan_backward(*PLAN(h), dh, params, grads, static_cast<float*>(arena), stage_begin, stage_end, accumulate, S(stream), dx,
+                       dx_accumulate, dfeats);
+}
+int r3m_feature_export_dt(const void* z_nhwc, float* out_nchw, int N, int H, int W, int C, int dtype, r3m_stream_t stream) {
+  return launch_feature_export(z_nhwc, out_nchw, N, H, W, C, dtype, S(stream));
+}
+int r3m_feature_grad_add_dt(const float* d_nchw, void* g_nhwc, int N, int H, int W, int C, int dtype, r3m_stream_t stream) {
+  return launch_feature_grad_add(d_nchw, g_nhwc, N, H, W, C, dtype, S(stream));
+}
 int r3m_resnet_set_trainable(r3m_resnet_t h, const unsigned char* mask, int n) {
   R3M_REQUIRE(h, "resnet_set_trainable: null handle");
   return plan_set_trainable(PLAN(h), mask, n);

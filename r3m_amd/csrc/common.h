@@ -273,6 +273,11 @@ int launch_maxpool_bwd(const void* dP, const unsigned char* amax, void* dZ, int 
 int launch_avgpool_fwd(const void* X, float* H, int N, int HW, int C, int dt, hipStream_t s);
 int launch_avgpool_bwd(const float* dH, void* dX, int N, int HW, int C, int dt, hipStream_t s);
 
+// ---- launchers (feat.hip): stage outputs out of / their gradients into the NHWC arena, fp32 NCHW on the caller's side ----
+// out[n][c][p] = (float) z[n][p][c]; g[n][p][c] = store(load(g[n][p][c]) + d[n][c][p]). C a multiple of 64, any H x W.
+int launch_feature_export(const void* z_nhwc, float* out_nchw, int N, int H, int W, int C, int dt, hipStream_t s);
+int launch_feature_grad_add(const float* d_nchw, void* g_nhwc, int N, int H, int W, int C, int dt, hipStream_t s);
+
 // ---- losses (loss.hip) and optimizers (adam.hip) ----
 size_t loss_workspace_floats(int B);
 int launch_tcn_lp_loss(const float* alle, const int* perm, const int* iperm, float* dalle, float* ws, int B, int D, int l2dist,

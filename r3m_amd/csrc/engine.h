@@ -55,10 +55,15 @@ Plan* plan_create(int size, int F, int dtype, int H, int W);
 void plan_destroy(Plan* P);
 // frames come either as [F,3,H,W] fp32 0..255 (x_nchw, crop == nullptr) or as raw clips + crop boxes (crop: rc / rctraj resampled
 // inside the stem pre-pass; 224 x 224 plans only)
+// feats (optional): feats[k-1] != null receives torchvision layer`k`'s output as fp32 NCHW [F, C_k, H_k, W_k] (plan_feature_info),
+// exported right behind the stage's last block on s; frames through x_nchw only
 int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena, float* h_out,
-                 int training, hipStream_t s);
+                 int training, hipStream_t s, float* const* feats = nullptr);
+// dh == nullptr: the embedding received no gradient. dfeats (optional): dfeats[k-1] != null is the gradient w.r.t. that output of
+// the forward, fp32 NCHW; every staged call carries the same array, the stage that owns an entry (stage 4 - k) reads it
 int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
-                  int accumulate, hipStream_t s, float* dx, int dx_accumulate);
+                  int accumulate, hipStream_t s, float* dx, int dx_accumulate, const float* const* dfeats = nullptr);
+int plan_feature_info(Plan* P, int layer, int* C, int* H, int* W);
 int plan_out_dim(Plan* P);
 int plan_input_hw(Plan* P, int* H, int* W);
 int plan_num_convs(Plan* P);

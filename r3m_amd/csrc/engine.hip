@@ -701,8 +701,11 @@ static int block_forward_fused(Ctx& c, const BlockSpec& B, float* Xin, float** o
   return conv_bn_fused(c, P.convs[B.conv[B.nconv - 1]], cur, res, EPI_AFFINE | EPI_ACCUM | EPI_RELU);
 }
 
+// the last block of its stage: its output is torchvision's layer`stage + 1` output
+static bool ends_stage(const Plan& P, size_t bi) { return bi + 1 == P.blocks.size() || P.blocks[bi + 1].stage != P.blocks[bi].stage; }
+
 int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena, float* h_out,
-                 int training, hipStream_t s) {
+                 int training, hipStream_t s, float* const* feats) {
   // training: 1 = batch statistics (+ running-statistics update), 0 = running statistics with everything a backward needs kept,
   // 2 = INFERENCE (round 6): running statistics, nothing kept — BatchNorm, residual join and ReLU ride in the convolutions' stores
   const bool infer = training == 2;
@@ -710,6 +713,7 @@ int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const fl
   Ctx c{P, P.run, params, nullptr, bufs, arena, s, training, 0, P.dtype};
   R3M_REQUIRE(!crop || (P.H == 224 && P.W == 224), "resnet_forward_crop: the crops are 224 x 224 but this plan takes %d x %d frames "
               "(create it for 224 x 224)", P.H, P.W);
+  R3M_REQUIRE(!(crop && feats), "resnet_forward_crop: feature maps are not available on the crop-fed forward");
   c.R.last_training = training;
   c.R.last_crop = crop ? 1 : 0;
   c.R.next_stage = infer ? -3 : 0;   // a new forward invalidates whatever an unfinished backward left behind (-3: nothing to differentiate)
@@ -719,13 +723,17 @@ int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const fl
   TRY(stem_forward(c, x_nchw, crop));
   const bool fused = infer && g_fused_inference;
   float* cur = arena + P.blocks[0].in_off;
-  for (const BlockSpec& B : P.blocks) {
+  for (size_t bi = 0; bi < P.blocks.size(); ++bi) {
+    const BlockSpec& B = P.blocks[bi];
     if (fused && block_fusable(c, B)) {
       TRY(block_forward_fused(c, B, cur, &cur));
     } else {
       TRY(block_forward(c, B, cur, fused ? nullptr : reinterpret_cast<unsigned*>(arena + B.mask_off)));
       cur = arena + B.out_off;
     }
+    // a requested stage output leaves here, behind the stage's last block: in the fused sequence `cur` is a block input or a
+    // downsample result that the next identity block overwrites in place
+    if (feats && feats[B.stage] && ends_stage(P, bi)) TRY(launch_feature_export(cur, feats[B.stage], P.F, B.Ho, B.Wo, B.Co, c.dt, s));
   }
   const BlockSpec& last = P.blocks.back();
   return launch_avgpool_fwd(cur, h_out, P.F, last.Ho * last.Wo, last.Co, c.dt, s);
@@ -1051,8 +1059,15 @@ static bool block_has_work(const Plan& P, const std::vector<int>& work, const Bl
 // dx != nullptr: d/d(frames) [F,3,H,W] fp32 NCHW of the frames of the last forward (stem_dgrad.hip), written (dx_accumulate = 0)
 // or added by stage 3. The call that runs stage 0 fixes the work of all four stages (backward_work) from the plan's trainable mask
 // and from whether it was given dx; a stage without work enqueues nothing.
+//
+// Stage-output gradients (dfeats): the gradient of layer`k`'s output joins the running output gradient G(0) right before
+// block_backward of that stage's last block — behind the pool's backward (or, without dh, a zero fill) for k = 4, at the top of
+// stages 1..3 for k = 3..1. There G(0) is complete: its producer is the pool or a downsample block (conv1's dgrad + the downsample's
+// accumulate), neither of which leaves EPI_BNRED partials, so the block's last BatchNorm runs its stand-alone first pass on the sum.
+// The output is post-ReLU, so adding before the block applies its mask is autograd's sum at that node. A block without work
+// (frozen prefix) drops the gradient, as autograd does.
 int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
-                  int accumulate, hipStream_t s, float* dx, int dx_accumulate) {
+                  int accumulate, hipStream_t s, float* dx, int dx_accumulate, const float* const* dfeats) {
   RunState& R = P.run;
   Ctx c{P, R, params, grads, nullptr, arena, s, R.last_training, accumulate, P.dtype};
   R3M_REQUIRE(stage_begin >= 0 && stage_end <= 4 && stage_begin < stage_end, "resnet_backward: stages [%d, %d) outside [0, 4)", stage_begin, stage_end);
@@ -1092,10 +1107,22 @@ int plan_backward(Plan& P, const float* dh, const float* params, float* grads, f
       R.a_next = 0;
       R.side.restart();
       R.dout_fused_rows = 0;     // the last block's output gradient comes from the pool: its BatchNorm runs the stand-alone reduce
-      if (any_work) TRY(launch_avgpool_bwd(dh, c.G(0), P.F, last.Ho * last.Wo, last.Co, c.dt, s));
+      if (any_work && dh) TRY(launch_avgpool_bwd(dh, c.G(0), P.F, last.Ho * last.Wo, last.Co, c.dt, s));
+      if (any_work && !dh) {       // the embedding received no gradient
+        const size_t bytes = (size_t)P.F * last.Ho * last.Wo * last.Co * (c.dt == DT_BF16 ? 2 : 4);
+        if (hipMemsetAsync(c.G(0), 0, bytes, s) != hipSuccess) { set_last_error("resnet_backward: cannot clear the output gradient"); return 1; }
+      }
     }
-    for (int bi = (int)P.blocks.size() - 1; bi >= 0; --bi)
-      if (P.blocks[bi].stage == 3 - st && block_has_work(P, R.work, P.blocks[bi])) TRY(block_backward(c, bi));
+    for (int bi = (int)P.blocks.size() - 1; bi >= 0; --bi) {
+      const BlockSpec& B = P.blocks[bi];
+      if (B.stage != 3 - st || !block_has_work(P, R.work, B)) continue;
+      if (dfeats && dfeats[B.stage] && ends_stage(P, bi)) {
+        R3M_REQUIRE(R.dout_fused_rows == 0, "resnet_backward: BatchNorm partials of layer%d's output gradient were formed before the "
+                    "feature-map gradient joined it", B.stage + 1);
+        TRY(launch_feature_grad_add(dfeats[B.stage], c.G(0), P.F, B.Ho, B.Wo, B.Co, c.dt, s));
+      }
+      TRY(block_backward(c, bi));
+    }
     if (st == 3 && stem_work) TRY(stem_backward(c, dx, dx_accumulate, dx ? stem_work : stem_work & ~BW_DGRAD));
     TRY(R.side.join());     // a finished stage's gradients are complete on the main stream (all-reduce hook, Adam)
   }
@@ -1117,6 +1144,19 @@ int plan_conv_info(Plan* P, int i, int* geo10) {
   const int v[10] = {c.Ci, c.Co, c.k, c.stride, c.pad, c.Hi, c.Wi, c.Ho, c.Wo, 0};
   for (int k = 0; k < 10; ++k) geo10[k] = v[k];
   return 0;
+}
+int plan_feature_info(Plan* P, int layer, int* C, int* H, int* W) {
+  R3M_REQUIRE(layer >= 1 && layer <= 4, "feature_info: layer %d outside 1..4", layer);
+  for (size_t bi = 0; bi < P->blocks.size(); ++bi) {
+    const BlockSpec& B = P->blocks[bi];
+    if (B.stage != layer - 1 || !ends_stage(*P, bi)) continue;
+    if (C) *C = B.Co;
+    if (H) *H = B.Ho;
+    if (W) *W = B.Wo;
+    return 0;
+  }
+  set_last_error("feature_info: the plan has no layer%d", layer);
+  return 1;
 }
 int plan_dtype(Plan* P) { return P->dtype; }
 long long plan_num_params(Plan* P) { return P->n_params; }

@@ -83,6 +83,56 @@ class _EncoderFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
+FEATURE_LAYERS = ("layer1", "layer2", "layer3", "layer4")   # torchvision's stages: feature map k is convnet.layerk's output
+
+
+class _NoEmbeddingGrad:
+    """Stands in for dh in a backward whose loss did not use the embedding: a null pointer on the device of the feature-map
+    gradients (r3m_resnet_backward_features: dh == NULL, zeros flow down from the pool instead of a zero tensor through a kernel)."""
+
+    def __init__(self, device):
+        self.device = device
+
+    def contiguous(self):
+        return self
+
+    def data_ptr(self):
+        return None
+
+
+class _FeaturesFn(torch.autograd.Function):
+    """(h, *maps) = encoder(x) with the requested stage outputs as fp32 NCHW tensors. The slot, generation and stage-hook
+    bookkeeping is _EncoderFn's own code, run on this node's ctx; the maps and their gradients travel through the module
+    (_feat_request -> _run_forward -> _feat_result, _feat_grads -> _run_backward)."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, module, training, layers):
+        ctx.set_materialize_grads(False)     # an output the loss did not use arrives as None -> a null pointer, not a zero tensor
+        module._feat_request = layers
+        try:
+            h = _EncoderFn.forward(ctx, x, anchor, module, training)
+        finally:
+            module._feat_request = None
+        maps, module._feat_result = module._feat_result, None
+        ctx.layers = layers
+        return (h,) + tuple(maps[k] for k in layers)
+
+    @staticmethod
+    def backward(ctx, dh, *dmaps):
+        m = ctx.module
+        grads = [None] * 4
+        for k, d in zip(ctx.layers, dmaps):
+            if d is not None:
+                grads[k] = d.contiguous() if d.dtype == torch.float32 else d.float().contiguous()
+        if dh is None:
+            dh = _NoEmbeddingGrad(next(g for g in grads if g is not None).device)
+        m._feat_grads = grads
+        try:
+            return _EncoderFn.backward(ctx, dh)
+        finally:
+            m._feat_grads = None
+
+
 PRECISIONS = {"fp32": 0, "bf16": 1}   # R3M_DT_F32 / R3M_DT_BF16 (include/r3m_hip.h)
 
 
@@ -183,6 +233,9 @@ class HipResNet(nn.Module):
         self._g_viewed = [False] * len(self._param_ranges)      # flat_grads() has given this tensor its .grad view
         self._plan_masks = {}     # native handle -> the trainable mask it was last given (absent: all trainable, the plan's default)
         self._stage_hook = None   # callable(stage, offset, count) after each backward stage (data-parallel wrapper)
+        # forward_features: the stage outputs the running call wants (indices 0..3), what its forward produced ({index: [F,C,H,W]}),
+        # and the gradients its backward was handed ([4], None = none); all None outside such a call
+        self._feat_request = self._feat_result = self._feat_grads = None
         self.reset_parameters()
 
     @property
@@ -493,7 +546,8 @@ class HipResNet(nn.Module):
 
     def _run_forward(self, x, training, crop=None, saved=False):
         """x: [F,3,H,W] fp32 frames, or None with crop = augment.CroppedClips (raw clips + boxes, resampled in the stem pre-pass).
-        saved: the call comes from autograd (_EncoderFn) and a backward will read this forward's activations."""
+        saved: the call comes from autograd (_EncoderFn) and a backward will read this forward's activations.
+        Inside forward_features (self._feat_request set) the requested stage outputs are left in self._feat_result."""
         L = _lib.lib()
         src = crop.raw if crop is not None else x
         F = src.shape[0]
@@ -512,8 +566,16 @@ class HipResNet(nn.Module):
         # 1 train / 0 eval with the activations kept for a backward / 2 inference: eval statistics and nothing kept — BatchNorm, residual
         # join and ReLU ride in the convolutions' stores (what load_r3m(...).eval() under no_grad runs, /root/reference/r3m/__init__.py:72-75)
         mode = 1 if training else (0 if saved else 2)
+        want = self._feat_request
         with _lib.on(src):
-            if crop is not None:
+            if want is not None:
+                maps = {k: torch.empty((F,) + self._feature_shape(h, k), dtype=torch.float32, device=src.device) for k in want}
+                ptrs = (C.c_void_p * 4)(*[_lib.ptr(maps.get(k)) for k in range(4)])
+                _lib.check(L.r3m_resnet_forward_features(h, x.data_ptr(), self._flat_p.data_ptr(), self._flat_b.data_ptr(),
+                                                         arena.data_ptr(), out.data_ptr(), ptrs, mode, _lib.stream_ptr(x.device)),
+                           "resnet_forward_features")
+                self._feat_result = maps
+            elif crop is not None:
                 _lib.check(L.r3m_resnet_forward_crop(h, crop.raw.data_ptr(), 1 if crop.raw.dtype == torch.uint8 else 0,
                                                      crop.boxes.data_ptr(), crop.frames_per_box, crop.raw.shape[-2], crop.raw.shape[-1],
                                                      self._flat_p.data_ptr(), self._flat_b.data_ptr(), arena.data_ptr(),
@@ -534,7 +596,8 @@ class HipResNet(nn.Module):
         """params: write the gradients of the parameters that require grad into the flat gradient buffer (False: frozen encoder — no
         weight-gradient launch, the buffer is neither created nor touched, no stage hook fires). With some parameters frozen the
         engine runs only what the trainable ones (and the input gradient) need; all four stage hooks still fire, in order.
-        input_grad: return d/d(frames) [F,3,H,W] fp32."""
+        input_grad: return d/d(frames) [F,3,H,W] fp32.
+        Inside a forward_features backward (self._feat_grads set) the stage outputs' gradients join, and dh may be the null stand-in."""
         slot = self._slot(si)
         if generation != slot.generation or slot.arena is None:
             raise RuntimeError(f"r3m_amd: the encoder ran {len(self._ring)} other forward(s) before this backward; its saved "
@@ -546,9 +609,15 @@ class HipResNet(nn.Module):
         accumulate = 0 if self._grad_fresh else 1
         partial = self._begin_param_backward(h) if params else False
         dx = torch.empty((slot.F, 3) + tuple(slot.hw), dtype=torch.float32, device=dh.device) if input_grad else None
+        dmaps = None if self._feat_grads is None else (C.c_void_p * 4)(*[_lib.ptr(d) for d in self._feat_grads])
         with _lib.on(dh):
             for stage in range(4):
-                if g is not None and dx is None:     # the pre-training path: unchanged launch sequence
+                if dmaps is not None:                # every stage carries the same array; the stage that owns an entry reads it
+                    _lib.check(L.r3m_resnet_backward_features(h, dh.data_ptr(), dmaps, self._flat_p.data_ptr(), _lib.ptr(g),
+                                                              slot.arena.data_ptr(), stage, stage + 1, accumulate,
+                                                              _lib.ptr(dx) if stage == 3 or partial else None, 0,
+                                                              _lib.stream_ptr(dh.device)), "resnet_backward_features")
+                elif g is not None and dx is None:   # the pre-training path: unchanged launch sequence
                     _lib.check(L.r3m_resnet_backward(h, dh.data_ptr(), self._flat_p.data_ptr(), g.data_ptr(), slot.arena.data_ptr(),
                                                      stage, stage + 1, accumulate, _lib.stream_ptr(dh.device)), "resnet_backward")
                 else:
@@ -562,6 +631,59 @@ class HipResNet(nn.Module):
         if g is not None:
             self._grad_fresh = False
         return dx
+
+    @staticmethod
+    def _feature_shape(h, k):
+        """(C, H, W) of stage output k (0..3 = layer1..layer4) of native plan h"""
+        c, hh, ww = C.c_int(), C.c_int(), C.c_int()
+        _lib.check(_lib.lib().r3m_resnet_feature_info(h, k + 1, C.byref(c), C.byref(hh), C.byref(ww)), "resnet_feature_info")
+        return c.value, hh.value, ww.value
+
+    def forward_features(self, x, layers=FEATURE_LAYERS):
+        """forward(x) plus the spatial feature maps: returns (h, {name: [F, C_k, H_k, W_k] fp32 NCHW}) for the requested `layers`
+        (names out of layer1..layer4) — the outputs of torchvision's convnet.layerk, what a forward hook on the reference's
+        convnet.layer4 or nn.Sequential(*list(convnet.children())[:-2]) gives (models_r3m.py:44-52). Differentiable like forward():
+        a loss on any mix of h and the maps backpropagates into the parameters that require grad and into x. Train, eval with grad,
+        and no_grad inference; both precisions (bf16 maps are the stored activations widened, exactly). x as for forward(), except
+        that CroppedClips input is not supported."""
+        layers = tuple(layers)
+        for i, name in enumerate(layers):
+            if name not in FEATURE_LAYERS:
+                raise ValueError(f"forward_features: unknown layer {name!r} (expected names out of {FEATURE_LAYERS})")
+            if name in layers[:i]:
+                raise ValueError(f"forward_features: layer {name!r} requested twice")
+        from .augment import CroppedClips
+        if isinstance(x, CroppedClips):
+            raise TypeError("forward_features: CroppedClips input is not supported (the crop-fed forward exports no feature maps); "
+                            "resample the clips first and pass [F,3,H,W] frames")
+        if not x.is_cuda:
+            raise RuntimeError("r3m_amd: the encoder runs on MI355X through libr3m_hip.so only; got a CPU tensor "
+                               "(no CPU / eager fallback exists — the CPU oracle lives under oracle/ for tests)")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
+            raise ValueError(f"expected [F,3,H,W] frames, got {tuple(x.shape)}")
+        if tuple(x.shape[2:]) != (224, 224):
+            self.check_input_hw(x.shape[2], x.shape[3])
+        self._ensure()
+        if self._flat_p.device != x.device:
+            raise RuntimeError(f"encoder parameters on {self._flat_p.device}, input on {x.device}")
+        x = x.contiguous()
+        if x.dtype != torch.float32:
+            x = x.float()
+        idx = tuple(FEATURE_LAYERS.index(name) for name in layers)
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or x.requires_grad):
+            anchor = next((p for p in self.parameters() if p.requires_grad), None)
+            if anchor is None:
+                anchor = next(self.parameters())
+            h, *maps = _FeaturesFn.apply(x, anchor, self, self.training, idx)
+        else:
+            self._feat_request = idx
+            try:
+                h = self._run_forward(x, self.training)
+            finally:
+                self._feat_request = None
+            got, self._feat_result = self._feat_result, None
+            maps = [got[k] for k in idx]
+        return h, dict(zip(layers, maps))
 
     def forward(self, x):
         """x: [F,3,H,W] float32 CUDA tensor with values in 0..255, any H and W in 32..512 (torchvision's ResNet takes any size; 224 x 224

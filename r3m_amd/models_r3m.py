@@ -83,6 +83,14 @@ class R3M(nn.Module):
         # in 32..512; HipResNet.forward)
         return self.convnet(obs)
 
+    def forward_features(self, obs, layers=("layer1", "layer2", "layer3", "layer4"), obs_shape=[3, 224, 224]):
+        """forward(obs) plus the outputs of convnet.layer1..layer4 (what a forward hook on the reference's convnet.layerk gives,
+        models_r3m.py:44-52): (h, {name: [F, C, H, W] fp32 NCHW}), differentiable; HipResNet.forward_features"""
+        if list(obs_shape) != [3, 224, 224]:
+            from .augment import resize_center_crop          # the same Resize(256) + CenterCrop(224) branch as forward
+            obs = resize_center_crop(obs.reshape(-1, *obs.shape[-3:]))
+        return self.convnet.forward_features(obs, layers)
+
     def sim(self, tensor1, tensor2):
         if self.l2dist:
             return -torch.linalg.norm(tensor1 - tensor2, dim=-1)
