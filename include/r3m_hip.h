@@ -487,6 +487,36 @@ int r3m_sgd_step_ranges(float* params, const float* grads, float* momentum_buf, 
                         const long long* step, int n_ranges, double lr, double momentum, double dampening, double weight_decay,
                         int nesterov, float grad_scale, r3m_stream_t stream);
 
+/* ---------------- parameter groups, weight decay and gradient clipping on the flat buffers ----------------
+ * Sum of squares of the fp32 gradients over n_ranges ranges (HOST arrays, checked as above, no step counts), accumulated in fp64:
+ * what torch.nn.utils.clip_grad_norm_ squares and adds, without its ~2 launches per tensor. *sqnorm (DEVICE, one double) is
+ * written (accumulate == 0) or added to (accumulate != 0): chain calls over several flat buffers for one global norm. Two launches
+ * per 64 ranges (one partial per block into `workspace`, then one block adds the partials in a fixed order); no atomics: the same
+ * gradients give the same bits on every run and every rank. n_ranges == 0: accumulate ? nothing : *sqnorm = 0. */
+size_t r3m_grad_sqnorm_workspace_bytes(void);
+int r3m_grad_sqnorm_ranges(const float* grads, const long long* off, const long long* count, int n_ranges, double* sqnorm,
+                           int accumulate, void* workspace, size_t workspace_bytes, r3m_stream_t stream);
+/* coef_norm (DEVICE, two floats) = { min(1, max_norm / (norm + 1e-6)), norm } with norm = grad_scale * sqrt(*sqnorm), formed in double
+ * and rounded once: clip_grad_norm_'s coefficient (its 1e-6 included; error_if_nonfinite=False: a non-finite norm is not treated
+ * specially) and the norm before clipping, of the gradients scaled by grad_scale. */
+int r3m_clip_coef(const double* sqnorm, double max_norm, float grad_scale, float* coef_norm, r3m_stream_t stream);
+/* The ranged steps with a learning rate and a weight decay per range (HOST double arrays, >= 0) and an optional clip coefficient
+ * (DEVICE float, coef_norm above; NULL: no multiplication): parameter groups of torch.optim.Adam(weight_decay=) (decoupled == 0:
+ * g += wd * p), torch.optim.AdamW (decoupled == 1: p *= (float)(1 - lr * wd) before the update) and torch.optim.SGD, after
+ * clip_grad_norm_. Per element g' = (g * grad_scale) * coef, then the decay, then the arithmetic of r3m_adam_step / r3m_sgd_step.
+ * One launch per 64 ranges. A range with weight_decay 0 skips the decay operation: with every weight_decay 0, one lr and a NULL
+ * coefficient the result is bit for bit that of r3m_adam_step_ranges / r3m_sgd_step_ranges (r3m_sgd_step_groups also with one
+ * non-zero weight_decay). A coefficient of exactly 1.0f gives the bits of NULL whenever g * grad_scale is exact (grad_scale a power of
+ * two, as 1 / world_size usually is); otherwise the fused g * grad_scale - m of the plain step may differ from it by one rounding.
+ * Bad ranges, step < 1, a negative (or NaN) lr or weight_decay return non-zero before anything is launched. */
+int r3m_adam_step_groups(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, const long long* off,
+                         const long long* count, const long long* step, const double* lr, const double* weight_decay, int n_ranges,
+                         double beta1, double beta2, double eps, int decoupled, float grad_scale, const float* clip_coef,
+                         r3m_stream_t stream);
+int r3m_sgd_step_groups(float* params, const float* grads, float* momentum_buf, const long long* off, const long long* count,
+                        const long long* step, const double* lr, const double* weight_decay, int n_ranges, double momentum,
+                        double dampening, int nesterov, float grad_scale, const float* clip_coef, r3m_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

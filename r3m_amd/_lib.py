@@ -144,6 +144,12 @@ SIGNATURES = {
     "r3m_sgd_step": (c_i, [c_f, c_f, c_f, c_ll, c_d, c_d, c_d, c_d, c_i, c_ll, c_fl, c_f]),
     "r3m_adam_step_ranges": (c_i, [c_f, c_f, c_f, c_f] + [C.POINTER(c_ll)] * 3 + [c_i, c_d, c_d, c_d, c_d, c_fl, c_f]),
     "r3m_sgd_step_ranges": (c_i, [c_f, c_f, c_f] + [C.POINTER(c_ll)] * 3 + [c_i, c_d, c_d, c_d, c_d, c_i, c_fl, c_f]),
+    "r3m_grad_sqnorm_workspace_bytes": (c_sz, []),
+    "r3m_grad_sqnorm_ranges": (c_i, [c_f] + [C.POINTER(c_ll)] * 2 + [c_i, c_f, c_i, c_f, c_sz, c_f]),
+    "r3m_clip_coef": (c_i, [c_f, c_d, c_fl, c_f, c_f]),
+    "r3m_adam_step_groups": (c_i, [c_f, c_f, c_f, c_f] + [C.POINTER(c_ll)] * 3 + [C.POINTER(c_d)] * 2 + [c_i, c_d, c_d, c_d, c_i, c_fl,
+                                                                                                          c_f, c_f]),
+    "r3m_sgd_step_groups": (c_i, [c_f, c_f, c_f] + [C.POINTER(c_ll)] * 3 + [C.POINTER(c_d)] * 2 + [c_i, c_d, c_d, c_i, c_fl, c_f, c_f]),
 }
 
 

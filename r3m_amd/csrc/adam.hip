@@ -6,15 +6,23 @@
 // The *_ranges forms step only some [offset, count) ranges of the buffer, each with its own step count (partial-freeze
 // fine-tuning: torch.optim.Adam skips parameters without a gradient and keeps `step` per parameter). Both forms run the same
 // element loop (adam_span / sgd_span), so a range gets bit for bit what the whole-buffer kernel gives the same elements.
+//
+// The *_groups forms are the ranged steps of fine-tuning: a learning rate and a weight decay per range (parameter groups, AdamW / L2
+// decay) and an optional clip coefficient read from device memory; sqnorm_* and clip_coef_kernel form that coefficient
+// (torch.nn.utils.clip_grad_norm_) as a deterministic fp64 sum over ranges. All of it at the end of this file.
 #include "common.h"
 #include <cstring>
 
 namespace r3m {
 
-// f32x4 groups i, i + stride, ... < n4 of the buffers
-__device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                          long long i, long long stride, long long n4, float beta2, float one_minus_beta1,
-                                          float one_minus_beta2, float neg_step_size, float bc2_sqrt, float eps, float grad_scale) {
+// f32x4 groups i, i + stride, ... < n4 of the buffers.
+// COEF: the gradient is also multiplied by `coef` (gradient clipping). DECAY 1: gr += wd * p (torch.optim.Adam(weight_decay=)),
+// DECAY 2: p *= wd, wd = (float)(1 - lr * weight_decay) (AdamW), before the update. <false, 0> is the plain step: adam_span below.
+template <bool COEF, int DECAY>
+__device__ __forceinline__ void adam_span_t(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                            long long i, long long stride, long long n4, float beta2, float one_minus_beta1,
+                                            float one_minus_beta2, float neg_step_size, float bc2_sqrt, float eps, float grad_scale,
+                                            float coef, float wd) {
   for (; i < n4; i += stride) {
     f32x4 pp = *reinterpret_cast<f32x4*>(p + i * 4);
     f32x4 gg = *reinterpret_cast<const f32x4*>(g + i * 4);
@@ -22,7 +30,10 @@ __device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __
     f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float gr = gg[e] * grad_scale;
+      float gr = gg[e] * grad_scale;
+      if (COEF) gr = gr * coef;
+      if (DECAY == 1) gr = gr + wd * pp[e];
+      if (DECAY == 2) pp[e] = pp[e] * wd;
       // exp_avg.lerp_(grad, 1-beta1); exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
       mm[e] = mm[e] + (gr - mm[e]) * one_minus_beta1;
       vv[e] = vv[e] * beta2 + (one_minus_beta2 * gr) * gr;
@@ -34,6 +45,11 @@ __device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __
     *reinterpret_cast<f32x4*>(m + i * 4) = mm;
     *reinterpret_cast<f32x4*>(v + i * 4) = vv;
   }
+}
+__device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                          long long i, long long stride, long long n4, float beta2, float one_minus_beta1,
+                                          float one_minus_beta2, float neg_step_size, float bc2_sqrt, float eps, float grad_scale) {
+  adam_span_t<false, 0>(p, g, m, v, i, stride, n4, beta2, one_minus_beta1, one_minus_beta2, neg_step_size, bc2_sqrt, eps, grad_scale, 0.f, 0.f);
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -100,16 +116,18 @@ __global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p,
 }
 
 // host checks shared by both optimizers; nothing is launched when one fails
-static int check_ranges(const char* what, const long long* off, const long long* count, const long long* step, int n_ranges) {
+// (with_step = false: ranges without step counts, the gradient norm)
+static int check_ranges(const char* what, const long long* off, const long long* count, const long long* step, int n_ranges,
+                        bool with_step = true) {
   R3M_REQUIRE(n_ranges >= 0, "%s: n_ranges=%d", what, n_ranges);
-  R3M_REQUIRE(n_ranges == 0 || (off && count && step), "%s: null range arrays", what);
+  R3M_REQUIRE(n_ranges == 0 || (off && count && (step || !with_step)), "%s: null range arrays", what);
   long long end = 0;
   for (int i = 0; i < n_ranges; ++i) {
     R3M_REQUIRE(off[i] >= 0 && count[i] >= 0 && off[i] % 4 == 0 && count[i] % 4 == 0,
                 "%s: range %d = [%lld, +%lld): offsets and counts must be non-negative multiples of 4", what, i, off[i], count[i]);
     R3M_REQUIRE(off[i] >= end, "%s: range %d starts at %lld, before the end %lld of the range before it (ranges must be sorted and disjoint)",
                 what, i, off[i], end);
-    R3M_REQUIRE(step[i] >= 1, "%s: range %d has step=%lld, must be >= 1", what, i, step[i]);
+    R3M_REQUIRE(!with_step || step[i] >= 1, "%s: range %d has step=%lld, must be >= 1", what, i, step[i]);
     end = off[i] + count[i];
   }
   return 0;
@@ -151,9 +169,11 @@ int launch_adam_ranges(float* p, const float* g, float* m, float* v, const long 
 //   g' = g*grad_scale + wd*p ; buf = (first step) g' : momentum*buf + (1-dampening)*g' ; d = nesterov ? g' + momentum*buf : buf ; p -= lr*d
 // The reference trains with Adam only (models_r3m.py:76); BASELINE.json's north_star names "the SGD/Adam step", so the plain
 // optimizer is provided on the same flat-buffer layout (one HBM pass: read p, g, buf - write p, buf).
-__device__ __forceinline__ void sgd_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long i,
-                                         long long stride, long long n4, float lr, float momentum, float one_minus_damp, float wd,
-                                         int nesterov, int first, float grad_scale) {
+// COEF: the gradient is also multiplied by `coef` (gradient clipping); <false> is the plain step: sgd_span below.
+template <bool COEF>
+__device__ __forceinline__ void sgd_span_t(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long i,
+                                           long long stride, long long n4, float lr, float momentum, float one_minus_damp, float wd,
+                                           int nesterov, int first, float grad_scale, float coef) {
   for (; i < n4; i += stride) {
     f32x4 pp = *reinterpret_cast<f32x4*>(p + i * 4);
     const f32x4 gg = *reinterpret_cast<const f32x4*>(g + i * 4);
@@ -162,6 +182,7 @@ __device__ __forceinline__ void sgd_span(float* __restrict__ p, const float* __r
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float gr = gg[e] * grad_scale;
+      if (COEF) gr = gr * coef;
       if (wd != 0.f) gr = gr + wd * pp[e];
       float d = gr;
       if (buf) {
@@ -173,6 +194,11 @@ __device__ __forceinline__ void sgd_span(float* __restrict__ p, const float* __r
     *reinterpret_cast<f32x4*>(p + i * 4) = pp;
     if (buf) *reinterpret_cast<f32x4*>(buf + i * 4) = bb;
   }
+}
+__device__ __forceinline__ void sgd_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long i,
+                                         long long stride, long long n4, float lr, float momentum, float one_minus_damp, float wd,
+                                         int nesterov, int first, float grad_scale) {
+  sgd_span_t<false>(p, g, buf, i, stride, n4, lr, momentum, one_minus_damp, wd, nesterov, first, grad_scale, 0.f);
 }
 
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long n4,
@@ -225,6 +251,206 @@ int launch_sgd_ranges(float* p, const float* g, float* momentum_buf, const long 
     if (int e = check_launch("sgd_ranges")) return e;
   }
   return 0;
+}
+
+// ---- grouped steps: a learning rate and a weight decay per range, and an optional clip coefficient -----------------------------
+// The fine-tuning forms of the ranged steps (parameter groups: torch.optim.AdamW / Adam(weight_decay=) / SGD with per-group lr and
+// weight_decay, after torch.nn.utils.clip_grad_norm_). The table gains one float per range; a block picks the element loop of its
+// range: a range without decay and a launch without coefficient run adam_span / sgd_span themselves, so they give the bits of
+// r3m_adam_step_ranges / r3m_sgd_step_ranges.
+struct GroupTable {
+  RangeTable r;                       // Adam: a = -lr_r / bias_correction1, b = sqrt(bias_correction2) ; SGD: a = first step, b = lr_r
+  float wd[OPT_MAX_RANGES];           // Adam L2 and SGD: weight_decay_r ; AdamW: (float)(1 - lr_r * weight_decay_r), 1.f = no decay
+};
+static_assert(sizeof(GroupTable) == sizeof(RangeTable) + 256 && sizeof(GroupTable) + 64 <= 4096,
+              "the range table travels in the kernel arguments (4 KiB)");
+
+template <bool COEF>
+__device__ __forceinline__ void adam_group_block(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                 float* __restrict__ v, const GroupTable& t, float beta2, float one_minus_beta1,
+                                                 float one_minus_beta2, float eps, float grad_scale, float coef, int decoupled) {
+  const int r = range_of_block(t.r);
+  const long long o = t.r.off4[r] * 4;
+  const int blocks = t.r.first_block[r + 1] - t.r.first_block[r];
+  const long long i = (long long)(blockIdx.x - t.r.first_block[r]) * 256 + threadIdx.x, stride = (long long)blocks * 256;
+  const float wd = t.wd[r];
+  if (decoupled ? wd == 1.f : wd == 0.f)
+    adam_span_t<COEF, 0>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.r.a[r], t.r.b[r], eps,
+                         grad_scale, coef, 0.f);
+  else if (decoupled)
+    adam_span_t<COEF, 2>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.r.a[r], t.r.b[r], eps,
+                         grad_scale, coef, wd);
+  else
+    adam_span_t<COEF, 1>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.r.a[r], t.r.b[r], eps,
+                         grad_scale, coef, wd);
+}
+
+__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const GroupTable t, float beta2, float one_minus_beta1,
+                                                           float one_minus_beta2, float eps, float grad_scale,
+                                                           const float* __restrict__ coef, int decoupled) {
+  if (coef)       // the same address for every lane: one scalar load
+    adam_group_block<true>(p, g, m, v, t, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, *coef, decoupled);
+  else
+    adam_group_block<false>(p, g, m, v, t, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, 0.f, decoupled);
+}
+
+__global__ __launch_bounds__(256) void sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                          const GroupTable t, float momentum, float one_minus_damp, int nesterov,
+                                                          float grad_scale, const float* __restrict__ coef) {
+  const int r = range_of_block(t.r);
+  const long long o = t.r.off4[r] * 4;
+  const int blocks = t.r.first_block[r + 1] - t.r.first_block[r];
+  const long long i = (long long)(blockIdx.x - t.r.first_block[r]) * 256 + threadIdx.x, stride = (long long)blocks * 256;
+  float* b = buf ? buf + o : nullptr;
+  if (coef)
+    sgd_span_t<true>(p + o, g + o, b, i, stride, t.r.n4[r], t.r.b[r], momentum, one_minus_damp, t.wd[r], nesterov, t.r.a[r] != 0.f, grad_scale,
+                     *coef);
+  else
+    sgd_span(p + o, g + o, b, i, stride, t.r.n4[r], t.r.b[r], momentum, one_minus_damp, t.wd[r], nesterov, t.r.a[r] != 0.f, grad_scale);
+}
+
+static int check_groups(const char* what, const long long* off, const long long* count, const long long* step, const double* lr,
+                        const double* weight_decay, int n_ranges) {
+  if (int e = check_ranges(what, off, count, step, n_ranges)) return e;
+  R3M_REQUIRE(n_ranges == 0 || (lr && weight_decay), "%s: null lr / weight_decay arrays", what);
+  for (int i = 0; i < n_ranges; ++i) {
+    R3M_REQUIRE(lr[i] >= 0.0, "%s: range %d has lr=%g, must be >= 0", what, i, lr[i]);
+    R3M_REQUIRE(weight_decay[i] >= 0.0, "%s: range %d has weight_decay=%g, must be >= 0", what, i, weight_decay[i]);
+  }
+  return 0;
+}
+
+int launch_adam_groups(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
+                       const double* lr, const double* weight_decay, int n_ranges, double beta1, double beta2, double eps, int decoupled,
+                       float grad_scale, const float* clip_coef, hipStream_t s) {
+  if (int e = check_groups("adam_groups", off, count, step, lr, weight_decay, n_ranges)) return e;
+  R3M_REQUIRE(n_ranges == 0 || (p && g && m && v), "adam_groups: null buffer");
+  for (int i = 0; i < n_ranges;) {
+    GroupTable t;
+    int src[OPT_MAX_RANGES];
+    const int grid = fill_ranges(t.r, off, count, n_ranges, &i, src);
+    if (!grid) break;
+    for (int r = 0; r < OPT_MAX_RANGES; ++r) t.wd[r] = 0.f;
+    for (int r = 0; r < t.r.n; ++r) {
+      const int k = src[r];
+      adam_bias_corrections(lr[k], beta1, beta2, step[k], &t.r.a[r], &t.r.b[r]);
+      // AdamW: param.mul_(1 - lr * weight_decay), the factor a python (double) scalar
+      t.wd[r] = decoupled ? (weight_decay[k] == 0.0 ? 1.f : (float)(1.0 - lr[k] * weight_decay[k])) : (float)weight_decay[k];
+    }
+    hipLaunchKernelGGL(adam_groups_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, t, (float)beta2, (float)(1.0 - beta1),
+                       (float)(1.0 - beta2), (float)eps, grad_scale, clip_coef, decoupled ? 1 : 0);
+    if (int e = check_launch("adam_groups")) return e;
+  }
+  return 0;
+}
+
+int launch_sgd_groups(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
+                      const double* lr, const double* weight_decay, int n_ranges, double momentum, double dampening, int nesterov,
+                      float grad_scale, const float* clip_coef, hipStream_t s) {
+  if (int e = check_groups("sgd_groups", off, count, step, lr, weight_decay, n_ranges)) return e;
+  if (int e = check_sgd(momentum, dampening, nesterov, momentum_buf)) return e;
+  R3M_REQUIRE(n_ranges == 0 || (p && g), "sgd_groups: null buffer");
+  for (int i = 0; i < n_ranges;) {
+    GroupTable t;
+    int src[OPT_MAX_RANGES];
+    const int grid = fill_ranges(t.r, off, count, n_ranges, &i, src);
+    if (!grid) break;
+    for (int r = 0; r < OPT_MAX_RANGES; ++r) t.wd[r] = 0.f;
+    for (int r = 0; r < t.r.n; ++r) {
+      const int k = src[r];
+      t.r.a[r] = step[k] == 1 ? 1.f : 0.f;
+      t.r.b[r] = (float)lr[k];
+      t.wd[r] = (float)weight_decay[k];
+    }
+    hipLaunchKernelGGL(sgd_groups_kernel, dim3(grid), dim3(256), 0, s, p, g, momentum != 0.0 ? momentum_buf : nullptr, t, (float)momentum,
+                       (float)(1.0 - dampening), nesterov, grad_scale, clip_coef);
+    if (int e = check_launch("sgd_groups")) return e;
+  }
+  return 0;
+}
+
+// ---- squared gradient norm over ranges (torch.nn.utils.clip_grad_norm_'s norm, without its ~2 launches per tensor) --------------
+// Deterministic fp64: blocks map to ranges as in the steps; a lane squares and adds its elements in double, in index order; the 64
+// lanes of a wave combine by a fixed shuffle tree, the 4 waves of the block in wave order; one partial per block. A second,
+// single-block kernel adds the partials (lane l: l, l + 256, ... in index order, then the same block combine) and writes the total
+// to *out or adds it to *out: a plain load, add and store by lane 0. No atomics: the same input gives the same bits every time.
+constexpr int SQNORM_MAX_BLOCKS = OPT_MAX_RANGES * 256 * 16;      // opt_grid's cap per range
+
+__device__ __forceinline__ double block_sum_256(double x, double* wave_sums) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d, 64);
+  if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = x;
+  __syncthreads();
+  return ((wave_sums[0] + wave_sums[1]) + wave_sums[2]) + wave_sums[3];      // every lane; lane 0 stores
+}
+
+__global__ __launch_bounds__(256) void sqnorm_ranges_kernel(const float* __restrict__ g, const RangeTable t, double* __restrict__ partial) {
+  __shared__ double wave_sums[4];
+  const int r = range_of_block(t);
+  const float* gr = g + t.off4[r] * 4;
+  const int blocks = t.first_block[r + 1] - t.first_block[r];
+  const long long stride = (long long)blocks * 256, n4 = t.n4[r];
+  double acc = 0.0;
+  for (long long i = (long long)(blockIdx.x - t.first_block[r]) * 256 + threadIdx.x; i < n4; i += stride) {
+    const f32x4 gg = *reinterpret_cast<const f32x4*>(gr + i * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double x = (double)gg[e];
+      acc = acc + x * x;
+    }
+  }
+  const double sum = block_sum_256(acc, wave_sums);
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(256) void sqnorm_finish_kernel(const double* __restrict__ partial, int n, double* __restrict__ out,
+                                                             int accumulate) {
+  __shared__ double wave_sums[4];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc = acc + partial[i];
+  const double sum = block_sum_256(acc, wave_sums);
+  if (threadIdx.x == 0) *out = accumulate ? *out + sum : sum;
+}
+
+size_t grad_sqnorm_workspace_bytes() { return (size_t)SQNORM_MAX_BLOCKS * sizeof(double); }
+
+int launch_grad_sqnorm_ranges(const float* g, const long long* off, const long long* count, int n_ranges, double* sqnorm, int accumulate,
+                              double* ws, hipStream_t s) {
+  if (int e = check_ranges("grad_sqnorm_ranges", off, count, nullptr, n_ranges, false)) return e;
+  bool launched = false;
+  for (int i = 0; i < n_ranges;) {
+    RangeTable t;
+    int src[OPT_MAX_RANGES];
+    const int grid = fill_ranges(t, off, count, n_ranges, &i, src);
+    if (!grid) break;
+    hipLaunchKernelGGL(sqnorm_ranges_kernel, dim3(grid), dim3(256), 0, s, g, t, ws);
+    if (int e = check_launch("grad_sqnorm_ranges")) return e;
+    hipLaunchKernelGGL(sqnorm_finish_kernel, dim3(1), dim3(256), 0, s, ws, grid, sqnorm, (accumulate || launched) ? 1 : 0);
+    if (int e = check_launch("grad_sqnorm_finish")) return e;
+    launched = true;
+  }
+  if (!launched && !accumulate) {      // nothing to add up: the norm of no gradient is 0
+    hipLaunchKernelGGL(sqnorm_finish_kernel, dim3(1), dim3(256), 0, s, ws, 0, sqnorm, 0);
+    return check_launch("grad_sqnorm_finish");
+  }
+  return 0;
+}
+
+// torch.nn.utils.clip_grad_norm_(error_if_nonfinite=False): clip_coef = clamp(max_norm / (total_norm + 1e-6), max=1.0). In double, each
+// result rounded once to float; a non-finite norm takes the same course as in torch (inf -> 0, nan -> nan).
+__global__ void clip_coef_kernel(const double* __restrict__ sqnorm, double max_norm, float grad_scale, float* __restrict__ coef_norm) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const double norm = (double)grad_scale * sqrt(*sqnorm);
+  double c = max_norm / (norm + 1e-6);
+  if (c > 1.0) c = 1.0;
+  coef_norm[0] = (float)c;
+  coef_norm[1] = (float)norm;
+}
+
+int launch_clip_coef(const double* sqnorm, double max_norm, float grad_scale, float* coef_norm, hipStream_t s) {
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(64), 0, s, sqnorm, max_norm, grad_scale, coef_norm);
+  return check_launch("clip_coef");
 }
 
 }  // namespace r3m

@@ -742,4 +742,34 @@ int r3m_sgd_step_ranges(float* p, const float* g, float* momentum_buf, const lon
                            S(stream));
 }
 
+size_t r3m_grad_sqnorm_workspace_bytes(void) { return grad_sqnorm_workspace_bytes(); }
+
+int r3m_grad_sqnorm_ranges(const float* grads, const long long* off, const long long* count, int n_ranges, double* sqnorm, int accumulate,
+                           void* workspace, size_t workspace_bytes, r3m_stream_t stream) {
+  R3M_REQUIRE(sqnorm && workspace, "grad_sqnorm_ranges: null argument");
+  R3M_REQUIRE(n_ranges <= 0 || grads, "grad_sqnorm_ranges: null gradient buffer");
+  R3M_REQUIRE(workspace_bytes >= grad_sqnorm_workspace_bytes(), "grad_sqnorm_ranges: workspace too small");
+  return launch_grad_sqnorm_ranges(grads, off, count, n_ranges, sqnorm, accumulate, static_cast<double*>(workspace), S(stream));
+}
+
+int r3m_clip_coef(const double* sqnorm, double max_norm, float grad_scale, float* coef_norm, r3m_stream_t stream) {
+  R3M_REQUIRE(sqnorm && coef_norm, "clip_coef: null argument");
+  R3M_REQUIRE(max_norm >= 0.0, "clip_coef: max_norm=%g must be >= 0", max_norm);
+  return launch_clip_coef(sqnorm, max_norm, grad_scale, coef_norm, S(stream));
+}
+
+int r3m_adam_step_groups(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
+                         const double* lr, const double* weight_decay, int n_ranges, double b1, double b2, double eps, int decoupled,
+                         float grad_scale, const float* clip_coef, r3m_stream_t stream) {
+  return launch_adam_groups(p, g, m, v, off, count, step, lr, weight_decay, n_ranges, b1, b2, eps, decoupled, grad_scale, clip_coef,
+                            S(stream));
+}
+
+int r3m_sgd_step_groups(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
+                        const double* lr, const double* weight_decay, int n_ranges, double momentum, double dampening, int nesterov,
+                        float grad_scale, const float* clip_coef, r3m_stream_t stream) {
+  return launch_sgd_groups(p, g, momentum_buf, off, count, step, lr, weight_decay, n_ranges, momentum, dampening, nesterov, grad_scale,
+                           clip_coef, S(stream));
+}
+
 }  // extern "C"

@@ -295,6 +295,18 @@ int launch_adam_ranges(float* p, const float* g, float* m, float* v, const long 
 int launch_sgd_ranges(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
                       int n_ranges, double lr, double momentum, double dampening, double weight_decay, int nesterov, float grad_scale,
                       hipStream_t s);
+// the ranged steps with a learning rate and a weight decay per range (host arrays) and an optional device clip coefficient
+int launch_adam_groups(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
+                       const double* lr, const double* weight_decay, int n_ranges, double beta1, double beta2, double eps, int decoupled,
+                       float grad_scale, const float* clip_coef, hipStream_t s);
+int launch_sgd_groups(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
+                      const double* lr, const double* weight_decay, int n_ranges, double momentum, double dampening, int nesterov,
+                      float grad_scale, const float* clip_coef, hipStream_t s);
+// deterministic fp64 sum of squares of the gradients over ranges -> *sqnorm (device), and the clip coefficient from it
+size_t grad_sqnorm_workspace_bytes();
+int launch_grad_sqnorm_ranges(const float* g, const long long* off, const long long* count, int n_ranges, double* sqnorm, int accumulate,
+                              double* ws, hipStream_t s);
+int launch_clip_coef(const double* sqnorm, double max_norm, float grad_scale, float* coef_norm, hipStream_t s);
 
 // ---- augmentation (augment.hip) ----
 int launch_crop_resize(const void* in, int in_is_u8, const int* boxes, float* out, long long N, int C, int Hi, int Wi, int Ho,

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from .encoder import HipResNet
-from .optim import FusedAdam
+from .optim import FusedAdam, no_decay_groups
 
 epsilon = 1e-8
 
@@ -34,7 +34,7 @@ class _NormalizeSpec(nn.Module):
 
 class R3M(nn.Module):
     def __init__(self, device, lr, hidden_dim, size=34, l2weight=1.0, l1weight=1.0, langweight=1.0, tcnweight=0.0,
-                 l2dist=True, bs=16, precision="fp32", max_live_forwards=1):
+                 l2dist=True, bs=16, precision="fp32", max_live_forwards=1, weight_decay=0.0, grad_clip=0.0):
         super().__init__()
         self.device = device
         self.use_tb = False
@@ -66,7 +66,16 @@ class R3M(nn.Module):
             self.lang_rew = LanguageReward(None, self.outdim, hidden_dim, self.lang_enc.lang_size, simfunc=self.sim, precision=precision)
             owners.append(self.lang_rew)
 
-        self.encoder_opt = FusedAdam(owners, lr=lr)
+        # weight_decay / grad_clip (both 0: the reference's plain Adam): decoupled (AdamW) decay on the encoder's dim() >= 2 tensors only
+        # -- not on BatchNorm, nor on the language head, which steps as one group -- and one global gradient-norm clip over all owners
+        if weight_decay < 0 or grad_clip < 0:
+            raise ValueError(f"R3M: weight_decay={weight_decay!r} and grad_clip={grad_clip!r} must be >= 0")
+        if weight_decay > 0 or grad_clip > 0:
+            groups = no_decay_groups(self.convnet, weight_decay) if weight_decay > 0 else None
+            self.encoder_opt = FusedAdam(owners, lr=lr, decoupled_weight_decay=weight_decay > 0, param_groups=groups,
+                                         max_grad_norm=float(grad_clip) if grad_clip > 0 else None)
+        else:
+            self.encoder_opt = FusedAdam(owners, lr=lr)
 
     def get_reward(self, e0, es, sentences):
         le = self.lang_enc(sentences)
