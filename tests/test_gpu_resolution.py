@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as Fn
 
+from util import stem_inputs
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 MEAN = torch.tensor([0.485, 0.456, 0.406], dtype=torch.float64).view(1, 3, 1, 1)
@@ -42,13 +44,7 @@ def _bf(t):
 
 
 # ---- 1. the general stem kernels -------------------------------------------------------------------------------------------------
-def _stem_inputs(F, H, W, seed):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.floor(torch.rand(F, 3, H, W, generator=g) * 256).clamp(0, 255)
-    w = torch.randn(64, 7, 7, 3, generator=g) * 0.1                     # OHWI
-    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    dy = torch.randn(F, Ho, Wo, 64, generator=g)
-    return x, w, dy, Ho, Wo
+_stem_inputs = stem_inputs          # shared with tests/test_gpu_stem_edges.py, which checks these kernels element by element
 
 
 def _run_stem_gen(hip, x, w, dy, dtype):
@@ -100,7 +96,8 @@ def test_generic_stem_kernels_against_float64(hip, F, H, W, dtype):
     ey, ew, ex = l2rel(y, y_ref), l2rel(dw, dw_ref), l2rel(dx, dx_ref)
     report(f"generic stem {dtype} F={F} {H}x{W}: l2-rel fwd {ey:.2e} wgrad {ew:.2e} input grad {ex:.2e}")
     assert ey <= tol and ew <= (1e-5 if dtype == "fp32" else 1e-4) and ex <= (1e-5 if dtype == "fp32" else 1e-4), (ey, ew, ex)
-    # BatchNorm partials: per-channel sum and sum of squares of the stored-precision outputs, rows past M contribute nothing
+    # BatchNorm partials: per-channel sum and sum of squares of the fp32 accumulators, before the store rounds them (gg_stats,
+    # csrc/conv_dev.h; y_ref is the unrounded float64 result for bf16 too), rows past M contribute nothing
     s1 = stats[:, 0].double().sum(0)
     s2 = stats[:, 1].double().sum(0)
     yy = y_ref.reshape(-1, 64)

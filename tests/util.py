@@ -808,3 +808,264 @@ def assert_edge_figures(what, got, wit, ceil, witnessed=()):
             fails.append(f"{k}: {e:.3e} against the ceiling {c:.0e} (float32 oracle on the CPU: {w:.3e})")
     if fails:
         pytest.fail(f"{what}: " + "; ".join(fails))
+
+
+# ---- the general stem kernels at their launch edges (tests/test_gpu_stem_edges.py on the GPU, tests/test_stem_cases.py for the case
+# list on the CPU; section 1 of tests/test_gpu_resolution.py draws its inputs from stem_inputs) --------------------------------------------
+# r3m_stem_gen_prep / _fwd / _wgrad / _input_grad (csrc/stem_gen.hip) element by element against float64 F.conv2d on the operands the
+# kernel multiplies. Ceilings: the ones check_conv_fp32 / check_conv_bf16 / assert_close_store use for the same stores.
+STEM_TILE = 256              # output pixels of one forward tile: csrc/stem_gen.hip stem_fwd_gen_kernel `m0 = blk * 256`
+STEM_FWD_BLOCKS = 512        # most forward blocks: csrc/stem_gen.hip launch_stem_fwd_gen `grid = ntiles < 512 ? ntiles : 512`
+STEM_WG_BLOCKS = 512         # most weight-gradient blocks: csrc/stem_dev.h `#define R3M_STEM_WG_BLOCKS 512` (launch_stem_wgrad_gen `nb`)
+STEM_MEAN = torch.tensor([0.485, 0.456, 0.406], dtype=torch.float64).view(1, 3, 1, 1)
+STEM_STD = torch.tensor([0.229, 0.224, 0.225], dtype=torch.float64).view(1, 3, 1, 1)
+
+# (F, H, W): the smallest shapes at which each condition of STEM_CONDITIONS occurs (tests/test_stem_cases.py recomputes them)
+STEM_EDGE_CASES = [
+    (1, 32, 32), (2, 32, 32),                    # the minimum size: Ho Wo = 256, a tile is a frame, nothing straddles
+    (17, 32, 34),                                # Ho Wo = 272: the frame boundaries fall at every multiple of 16 of a tile
+    (2, 34, 32),                                 # a last tile of 32 live pixels behind a straddling tile
+    (3, 33, 35),                                 # odd H and W, Wo = 18, 2 of 4 tiles straddle, the last tile holds 150 pixels
+    (3, 65, 63), (2, 63, 129), (2, 64, 66),      # Wo = 32, 65, 33: 1, 3, 2 input-gradient M tiles; W: 1, 3, 2 trips of the col2im lane loop
+    (1, 32, 64),                                 # W = 64: exactly one full trip of the lane loop
+    (27, 37, 32),                                # F Ho = 513 weight-gradient rows: one block takes a second row
+    (33, 32, 32),                                # 528 weight-gradient rows, no forward straddle
+    (33, 128, 128),                              # 528 forward tiles, no straddle: the forward's second trip
+    (35, 126, 125),                              # 543 tiles, 34 straddle, last tile 163 pixels, 2205 weight-gradient rows
+    (2, 32, 503),                                # the forward's largest LDS footprint (136 KiB), with a straddling tile
+    (2, 37, 512), (2, 512, 37),                  # the widest staged row (Wo = 256: a tile is one row) and its transpose (F Ho = 512)
+    (1, 511, 509),                               # Wo = 255: tiles drift a pixel per row; odd H: invalid waves in the last parity group
+]
+
+
+def stem_case_id(c):
+    return "F{}_{}x{}".format(*c)
+
+
+def stem_case_props(F_, H, W):
+    """what the launchers and kernels of csrc/stem_gen.hip can tell apart about F frames of H x W, from (F, H, W) alone"""
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    HWo = Ho * Wo
+    M = F_ * HWo
+    ntiles = (M + STEM_TILE - 1) // STEM_TILE
+    first = [t * STEM_TILE // HWo for t in range(ntiles)]
+    last = [min(t * STEM_TILE + STEM_TILE - 1, M - 1) // HWo for t in range(ntiles)]
+    straddling = [t for t in range(ntiles) if first[t] != last[t]]
+    assert all(last[t] - first[t] <= 1 for t in range(ntiles))            # Ho Wo >= 256: at most two frames per tile
+    rows_p = ((H + 1) // 2, H // 2)                                        # input rows of parity 0 / 1
+    groups = (rows_p[0] + 3) // 4                                          # launch_stem_input_grad_gen: blocks per (frame, parity)
+    return dict(
+        Ho=Ho, Wo=Wo, M=M, ntiles=ntiles, straddling=len(straddling), last_fill=M - (ntiles - 1) * STEM_TILE,
+        straddle_phases=sorted({(f * HWo) % STEM_TILE for f in range(1, F_)}),          # where in its tile a frame starts
+        second_trip_straddles=any(t >= STEM_FWD_BLOCKS for t in straddling),
+        rows_per_tile_max=(Wo + STEM_TILE - 2) // Wo + 1,
+        wg_rows=F_ * Ho, wo_odd=Wo % 2 == 1,
+        m_tiles=(Wo + 31) // 32, m_tail=Wo % 32, lane_trips=(W + 63) // 64, lane_tail=W % 64,
+        dgrad_groups=groups, invalid_waves=tuple(4 * groups - r for r in rows_p))
+
+
+# condition -> predicate over (F, H, W, stem_case_props): the edges the case list is there for; every one must hold for some case
+STEM_CONDITIONS = {
+    "one frame, a tile is the frame": lambda F_, H, W, p: F_ == 1 and p["M"] == STEM_TILE,
+    "frames of exactly one tile: no straddle": lambda F_, H, W, p: F_ > 1 and p["Ho"] * p["Wo"] == STEM_TILE and p["straddling"] == 0,
+    "frame starts at every multiple of 16 of a tile": lambda F_, H, W, p: p["straddle_phases"] == list(range(0, 256, 16)),
+    "last tile of 32 live pixels with a straddling tile": lambda F_, H, W, p: p["last_fill"] == 32 and p["straddling"] >= 1,
+    "odd H and odd W with straddling tiles": lambda F_, H, W, p: H % 2 == 1 and W % 2 == 1 and p["straddling"] >= 2,
+    "partial last tile that is no multiple of a wave": lambda F_, H, W, p: p["last_fill"] % 64 != 0 and p["last_fill"] % 32 != 0,
+    "one full input-gradient M tile": lambda F_, H, W, p: p["m_tiles"] == 1 and p["m_tail"] == 0,
+    "two M tiles, a tail of one": lambda F_, H, W, p: p["m_tiles"] == 2 and p["m_tail"] == 1,
+    "three M tiles, a tail of one": lambda F_, H, W, p: p["m_tiles"] == 3 and p["m_tail"] == 1,
+    "lane loop: one trip with idle lanes": lambda F_, H, W, p: p["lane_trips"] == 1 and p["lane_tail"] != 0,
+    "lane loop: exactly one full trip": lambda F_, H, W, p: W == 64,
+    "lane loop: two trips": lambda F_, H, W, p: p["lane_trips"] == 2 and p["lane_tail"] != 0,
+    "lane loop: three trips": lambda F_, H, W, p: p["lane_trips"] == 3 and p["lane_tail"] != 0,
+    "odd Wo: the weight gradient pads to Wo2": lambda F_, H, W, p: p["wo_odd"] and p["Wo"] > 1,
+    "even Wo": lambda F_, H, W, p: not p["wo_odd"],
+    "weight gradient: exactly one block takes a second row": lambda F_, H, W, p: p["wg_rows"] == STEM_WG_BLOCKS + 1,
+    "weight gradient: exactly as many rows as blocks": lambda F_, H, W, p: p["wg_rows"] == STEM_WG_BLOCKS,
+    "weight gradient second trip, forward without straddle or second trip":
+        lambda F_, H, W, p: p["wg_rows"] > STEM_WG_BLOCKS and p["straddling"] == 0 and p["ntiles"] <= STEM_FWD_BLOCKS,
+    "weight gradient second trip with straddling frames": lambda F_, H, W, p: p["wg_rows"] > STEM_WG_BLOCKS and p["straddling"] > 0,
+    "forward second trip without straddle": lambda F_, H, W, p: p["ntiles"] > STEM_FWD_BLOCKS and p["straddling"] == 0,
+    "forward second trip with a straddling tile in it": lambda F_, H, W, p: p["ntiles"] > STEM_FWD_BLOCKS and p["second_trip_straddles"],
+    "a tile is exactly one output row (W = 512)": lambda F_, H, W, p: p["Wo"] == STEM_TILE and W == 512,
+    "64 input-gradient groups per parity, H even": lambda F_, H, W, p: p["dgrad_groups"] == 64 and H % 2 == 0,
+    "tiles drift one pixel per row": lambda F_, H, W, p: p["Wo"] == STEM_TILE - 1,
+    "odd H: an invalid wave in the last group of one parity only": lambda F_, H, W, p: H % 2 == 1 and p["invalid_waves"] == (0, 1),
+    "sixteen output rows per tile": lambda F_, H, W, p: p["Wo"] == 16,
+    "H != W both ways": lambda F_, H, W, p: H != W,
+}
+
+
+def stem_inputs(F_, H, W, seed):
+    """integer frames 0..255 [F,3,H,W], conv1 weights OHWI randn * 0.1, dY randn [F,Ho,Wo,64]"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.floor(torch.rand(F_, 3, H, W, generator=g) * 256).clamp(0, 255)
+    w = torch.randn(64, 7, 7, 3, generator=g) * 0.1                     # OHWI
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    dy = torch.randn(F_, Ho, Wo, 64, generator=g)
+    return x, w, dy, Ho, Wo
+
+
+def stem_edge_setup(case, dtype):
+    """the inputs of a case and the float64 operands the kernels multiply: the normalised image (bf16: rounded once), the weights OIHW
+    (bf16: rounded; `w_master`: the fp32 master the input gradient multiplies), dY NCHW (bf16: rounded)"""
+    F_, H, W = case
+    x, w, dy, Ho, Wo = stem_inputs(F_, H, W, 1000 * H + W + F_)
+    xn32 = (x / 255.0 - STEM_MEAN.float()) / STEM_STD.float()          # fp32, the arithmetic of stem_normalize
+    q = (lambda t: t.to(torch.bfloat16)) if dtype == "bf16" else (lambda t: t)
+    return dict(F=F_, H=H, W=W, Ho=Ho, Wo=Wo, dt=1 if dtype == "bf16" else 0, tdt=torch.bfloat16 if dtype == "bf16" else torch.float32,
+                x=x, w=w, dy=dy, xn32=xn32, xn=q(xn32).double(), w_op=q(w).double().permute(0, 3, 1, 2).contiguous(),
+                w_master=w.double().permute(0, 3, 1, 2).contiguous(), dy_op=q(dy).double().permute(0, 3, 1, 2).contiguous())
+
+
+def _scalar(v):
+    return torch.as_tensor(float(v), dtype=torch.float64)
+
+
+def stem_gen_prep_dev(hip, s):
+    """r3m_stem_gen_prep into a NaN-filled (all-ones bytes) image; returns the device byte buffer"""
+    nbytes = hip.r3m_stem_gen_image_bytes(s["F"], s["H"], s["W"], s["dt"])
+    assert nbytes == s["F"] * s["H"] * s["W"] * 3 * (2 if s["dt"] else 4)
+    xn = torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=DEV)     # 0xFFFF / 0xFFFFFFFF: a NaN in either type
+    xd = s["x"].to(DEV).contiguous()
+    assert hip.r3m_stem_gen_prep(xd.data_ptr(), xn.data_ptr(), s["F"], s["H"], s["W"], s["dt"], _st()) == 0, hip.r3m_last_error()
+    return xn
+
+
+def _stem_frames(F_):
+    return sorted({0, F_ // 2, F_ - 1})
+
+
+def check_stem_gen_prep(hip, case, dtype):
+    """the pre-pass: xn[f][iy][ix * 3 + c] (the layout csrc/stem_gen.hip stem_prep_gen_kernel writes, r3m_stem_gen_image_bytes long) is
+    bit for bit torch CPU fp32 (x / 255 - mean) / std, for bf16 that value rounded once"""
+    s = stem_edge_setup(case, dtype)
+    xn = stem_gen_prep_dev(hip, s)
+    got = xn.view(s["tdt"]).view(s["F"], s["H"], s["W"], 3).cpu()
+    want = nhwc(s["xn32"]).to(s["tdt"])
+    assert bool(torch.isfinite(got.float()).all()), f"stem prep {dtype} {case}: an element was not written"
+    diff = int((got.view(torch.int16 if s["dt"] else torch.int32) != want.view(torch.int16 if s["dt"] else torch.int32)).sum())
+    print(f"stem prep {dtype} {case}: {diff} of {want.numel()} elements differ in their bits")
+    assert diff == 0
+
+
+def check_stem_gen_forward(hip, case, dtype):
+    """r3m_stem_gen_fwd with and without statistics under assert_close_store's ceilings, the BatchNorm partials per 256-pixel tile, and
+    frames 0 / middle / last bit-identical to 1-frame calls (a pixel's MFMA sums do not depend on where its tile starts)."""
+    import pytest
+    s = stem_edge_setup(case, dtype)
+    F_, H, W, Ho, Wo, dt, tdt = (s[k] for k in ("F", "H", "W", "Ho", "Wo", "dt", "tdt"))
+    y_ref = F.conv2d(s["xn"], s["w_op"], stride=2, padding=3)
+    what = f"stem forward {dtype} {case}"
+    assert_range(y_ref, [_scalar(s["xn"].abs().max() * s["w_op"].abs().max())], what)
+    xn = stem_gen_prep_dev(hip, s)
+    wd = s["w"].to(DEV).contiguous()
+    M = F_ * Ho * Wo
+    nt = (M + STEM_TILE - 1) // STEM_TILE
+
+    def launch(xn_, frames, with_stats):
+        y = torch.full((frames, Ho, Wo, 64), float("nan"), dtype=tdt, device=DEV)
+        st_ = torch.full(((frames * Ho * Wo + STEM_TILE - 1) // STEM_TILE, 2, 64), float("nan"), device=DEV) if with_stats else None
+        rc = hip.r3m_stem_gen_fwd(xn_.data_ptr(), wd.data_ptr(), y.data_ptr(), None if st_ is None else st_.data_ptr(), frames, H, W, dt, _st())
+        assert rc == 0, hip.r3m_last_error()
+        return y, st_
+
+    y, stats = launch(xn, F_, True)
+    y0, _ = launch(xn, F_, False)
+    assert_close_store(what + " (statistics)", nchw(y.float().cpu()), y_ref, dtype)
+    assert_close_store(what + " (stats = NULL)", nchw(y0.float().cpu()), y_ref, dtype)
+    # BatchNorm partials, tile by tile. gg_stats (csrc/conv_dev.h) sums the fp32 ACCUMULATORS, before the store rounds them: for bf16 too
+    # the reference is the unrounded float64 result. Pixels past M were cleared after the K loop and add nothing.
+    yy = torch.zeros(nt * STEM_TILE, 64, dtype=torch.float64)
+    yy[:M] = nhwc(y_ref).reshape(M, 64)
+    yy = yy.view(nt, STEM_TILE, 64)
+    r1, a1, r2 = yy.sum(1), yy.abs().sum(1), (yy * yy).sum(1)
+    got = stats.double().cpu()
+    assert tuple(got.shape) == (nt, 2, 64)
+    e1, e2 = (got[:, 0] - r1).abs() / a1, (got[:, 1] - r2).abs() / r2
+    e1[~torch.isfinite(e1)] = float("inf")
+    e2[~torch.isfinite(e2)] = float("inf")
+    print(f"{what}: statistics per tile, worst |s1 - sum y| / sum|y| {float(e1.max()):.3e}, |s2 - sum y^2| / sum y^2 {float(e2.max()):.3e} "
+          f"({nt} tiles, last holds {M - (nt - 1) * STEM_TILE} pixels)")
+    bad = torch.nonzero(((e1 > 1e-4) | (e2 > 1e-4)).any(1)).flatten()
+    if bad.numel():
+        pytest.fail(f"{what}: the statistics of {bad.numel()} of {nt} tiles are off (first {bad[:8].tolist()}, last {bad[-3:].tolist()}): worst "
+                    f"s1 {float(e1.max()):.3e} s2 {float(e2.max()):.3e} against 1e-4")
+    # frame independence, exact
+    if F_ > 1:
+        fb = H * W * 3 * (2 if dt else 4)
+        for f in _stem_frames(F_):
+            y1, _ = launch(xn[f * fb:(f + 1) * fb].clone(), 1, True)
+            if not torch.equal(y1[0], y[f]):
+                pytest.fail(f"{what}: frame {f} of the {F_}-frame call differs from a 1-frame call on its data: "
+                            + describe_bad(y[f].float().cpu(), y1[0].float().cpu(), 0.0))
+        print(f"{what}: frames {_stem_frames(F_)} bit-identical to 1-frame calls")
+
+
+def check_stem_gen_wgrad(hip, case, dtype):
+    """r3m_stem_gen_wgrad with accumulate 0 into NaN, then accumulate 1 on top: max-rel < 5e-5 of the range against 1 x and 2 x float64"""
+    s = stem_edge_setup(case, dtype)
+    F_, H, W, dt, tdt = (s[k] for k in ("F", "H", "W", "dt", "tdt"))
+    wr = s["w_op"].clone().requires_grad_(True)
+    F.conv2d(s["xn"], wr, stride=2, padding=3).backward(s["dy_op"])
+    dw_ref = wr.grad                                                    # OIHW
+    what = f"stem weight gradient {dtype} {case}"
+    assert_range(dw_ref, [_scalar(s["xn"].abs().max() * s["dy_op"].abs().max())], what)
+    xn = stem_gen_prep_dev(hip, s)
+    dyd = s["dy"].to(tdt).to(DEV).contiguous()
+    dw = torch.full((64, 7, 7, 3), float("nan"), device=DEV)
+    wsb = hip.r3m_stem_gen_wgrad_ws_bytes()
+    ws = guarded_bytes(wsb)
+    for acc in (0, 1):
+        rc = hip.r3m_stem_gen_wgrad(xn.data_ptr(), dyd.data_ptr(), dw.data_ptr(), ws.data_ptr(), F_, H, W, acc, dt, _st())
+        assert rc == 0, hip.r3m_last_error()
+        e_max, e_l2 = rel_err(dw.cpu().permute(0, 3, 1, 2).numpy(), (acc + 1) * dw_ref.numpy())
+        print(f"{what} accumulate {acc}: max-rel {e_max:.3e} l2-rel {e_l2:.3e}")
+        assert e_max < 5e-5, f"{what} accumulate {acc}: max-rel {e_max}"
+    assert_guard_intact(ws, wsb, what)
+
+
+def check_stem_gen_input_grad(hip, case, dtype):
+    """r3m_stem_gen_input_grad (fp32 NCHW output for both dtypes): accumulate 0 into NaN and accumulate 1 onto a base that is non-zero
+    everywhere, max-rel < 2e-5 of the range, every element finite, frames 0 / middle / last bit-identical to 1-frame calls"""
+    import pytest
+    s = stem_edge_setup(case, dtype)
+    F_, H, W, Ho, Wo, dt, tdt = (s[k] for k in ("F", "H", "W", "Ho", "Wo", "dt", "tdt"))
+    # (bf16) dZ against the fp32 master weights, then d(normalised) / d(frame value) = 1 / (255 std)
+    dx_ref = torch.nn.grad.conv2d_input((F_, 3, H, W), s["w_master"], s["dy_op"], stride=2, padding=3) / (255.0 * STEM_STD)
+    what = f"stem input gradient {dtype} {case}"
+    top = _scalar(s["dy_op"].abs().max() * s["w_master"].abs().max() / (255.0 * float(STEM_STD.min())))
+    assert_range(dx_ref, [top], what)
+    sd = float(dx_ref.pow(2).mean().sqrt())
+    base = rnd((F_, 3, H, W), 31, 0.25, 1.0) * torch.where(rnd((F_, 3, H, W), 32) > 0, 1.0, -1.0) * sd
+    assert bool((base != 0).all()), f"{what}: the base must be non-zero everywhere"
+    ref_acc = dx_ref + base.double()
+    assert_range(ref_acc, [dx_ref, base], what + " accumulate")
+    dyd = s["dy"].to(tdt).to(DEV).contiguous()
+    wd = s["w"].to(DEV).contiguous()
+
+    def launch(dz, frames, old):
+        dx = torch.full((frames, 3, H, W), float("nan"), device=DEV) if old is None else old.to(DEV).contiguous()
+        rc = hip.r3m_stem_gen_input_grad(dz.data_ptr(), wd.data_ptr(), dx.data_ptr(), frames, H, W, 0 if old is None else 1, dt, _st())
+        assert rc == 0, hip.r3m_last_error()
+        return dx
+
+    dx = launch(dyd, F_, None)
+    dxa = launch(dyd, F_, base)
+    for name, got, ref in (("accumulate 0", dx, dx_ref), ("accumulate 1", dxa, ref_acc)):
+        g = got.cpu()
+        assert bool(torch.isfinite(g).all()), f"{what} {name}: {int((~torch.isfinite(g)).sum())} elements of [F,3,H,W] are not finite"
+        e_max, e_l2 = rel_err(g.numpy(), ref.numpy())
+        print(f"{what} {name}: max-rel {e_max:.3e} l2-rel {e_l2:.3e}")
+        if not e_max < 2e-5:
+            d = (g.double() - ref).abs() > 2e-5 * float(ref.abs().max())
+            rows = torch.nonzero(d.any(3).any(1).any(0)).flatten()
+            cols = torch.nonzero(d.any(2).any(1).any(0)).flatten()
+            pytest.fail(f"{what} {name}: max-rel {e_max}; {int(d.sum())} elements off in {len(rows)} rows (first {rows[:6].tolist()}, last "
+                        f"{rows[-3:].tolist()}) and {len(cols)} columns (first {cols[:6].tolist()}, last {cols[-3:].tolist()})")
+    if F_ > 1:
+        for f in _stem_frames(F_):
+            one = launch(dyd[f:f + 1].contiguous(), 1, None)
+            assert torch.equal(one[0], dx[f]), f"{what}: frame {f} of the {F_}-frame call differs from a 1-frame call on its data"
+        print(f"{what}: frames {_stem_frames(F_)} bit-identical to 1-frame calls")
