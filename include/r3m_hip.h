@@ -402,7 +402,8 @@ int r3m_linear_fwd(const float* x, const float* w, const float* bias, float* y, 
 /* RandomResizedCrop resample of the rc / rctraj augmentations (r3m/utils/data_loaders.py:47-50,81-102): crop box
  * boxes[n / frames_per_box] = {top, left, height, width} (host-drawn), bilinear resize to Ho x Wo (align_corners=False),
  * on x/255, result * 255. frames: [N,C,Hi,Wi] uint8 or float in 0..255; out: [N,C,Ho,Wo] float. frames_per_box = 5 for
- * rctraj (one box per clip), 1 for rc. */
+ * rctraj (one box per clip), 1 for rc. Every box must lie inside its frame (not checked). This call and r3m_resize_crop refuse
+ * Hi, Wi, C < 1 and N, Ho, Wo < 0 before any launch; N, Ho or Wo of 0 is an empty call. */
 int r3m_crop_resize(const void* frames, int frames_are_u8, const int* boxes, float* out, long long N, int C, int Hi, int Wi,
                     int Ho, int Wo, int frames_per_box, r3m_stream_t stream);
 /* R3M.forward's branch for inputs that are not 224 x 224 (r3m/models/models_r3m.py:85-90: transforms.Resize(256) +

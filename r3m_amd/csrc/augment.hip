@@ -47,6 +47,9 @@ static int launch_resample(const void* in, int in_is_u8, const int* boxes, float
 int launch_crop_resize(const void* in, int in_is_u8, const int* boxes, float* out, long long N, int C, int Hi, int Wi, int Ho,
                        int Wo, int frames_per_box, hipStream_t s) {
   R3M_REQUIRE(frames_per_box >= 1, "crop_resize: frames_per_box=%d", frames_per_box);
+  // (two negative extents would make a positive element count, and a launch)
+  R3M_REQUIRE(Hi >= 1 && Wi >= 1 && N >= 0 && C >= 1, "crop_resize: frames %lldx%dx%dx%d", N, C, Hi, Wi);
+  R3M_REQUIRE(Ho >= 0 && Wo >= 0, "crop_resize: output %dx%d", Ho, Wo);
   return launch_resample(in, in_is_u8, boxes, out, N, C, Hi, Wi, Ho, Wo, frames_per_box, 0, 0, Ho, Wo, s);
 }
 
@@ -56,6 +59,8 @@ int launch_resize_crop(const void* in, int in_is_u8, float* out, long long N, in
                        int top, int left, int Ho, int Wo, hipStream_t s) {
   R3M_REQUIRE(full_Ho >= 1 && full_Wo >= 1 && top >= 0 && left >= 0 && top + Ho <= full_Ho && left + Wo <= full_Wo,
               "resize_crop: window %dx%d at (%d,%d) outside the %dx%d resized frame", Ho, Wo, top, left, full_Ho, full_Wo);
+  R3M_REQUIRE(Hi >= 1 && Wi >= 1 && N >= 0 && C >= 1, "resize_crop: frames %lldx%dx%dx%d", N, C, Hi, Wi);
+  R3M_REQUIRE(Ho >= 0 && Wo >= 0, "resize_crop: window %dx%d", Ho, Wo);
   return launch_resample(in, in_is_u8, nullptr, out, N, C, Hi, Wi, Ho, Wo, 1, top, left, full_Ho, full_Wo, s);
 }
 

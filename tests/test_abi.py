@@ -85,6 +85,30 @@ def test_bf16_plan_is_smaller_and_same_parameters():
         L.r3m_resnet_destroy(h16)
 
 
+def test_forward_resample_launchers_refuse_negative_extents():
+    """r3m_crop_resize and r3m_resize_crop refuse what r3m_resize_crop_backward refuses (csrc/augment.hip): Hi, Wi, C >= 1, N >= 0,
+    Ho, Wo >= 0. Two negative extents make a positive element count, so without the checks a launch followed. A refusal returns
+    before any HIP call: the pointers are dummies and no GPU is needed."""
+    import ctypes
+    from r3m_amd import _lib
+    L = _lib.lib()
+    buf = (ctypes.c_int * 16)()
+    p = ctypes.addressof(buf)
+    ok = dict(N=2, C=3, Hi=8, Wi=9, Ho=4, Wo=5)
+    bad = [dict(Ho=-4), dict(Wo=-5), dict(Ho=-4, Wo=-5), dict(N=-2), dict(N=-2, C=-3), dict(C=0), dict(C=-3, Ho=-4), dict(Hi=0),
+           dict(Hi=-8, Wi=-9), dict(Wi=0), dict(Wi=-9, N=-2)]
+    for change in bad:
+        a = dict(ok, **change)
+        rc = L.r3m_crop_resize(p, 1, p, p, a["N"], a["C"], a["Hi"], a["Wi"], a["Ho"], a["Wo"], 1, None)
+        assert rc != 0 and b"crop_resize" in L.r3m_last_error(), change
+        # the whole 16 x 16 resized frame holds any window of these sizes at (0, 0)
+        rc = L.r3m_resize_crop(p, 1, p, a["N"], a["C"], a["Hi"], a["Wi"], 16, 16, 0, 0, a["Ho"], a["Wo"], None)
+        assert rc != 0 and b"resize_crop" in L.r3m_last_error(), change
+    # an empty batch and an empty window are not errors: nothing is launched
+    assert L.r3m_crop_resize(p, 1, p, p, 0, 3, 8, 9, 4, 5, 1, None) == 0
+    assert L.r3m_resize_crop(p, 1, p, 2, 3, 8, 9, 16, 16, 0, 0, 0, 5, None) == 0
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from r3m_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
