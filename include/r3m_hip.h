@@ -358,6 +358,8 @@ int r3m_stem_conv_fwd_bf16(const void* xn16, const float* w_ohwi, void* y, float
 size_t r3m_stem_conv_wgrad_bf16_workspace_bytes(void);
 int r3m_stem_conv_wgrad_bf16(const void* xn16, const void* dy, float* dw_ohwi, void* workspace, size_t workspace_bytes, int frames,
                              int accumulate, r3m_stream_t stream);
+/* The BatchNorm entry points check their arguments, carve the workspace and run the host sequences of csrc/bn.hip / bn_pool.hip
+ * (bn_train_coeffs, bn_bwd, bn_bwd_pair, bn_bwd_pool), which are the launch sequences of the engine's training step. */
 int r3m_bn_act_fwd_dt(const void* y, const float* coef, const void* r, const void* y2, const float* coef2, void* z,
                       long long rows, int C, int relu, unsigned* maskbits, int dtype, r3m_stream_t stream);
 int r3m_bn_bwd_dt(const void* dz, const void* zmask, const unsigned* zbits, const void* y, const float* coef, float* dgamma,

@@ -62,7 +62,7 @@ size_t bn_acc_bytes(int C) {
 
 // acc must hold 131072 * 2 doubles (64 slices x 2 x 2048 channels, or more slices of fewer channels); the slice count is a pure function of the partial-row count (reduce_slices), so
 // the finalize launchers below take the same `stat_rows` and recompute it.
-int launch_bn_stats_reduce(const float* partials, int rows, int C, double* acc, hipStream_t s) {
+static int launch_bn_stats_reduce(const float* partials, int rows, int C, double* acc, hipStream_t s) {
   const int S = reduce_slices(rows, C);
   hipLaunchKernelGGL(bn_stats_reduce_kernel, dim3(ceil_div(C, 64), S), dim3(256), 0, s, partials, rows, C, acc);
   return check_launch("bn_stats_reduce");
@@ -125,14 +125,20 @@ __global__ __launch_bounds__(64 * SG) void bn_finalize_kernel(const double* __re
 }
 
 // `stat_rows` = number of partial rows that were reduced (fixes the slice count), `count` = elements per channel.
-int launch_bn_finalize_rows(const double* acc, int stat_rows, long long count, const float* gamma, const float* beta,
-                            float* running_mean, float* running_var, float momentum, float eps, float* mean,
-                            float* invstd, float* scale, float* shift, int C, hipStream_t s) {
+static int launch_bn_finalize_rows(const double* acc, int stat_rows, long long count, const float* gamma, const float* beta,
+                                   float* running_mean, float* running_var, float momentum, float eps, const BnCoefOut& o, int C,
+                                   hipStream_t s) {
   const double inv_count = 1.0 / (double)count;
   const double unbias = count > 1 ? (double)count / (double)(count - 1) : 1.0;
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(ceil_div(C, 64)), dim3(64 * SG), 0, s, acc, reduce_slices(stat_rows, C), inv_count,
-                     unbias, gamma, beta, running_mean, running_var, momentum, eps, mean, invstd, scale, shift, C);
+                     unbias, gamma, beta, running_mean, running_var, momentum, eps, o.mean, o.invstd, o.scale, o.shift, C);
   return check_launch("bn_finalize");
+}
+
+int bn_train_coeffs(const float* stats, int stats_rows, long long count, const float* gamma, const float* beta, float* running_mean,
+                    float* running_var, float momentum, float eps, const BnCoefOut& o, int C, double* acc, hipStream_t s) {
+  TRY(launch_bn_stats_reduce(stats, stats_rows, C, acc, s));
+  return launch_bn_finalize_rows(acc, stats_rows, count, gamma, beta, running_mean, running_var, momentum, eps, o, C, s);
 }
 
 __global__ __launch_bounds__(256) void bn_eval_coeffs_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -149,10 +155,10 @@ __global__ __launch_bounds__(256) void bn_eval_coeffs_kernel(const float* __rest
   shift_o[c] = fmaf(-rm[c], sc, beta[c]);
 }
 
-int launch_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
-                          float eps, float* mean, float* invstd, float* scale, float* shift, int C, hipStream_t s) {
+int launch_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                          const BnCoefOut& o, int C, hipStream_t s) {
   hipLaunchKernelGGL(bn_eval_coeffs_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, s, gamma, beta, running_mean,
-                     running_var, eps, mean, invstd, scale, shift, C);
+                     running_var, eps, o.mean, o.invstd, o.scale, o.shift, C);
   return check_launch("bn_eval_coeffs");
 }
 
@@ -250,16 +256,17 @@ static inline int col_blocks(int C, int vec, int cpb) { return ceil_div(C / vec,
     else { set_last_error(NAME ": unknown dtype %d", (int)(dt)); return 1; }              \
   } while (0)
 
-int launch_bn_act_fwd(const void* Y, const float* scale, const float* shift, const void* R, const float* scale2,
-                      const float* shift2, void* Z, long long rows, int C, int relu, unsigned* maskbits, int dt, hipStream_t s) {
+int launch_bn_act_fwd(const void* Y, const BnCoef& K, const void* R, const BnCoef* K2, void* Z, long long rows, int C, int relu,
+                      unsigned* maskbits, int dt, hipStream_t s) {
   R3M_REQUIRE(is_pow2(C) && C >= 4, "bn_act_fwd: C=%d must be a power of two >= 4", C);
   R3M_REQUIRE(!maskbits || (rows * C / 4) % 8 == 0, "bn_act_fwd: bit mask needs rows*C to be a multiple of 32");
   const int vec = bn_vec(dt, C), span = fwd_span(vec, C);
   const long long n = bn_items(rows, C, vec);
   BN_DISPATCH(dt, vec, "bn_act_fwd", {
-    const auto kernel = (R && scale2) ? bn_act_fwd_kernel<2, T, V4> : R ? bn_act_fwd_kernel<1, T, V4> : bn_act_fwd_kernel<0, T, V4>;
-    hipLaunchKernelGGL(kernel, dim3(span_grid(n, span)), dim3(256), 0, s, static_cast<const T*>(Y), scale, shift,
-                       static_cast<const T*>(R), scale2, shift2, static_cast<T*>(Z), n, C / vec - 1, relu, maskbits, span);
+    const auto kernel = (R && K2) ? bn_act_fwd_kernel<2, T, V4> : R ? bn_act_fwd_kernel<1, T, V4> : bn_act_fwd_kernel<0, T, V4>;
+    hipLaunchKernelGGL(kernel, dim3(span_grid(n, span)), dim3(256), 0, s, static_cast<const T*>(Y), K.scale, K.shift,
+                       static_cast<const T*>(R), K2 ? K2->scale : nullptr, K2 ? K2->shift : nullptr, static_cast<T*>(Z), n, C / vec - 1, relu,
+                       maskbits, span);
   });
   return check_launch("bn_act_fwd");
 }
@@ -276,8 +283,6 @@ int launch_bn_act_fwd(const void* Y, const float* scale, const float* shift, con
 // are read once: 20 instead of 24 bytes per element in pass 2 in fp32 (10 / 12 in bf16). Same arithmetic per element, block geometry
 // and summation order as two NB = 1 launches (bit-identical results). The mask comes as bits: block outputs always have them.
 // ---------------------------------------------------------------------------------------------------------
-struct BnCoef { const float* scale; const float* shift; const float* mean; const float* invstd; const float* c1; const float* c2; };
-
 // g = dz where the forward's output was positive, else 0; the source is picked per vector, outside the per-element loops
 template <class T, int V4, bool BITS_ONLY>
 __device__ __forceinline__ void relu_grad(const T* __restrict__ Zmask, const unsigned* __restrict__ Zbits, long long off,
@@ -398,12 +403,10 @@ static void run_bn_bwd_reduce(const void* dZ, const void* Zmask, const unsigned*
                      rows, C, cpb, rpb);
 }
 
-int launch_bn_bwd_reduce(const void* dZ, const void* Zmask, const unsigned* Zbits, const void* Y, const float* scale,
-                         const float* shift, const float* mean, const float* invstd, float* partials, long long rows, int C,
-                         int dt, hipStream_t s) {
+static int launch_bn_bwd_reduce(const void* dZ, const void* Zmask, const unsigned* Zbits, const void* Y, const BnCoef& A, float* partials,
+                                long long rows, int C, int dt, hipStream_t s) {
   R3M_REQUIRE(is_pow2(C) && C >= 4, "bn_bwd_reduce: C=%d must be a power of two >= 4", C);
   R3M_REQUIRE(!Zmask || bn_vec(dt, C) == 4, "bn_bwd_reduce(bf16): pass the 1-bit mask (zbits) or no mask; a bf16 zmask tensor is not supported");
-  const BnCoef A{scale, shift, mean, invstd, nullptr, nullptr};
   BN_DISPATCH(dt, bn_vec(dt, C), "bn_bwd_reduce", (run_bn_bwd_reduce<T, V4, 1>(dZ, Zmask, Zbits, Y, A, nullptr, A, partials, 0, rows, C, s)));
   return check_launch("bn_bwd_reduce");
 }
@@ -424,12 +427,17 @@ __global__ __launch_bounds__(64 * SG) void bn_bwd_finalize_kernel(const double* 
   c2[c] = use_batch_stats ? (float)(sgy * inv_count) : 0.f;
 }
 
-int launch_bn_bwd_finalize_rows(const double* acc, int stat_rows, long long count, int use_batch_stats, float* dgamma,
-                                float* dbeta, float* c1, float* c2, int accumulate, int C, hipStream_t s,
-                                const float* second_sum_scale) {
+static int launch_bn_bwd_finalize_rows(const double* acc, int stat_rows, long long count, int use_batch_stats, const BnBwdOut& o, int C,
+                                       hipStream_t s, const float* second_sum_scale) {
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(ceil_div(C, 64)), dim3(64 * SG), 0, s, acc, reduce_slices(stat_rows, C),
-                     1.0 / (double)count, use_batch_stats, dgamma, dbeta, c1, c2, accumulate, C, second_sum_scale);
+                     1.0 / (double)count, use_batch_stats, o.dgamma, o.dbeta, o.c1, o.c2, o.accumulate, C, second_sum_scale);
   return check_launch("bn_bwd_finalize");
+}
+
+int bn_bwd_combine(const float* partial, int prow, long long count, int use_batch_stats, const BnBwdOut& o, const float* second_sum_scale,
+                   int C, double* acc, hipStream_t s) {
+  TRY(launch_bn_stats_reduce(partial, prow, C, acc, s));
+  return launch_bn_bwd_finalize_rows(acc, prow, count, use_batch_stats, o, C, s, second_sum_scale);
 }
 
 // one BatchNorm's pass-2 coefficients of a thread's V channels
@@ -491,33 +499,25 @@ static void run_bn_bwd_apply(const void* dZ, const void* Zmask, const unsigned* 
                      static_cast<T*>(dYB), n, C / (4 * V4) - 1, span);
 }
 
-int launch_bn_bwd_apply(const void* dZ, const void* Zmask, const unsigned* Zbits, const void* Y, const float* scale,
-                        const float* shift, const float* mean, const float* invstd, const float* c1, const float* c2, void* dY,
-                        long long rows, int C, int dt, hipStream_t s) {
+static int launch_bn_bwd_apply(const void* dZ, const void* Zmask, const unsigned* Zbits, const void* Y, const BnCoef& A, void* dY,
+                               long long rows, int C, int dt, hipStream_t s) {
   R3M_REQUIRE(is_pow2(C) && C >= 4, "bn_bwd_apply: C=%d must be a power of two >= 4", C);
-  const BnCoef A{scale, shift, mean, invstd, c1, c2};
   BN_DISPATCH(dt, Zmask ? 4 : bn_vec(dt, C), "bn_bwd_apply",   // a Zmask source is 4-wide; launch_bn_bwd_reduce has refused it for bf16 by now
               (run_bn_bwd_apply<T, V4, 1>(dZ, Zmask, Zbits, Y, A, dY, nullptr, A, nullptr, rows, C, s)));
   return check_launch("bn_bwd_apply");
 }
 
-// coefA / coefB: the layer's coefficient block [6][C] = {mean, invstd, scale, shift, c1, c2} (engine.hip coef())
-static inline BnCoef coef_block(const float* k, int C) { return BnCoef{k + 2LL * C, k + 3LL * C, k, k + C, k + 4LL * C, k + 5LL * C}; }
-
-// true: launched (bf16 plans with C a multiple of 8); false: the caller runs two stand-alone first passes
-bool bn_bwd_reduce2_available(int C, int dt) { return bn_vec(dt, C) == 8; }
-int launch_bn_bwd_reduce2(const void* dZ, const unsigned* Zbits, const void* YA, const float* coefA, const void* YB, const float* coefB,
-                          float* partials, long long set_stride, long long rows, int C, int dt, hipStream_t s) {
+static int launch_bn_bwd_reduce2(const void* dZ, const unsigned* Zbits, const void* YA, const BnCoef& A, const void* YB, const BnCoef& B,
+                                 float* partials, long long set_stride, long long rows, int C, int dt, hipStream_t s) {
   R3M_REQUIRE(is_pow2(C) && bn_vec(dt, C) == 8 && Zbits, "bn_bwd_reduce2: bf16 plans with mask bits only (C=%d dtype=%d)", C, dt);
   R3M_REQUIRE((long long)bn_bwd_partial_rows(rows, C, dt) * 2 * C <= set_stride, "bn_bwd_reduce2: partial sets overlap");
-  run_bn_bwd_reduce<bf16_t, 2, 2>(dZ, nullptr, Zbits, YA, coef_block(coefA, C), YB, coef_block(coefB, C), partials, set_stride, rows, C, s);
+  run_bn_bwd_reduce<bf16_t, 2, 2>(dZ, nullptr, Zbits, YA, A, YB, B, partials, set_stride, rows, C, s);
   return check_launch("bn_bwd_reduce2");
 }
 
-int launch_bn_bwd_apply2(const void* dZ, const unsigned* Zbits, const void* YA, const float* coefA, void* dYA, const void* YB,
-                         const float* coefB, void* dYB, long long rows, int C, int dt, hipStream_t s) {
+static int launch_bn_bwd_apply2(const void* dZ, const unsigned* Zbits, const void* YA, const BnCoef& A, void* dYA, const void* YB,
+                                const BnCoef& B, void* dYB, long long rows, int C, int dt, hipStream_t s) {
   R3M_REQUIRE(is_pow2(C) && C >= 8 && Zbits, "bn_bwd_apply2: C=%d must be a power of two >= 8 and the mask must come as bits", C);
-  const BnCoef A = coef_block(coefA, C), B = coef_block(coefB, C);
   if (bn_vec(dt, C) == 8) {
     run_bn_bwd_apply<bf16_t, 2, 2>(dZ, nullptr, Zbits, YA, A, dYA, YB, B, dYB, rows, C, s);
   } else {
@@ -525,6 +525,39 @@ int launch_bn_bwd_apply2(const void* dZ, const unsigned* Zbits, const void* YA, 
     run_bn_bwd_apply<float, 1, 2>(dZ, nullptr, Zbits, YA, A, dYA, YB, B, dYB, rows, C, s);
   }
   return check_launch("bn_bwd_apply2");
+}
+
+// ---- the backward sequences (common.h): what the engine's step and the C ABI's bn_bwd entry points both run ----
+// b's sums: its first pass into w.partial, or the `fused_rows` EPI_BNRED rows a dgrad left in `fused`, then the combine
+static int bn_bwd_sums(const void* dZ, const void* Zmask, const unsigned* Zbits, const BnBwdSide& b, const float* fused, int fused_rows,
+                       long long rows, int C, int use_batch_stats, const BnScratch& w, int dt, hipStream_t s) {
+  if (fused_rows) return bn_bwd_combine(fused, fused_rows, rows, use_batch_stats, b.out, b.K.invstd, C, w.acc, s);
+  TRY(launch_bn_bwd_reduce(dZ, Zmask, Zbits, b.Y, b.K, w.partial, rows, C, dt, s));
+  return bn_bwd_combine(w.partial, bn_bwd_partial_rows(rows, C, dt), rows, use_batch_stats, b.out, nullptr, C, w.acc, s);
+}
+
+int bn_bwd(const void* dZ, const void* Zmask, const unsigned* Zbits, const BnBwdSide& b, const float* fused, int fused_rows, bool apply,
+           long long rows, int C, int use_batch_stats, const BnScratch& w, int dt, hipStream_t s) {
+  if (b.sums) TRY(bn_bwd_sums(dZ, Zmask, Zbits, b, fused, fused_rows, rows, C, use_batch_stats, w, dt, s));
+  if (!apply) return 0;
+  return launch_bn_bwd_apply(dZ, Zmask, Zbits, b.Y, b.apply_coef(), b.dY, rows, C, dt, s);
+}
+
+int bn_bwd_pair(const void* dZ, const unsigned* Zbits, const BnBwdSide& a, const BnBwdSide& b, const float* fused_a, int fused_rows_a,
+                bool apply, long long set_stride, long long rows, int C, int use_batch_stats, const BnScratch& w, int dt, hipStream_t s) {
+  if (!fused_rows_a && bn_vec(dt, C) == 8) {
+    // both first passes are stand-alone and the joint kernel exists (bf16, C a multiple of 8): one launch, two partial sets, then the
+    // two combines one after the other (one accumulator)
+    const int prow = bn_bwd_partial_rows(rows, C, dt);
+    TRY(launch_bn_bwd_reduce2(dZ, Zbits, a.Y, a.K, b.Y, b.K, w.partial, set_stride, rows, C, dt, s));
+    if (a.sums) TRY(bn_bwd_combine(w.partial, prow, rows, use_batch_stats, a.out, nullptr, C, w.acc, s));
+    if (b.sums) TRY(bn_bwd_combine(w.partial + set_stride, prow, rows, use_batch_stats, b.out, nullptr, C, w.acc, s));
+  } else {
+    if (a.sums) TRY(bn_bwd_sums(dZ, nullptr, Zbits, a, fused_a, fused_rows_a, rows, C, use_batch_stats, w, dt, s));
+    if (b.sums) TRY(bn_bwd_sums(dZ, nullptr, Zbits, b, nullptr, 0, rows, C, use_batch_stats, w, dt, s));
+  }
+  if (!apply) return 0;
+  return launch_bn_bwd_apply2(dZ, Zbits, a.Y, a.apply_coef(), a.dY, b.Y, b.apply_coef(), b.dY, rows, C, dt, s);
 }
 
 // What the launchers above pick for a [rows][C] tensor, without launching anything (r3m_debug_bn_geometry; the index names are in

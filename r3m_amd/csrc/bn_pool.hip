@@ -252,21 +252,21 @@ static inline int ilog2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; retu
 // threads of a block that owns Wo x CV (pixel, channel-vector) items: all of them when they fit, else 1024 (a multiple of CV <= 256)
 static inline int pool_row_threads(int items) { return items >= 1024 ? 1024 : (items + 63) / 64 * 64; }
 
-int launch_bn_relu_maxpool_fwd(const void* Y, const float* scale, const float* shift, void* P, unsigned char* amax, int N, int Hi,
-                               int Wi, int C, int dt, hipStream_t s) {
+int launch_bn_relu_maxpool_fwd(const void* Y, const BnCoef& K, void* P, unsigned char* amax, int N, int Hi, int Wi, int C, int dt,
+                               hipStream_t s) {
   const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
   R3M_REQUIRE(C % 8 == 0, "bn_relu_maxpool_fwd: C=%d must be a multiple of 8", C);
   if (dt == DT_BF16 && is_pow2(C) && C <= 2048) {
     const int CV = C / 8, segs = ceil_div(Ho, POOL_SEG);
     hipLaunchKernelGGL(bn_relu_maxpool_fwd16_kernel, dim3(N * segs), dim3(pool_row_threads(Wo * CV)), 0, s,
-                       static_cast<const bf16_t*>(Y), scale, shift, static_cast<bf16_t*>(P), amax, Hi, Wi, Ho, Wo, CV, ilog2_exact(CV), segs);
+                       static_cast<const bf16_t*>(Y), K.scale, K.shift, static_cast<bf16_t*>(P), amax, Hi, Wi, Ho, Wo, CV, ilog2_exact(CV), segs);
     return check_launch("bn_relu_maxpool_fwd16");
   }
   DT_DISPATCH(dt, "bn_relu_maxpool_fwd", {
     constexpr int V = 4 * PoolVec<T>::V4;
     const long long total = (long long)N * Ho * Wo * (C / V);
-    hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<T>), dim3(ceil_div(total, 256)), dim3(256), 0, s, static_cast<const T*>(Y), scale,
-                       shift, static_cast<T*>(P), amax, total, Hi, Wi, Ho, Wo, C / V);
+    hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<T>), dim3(ceil_div(total, 256)), dim3(256), 0, s, static_cast<const T*>(Y), K.scale,
+                       K.shift, static_cast<T*>(P), amax, total, Hi, Wi, Ho, Wo, C / V);
   });
   return check_launch("bn_relu_maxpool_fwd");
 }
@@ -465,9 +465,8 @@ int bn_bwd_pool_partial_rows(int N, int Hi, int Wi, int C) {
   return nblk;
 }
 
-int launch_bn_bwd_reduce_pool(const void* dP, const unsigned char* amax, const void* Y, const float* scale, const float* shift,
-                              const float* mean, const float* invstd, float* partials, int N, int Hi, int Wi, int C, int dt,
-                              hipStream_t s) {
+static int launch_bn_bwd_reduce_pool(const void* dP, const unsigned char* amax, const void* Y, const BnCoef& K, float* partials, int N,
+                                     int Hi, int Wi, int C, int dt, hipStream_t s) {
   R3M_REQUIRE(is_pow2(C) && C >= 8 && C <= 1024, "bn_bwd_reduce_pool: C=%d must be a power of two in [8, 1024]", C);
   const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
   int rq, nblk;
@@ -476,25 +475,34 @@ int launch_bn_bwd_reduce_pool(const void* dP, const unsigned char* amax, const v
     constexpr int V4 = PoolVec<T>::V4, V = 4 * V4;
     const int CV = C / V, nt = pool_row_threads(Wo * CV);
     hipLaunchKernelGGL((bn_bwd_reduce_pool_kernel<T>), dim3(nblk), dim3(nt), (size_t)2 * V4 * nt * sizeof(f32x4), s,
-                       static_cast<const T*>(dP), amax, static_cast<const T*>(Y), scale, shift, mean, invstd, partials, N * Ho, rq, C,
+                       static_cast<const T*>(dP), amax, static_cast<const T*>(Y), K.scale, K.shift, K.mean, K.invstd, partials, N * Ho, rq, C,
                        CV, ilog2_exact(CV), Hi, Wi, Ho, Wo);
   });
   return check_launch("bn_bwd_reduce_pool");
 }
 
-int launch_bn_bwd_apply_pool(const void* dP, const unsigned char* amax, const void* Y, const float* scale, const float* shift,
-                             const float* mean, const float* invstd, const float* c1, const float* c2, void* dY, int N, int Hi, int Wi,
-                             int C, int dt, hipStream_t s) {
+static int launch_bn_bwd_apply_pool(const void* dP, const unsigned char* amax, const void* Y, const BnCoef& K, void* dY, int N, int Hi,
+                                    int Wi, int C, int dt, hipStream_t s) {
   const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
   R3M_REQUIRE(is_pow2(C) && C >= 8 && C <= 1024, "bn_bwd_apply_pool: C=%d must be a power of two in [8, 1024]", C);
   DT_DISPATCH(dt, "bn_bwd_apply_pool", {
     constexpr int V = 4 * PoolVec<T>::V4;
     const int CV = C / V;
     hipLaunchKernelGGL((bn_bwd_apply_pool_kernel<T>), dim3(N * Ho), dim3(pool_row_threads(Wo * CV)), 0, s, static_cast<const T*>(dP),
-                       amax, static_cast<const T*>(Y), scale, shift, mean, invstd, c1, c2, static_cast<T*>(dY), CV, ilog2_exact(CV), Hi, Wi,
-                       Ho, Wo);
+                       amax, static_cast<const T*>(Y), K.scale, K.shift, K.mean, K.invstd, K.c1, K.c2, static_cast<T*>(dY), CV,
+                       ilog2_exact(CV), Hi, Wi, Ho, Wo);
   });
   return check_launch("bn_bwd_apply_pool");
+}
+
+int bn_bwd_pool(const void* dP, const unsigned char* amax, const BnBwdSide& b, bool apply, int N, int Hi, int Wi, int C,
+                int use_batch_stats, const BnScratch& w, int dt, hipStream_t s) {
+  if (b.sums) {
+    TRY(launch_bn_bwd_reduce_pool(dP, amax, b.Y, b.K, w.partial, N, Hi, Wi, C, dt, s));
+    TRY(bn_bwd_combine(w.partial, bn_bwd_pool_partial_rows(N, Hi, Wi, C), (long long)N * Hi * Wi, use_batch_stats, b.out, nullptr, C, w.acc, s));
+  }
+  if (!apply) return 0;
+  return launch_bn_bwd_apply_pool(dP, amax, b.Y, b.apply_coef(), b.dY, N, Hi, Wi, C, dt, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------

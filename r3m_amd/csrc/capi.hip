@@ -329,23 +329,22 @@ int r3m_conv2d_fwd(const float* x, const float* w, float* y, float* stats, int N
   return r3m_conv2d_fwd_dt(x, w, y, stats, N, Hi, Wi, Ci, Co, k, stride, pad, DT_F32, stream);
 }
 size_t r3m_conv2d_dgrad_workspace_bytes(int Ci, int Co, int k) { return (size_t)Ci * Co * k * k * 4; }
+// the r3m_conv2d_dgrad*_dt entry points: the workspace receives the layer's [Ci][k*k][Co] weight image in the activation type
+static int dgrad_weight_image(const char* what, const float* w, void* ws, size_t ws_bytes, int Ci, int Co, int k, int dtype, hipStream_t s) {
+  R3M_REQUIRE(ws_bytes >= r3m_conv2d_dgrad_workspace_bytes(Ci, Co, k), "%s: workspace too small", what);
+  if (dtype == DT_BF16) return launch_transpose_w_bf16(w, ws, Co, k * k, Ci, s);
+  return launch_transpose_w(w, static_cast<float*>(ws), Co, k * k, Ci, s);
+}
 int r3m_conv2d_dgrad_dt(const void* dy, const float* w, void* dx, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int Ci, int Co,
                         int k, int stride, int pad, int dtype, r3m_stream_t stream) {
   if (check_dt(dtype, "conv2d_dgrad")) return 1;
-  R3M_REQUIRE(ws_bytes >= r3m_conv2d_dgrad_workspace_bytes(Ci, Co, k), "conv2d_dgrad: workspace too small");
-  float* Wt = static_cast<float*>(ws);
-  if (dtype == DT_BF16) { if (int e = launch_transpose_w_bf16(w, Wt, Co, k * k, Ci, S(stream))) return e; }
-  else if (int e = launch_transpose_w(w, Wt, Co, k * k, Ci, S(stream))) return e;
-  return conv_dgrad_launch(FP(dy), Wt, FPM(dx), nullptr, nullptr, nullptr, {N, Hi, Wi, Ci, Co, k, stride, pad}, 0, dtype, S(stream));
+  if (int e = dgrad_weight_image("conv2d_dgrad", w, ws, ws_bytes, Ci, Co, k, dtype, S(stream))) return e;
+  return conv_dgrad_launch(FP(dy), FP(ws), FPM(dx), nullptr, nullptr, nullptr, {N, Hi, Wi, Ci, Co, k, stride, pad}, 0, dtype, S(stream));
 }
 int r3m_conv2d_dgrad_bnred_rows(int N, int Hi, int Wi, int stride) {
   if (stride == 1) return bnred_partial_rows((long long)N * Hi * Wi);
   int rows = 0;
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      const int Hg = (Hi - py + 1) / 2, Wg = (Wi - px + 1) / 2;
-      if (Hg > 0 && Wg > 0) rows += bnred_partial_rows((long long)N * Hg * Wg);
-    }
+  for_each_parity_class(Hi, Wi, [&](int, int, int Hg, int Wg) { rows += bnred_partial_rows((long long)N * Hg * Wg); return 0; });
   return rows;
 }
 int r3m_conv2d_dgrad_bnred_dt(const void* dy, const float* w, void* dx, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int Ci, int Co,
@@ -357,12 +356,9 @@ int r3m_conv2d_dgrad_bnred_dt(const void* dy, const float* w, void* dx, void* ws
   R3M_REQUIRE(bn_bits || (bn_scale && bn_shift), "conv2d_dgrad_bnred: pass the mask bits or scale + shift to recompute the mask");
   R3M_REQUIRE(!residual_grad || residual_bits, "conv2d_dgrad_bnred: a residual gradient needs its mask bits");
   R3M_REQUIRE(!(k == 1 && stride == 2), "conv2d_dgrad_bnred: 1x1 stride-2 (parity classes without taps) is not supported");
-  R3M_REQUIRE(ws_bytes >= r3m_conv2d_dgrad_workspace_bytes(Ci, Co, k), "conv2d_dgrad_bnred: workspace too small");
-  float* Wt = static_cast<float*>(ws);
-  if (dtype == DT_BF16) { if (int e = launch_transpose_w_bf16(w, Wt, Co, k * k, Ci, S(stream))) return e; }
-  else if (int e = launch_transpose_w(w, Wt, Co, k * k, Ci, S(stream))) return e;
+  if (int e = dgrad_weight_image("conv2d_dgrad_bnred", w, ws, ws_bytes, Ci, Co, k, dtype, S(stream))) return e;
   BnRedArgs br{FP(bn_y), bn_bits, bn_scale, bn_shift, bn_mean, partials, 0};
-  return conv_dgrad_launch(FP(dy), Wt, FPM(dx), FP(residual_grad), nullptr, residual_bits, {N, Hi, Wi, Ci, Co, k, stride, pad},
+  return conv_dgrad_launch(FP(dy), FP(ws), FPM(dx), FP(residual_grad), nullptr, residual_bits, {N, Hi, Wi, Ci, Co, k, stride, pad},
                            residual_grad ? EPI_MASKED_ADD : 0, dtype, S(stream), &br);
 }
 int r3m_conv2d_dgrad_join_dt(const void* dy, const float* w, void* dx, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int Ci, int Co, int k,
@@ -373,11 +369,8 @@ int r3m_conv2d_dgrad_join_dt(const void* dy, const float* w, void* dx, void* ws,
   R3M_REQUIRE((accumulate != 0) != (residual_grad != nullptr), "conv2d_dgrad_join: pass accumulate = 1 or a residual gradient, one of the two");
   R3M_REQUIRE(!accumulate || (k == 1 && pad == 0), "conv2d_dgrad_join: accumulate is the downsample branch's (k = 1, pad 0), not k=%d pad=%d", k, pad);
   R3M_REQUIRE(!residual_grad || (residual_bits && stride == 1), "conv2d_dgrad_join: a residual gradient needs its mask bits and stride 1");
-  R3M_REQUIRE(ws_bytes >= r3m_conv2d_dgrad_workspace_bytes(Ci, Co, k), "conv2d_dgrad_join: workspace too small");
-  float* Wt = static_cast<float*>(ws);
-  if (dtype == DT_BF16) { if (int e = launch_transpose_w_bf16(w, Wt, Co, k * k, Ci, S(stream))) return e; }
-  else if (int e = launch_transpose_w(w, Wt, Co, k * k, Ci, S(stream))) return e;
-  return conv_dgrad_launch(FP(dy), Wt, FPM(dx), FP(residual_grad), nullptr, residual_bits, {N, Hi, Wi, Ci, Co, k, stride, pad},
+  if (int e = dgrad_weight_image("conv2d_dgrad_join", w, ws, ws_bytes, Ci, Co, k, dtype, S(stream))) return e;
+  return conv_dgrad_launch(FP(dy), FP(ws), FPM(dx), FP(residual_grad), nullptr, residual_bits, {N, Hi, Wi, Ci, Co, k, stride, pad},
                            accumulate ? EPI_ACCUM : EPI_MASKED_ADD, dtype, S(stream));
 }
 int r3m_conv2d_fwd_affine_dt(const void* x, const void* w, void* out, const float* scale, const float* shift, int N, int Hi, int Wi, int Ci,
@@ -490,32 +483,37 @@ int r3m_stem_conv_wgrad_bf16(const void* xn16, const void* dy, float* dw_ohwi, v
   return launch_stem_wgrad16(xn16, dy, dw_ohwi, static_cast<float*>(ws), frames, accumulate, S(stream));
 }
 
-// workspace: [partials: bn_bwd_partial_rows*2*C floats][acc: 64*2*C doubles]
+// BatchNorm: argument checks and workspace carving here, the launch sequences in bn.hip / bn_pool.hip (the ones the engine runs).
+// workspace of a backward: [partials: bn_bwd_partial_rows*2*C floats][acc: bn_acc_bytes(C)][c1, c2: 2*C floats]
 static size_t bn_acc_off(long long rows, int C) {
   size_t p = (size_t)bn_bwd_partial_rows(rows, C, DT_F32) * 2 * C * 4;   // the fp32 geometry has the most rows
   return (p + 255) / 256 * 256;
 }
 static size_t bn_c12_off(long long rows, int C) { return bn_acc_off(rows, C) + bn_acc_bytes(C); }
 size_t r3m_bn_workspace_bytes(long long rows, int C) { return bn_c12_off(rows, C) + (size_t)2 * C * 4; }
+static char* ws_at(void* ws, size_t off) { return static_cast<char*>(ws) + off; }
+// one BatchNorm of a backward with its coefficient block in `coef` and c1 / c2 in c12[2][C]
+static BnBwdSide bn_side(const void* y, const float* coef, float* dgamma, float* dbeta, float* c12, void* dy, int C, int accumulate) {
+  return {y, bn_coef_block(coef, C), {dgamma, dbeta, c12, c12 + C, accumulate}, dy, true};
+}
 
 int r3m_bn_train_coeffs(const float* stats, int stats_rows, long long count, const float* gamma, const float* beta, float* rm,
                         float* rv, float momentum, float eps, float* coef, void* ws, size_t ws_bytes, int C, r3m_stream_t stream) {
   R3M_REQUIRE(ws_bytes >= bn_acc_bytes(C), "bn_train_coeffs: workspace too small (need %zu)", bn_acc_bytes(C));
-  double* acc = static_cast<double*>(ws);
-  if (int e = launch_bn_stats_reduce(stats, stats_rows, C, acc, S(stream))) return e;
-  return launch_bn_finalize_rows(acc, stats_rows, count, gamma, beta, rm, rv, momentum, eps, coef, coef + C, coef + 2 * C,
-                                 coef + 3 * C, C, S(stream));
+  return bn_train_coeffs(stats, stats_rows, count, gamma, beta, rm, rv, momentum, eps, bn_coef_out(coef, C), C, static_cast<double*>(ws),
+                         S(stream));
 }
 int r3m_bn_eval_coeffs(const float* gamma, const float* beta, const float* rm, const float* rv, float eps, float* coef, int C,
                        r3m_stream_t stream) {
-  return launch_bn_eval_coeffs(gamma, beta, rm, rv, eps, coef, coef + C, coef + 2 * C, coef + 3 * C, C, S(stream));
+  return launch_bn_eval_coeffs(gamma, beta, rm, rv, eps, bn_coef_out(coef, C), C, S(stream));
 }
 int r3m_bn_act_fwd_dt(const void* y, const float* coef, const void* r, const void* y2, const float* coef2, void* z, long long rows,
                       int C, int relu, unsigned* maskbits, int dtype, r3m_stream_t stream) {
   R3M_REQUIRE(!(r && y2), "bn_act_fwd: pass either r (identity) or y2/coef2 (downsample), not both");
   if (check_dt(dtype, "bn_act_fwd")) return 1;
-  if (y2) return launch_bn_act_fwd(y, coef + 2 * C, coef + 3 * C, y2, coef2 + 2 * C, coef2 + 3 * C, z, rows, C, relu, maskbits, dtype, S(stream));
-  return launch_bn_act_fwd(y, coef + 2 * C, coef + 3 * C, r, nullptr, nullptr, z, rows, C, relu, maskbits, dtype, S(stream));
+  if (!y2) return launch_bn_act_fwd(y, bn_coef_block(coef, C), r, nullptr, z, rows, C, relu, maskbits, dtype, S(stream));
+  const BnCoef K2 = bn_coef_block(coef2, C);
+  return launch_bn_act_fwd(y, bn_coef_block(coef, C), y2, &K2, z, rows, C, relu, maskbits, dtype, S(stream));
 }
 int r3m_bn_act_fwd(const float* y, const float* coef, const float* r, const float* y2, const float* coef2, float* z, long long rows,
                    int C, int relu, unsigned* maskbits, r3m_stream_t stream) {
@@ -526,22 +524,17 @@ int r3m_bn_bwd_dt(const void* dz, const void* zmask, const unsigned* zbits, cons
                   int dtype, r3m_stream_t stream) {
   if (check_dt(dtype, "bn_bwd")) return 1;
   R3M_REQUIRE(ws_bytes >= r3m_bn_workspace_bytes(rows, C), "bn_bwd: workspace too small (need %zu)", r3m_bn_workspace_bytes(rows, C));
-  float* partial = static_cast<float*>(ws);
-  double* acc = reinterpret_cast<double*>(static_cast<char*>(ws) + bn_acc_off(rows, C));
-  float* c12 = reinterpret_cast<float*>(static_cast<char*>(ws) + bn_c12_off(rows, C));
-  const float *mean = coef, *invstd = coef + C, *scale = coef + 2 * C, *shift = coef + 3 * C;
-  if (int e = launch_bn_bwd_reduce(dz, zmask, zbits, y, scale, shift, mean, invstd, partial, rows, C, dtype, S(stream))) return e;
-  const int prow = bn_bwd_partial_rows(rows, C, dtype);
-  if (int e = launch_bn_stats_reduce(partial, prow, C, acc, S(stream))) return e;
-  if (int e = launch_bn_bwd_finalize_rows(acc, prow, rows, use_batch_stats, dgamma, dbeta, c12, c12 + C, accumulate, C, S(stream))) return e;
-  return launch_bn_bwd_apply(dz, zmask, zbits, y, scale, shift, mean, invstd, c12, c12 + C, dy, rows, C, dtype, S(stream));
+  const BnScratch w{static_cast<float*>(ws), reinterpret_cast<double*>(ws_at(ws, bn_acc_off(rows, C)))};
+  float* c12 = reinterpret_cast<float*>(ws_at(ws, bn_c12_off(rows, C)));
+  return bn_bwd(dz, zmask, zbits, bn_side(y, coef, dgamma, dbeta, c12, dy, C, accumulate), nullptr, 0, true, rows, C, use_batch_stats, w, dtype,
+                S(stream));
 }
 int r3m_bn_bwd(const float* dz, const float* zmask, const unsigned* zbits, const float* y, const float* coef, float* dgamma,
                float* dbeta, float* dy, void* ws, size_t ws_bytes, long long rows, int C, int use_batch_stats, int accumulate, r3m_stream_t stream) {
   return r3m_bn_bwd_dt(dz, zmask, zbits, y, coef, dgamma, dbeta, dy, ws, ws_bytes, rows, C, use_batch_stats, accumulate, DT_F32, stream);
 }
-// The two BatchNorms of a downsample block's tail, as the engine's bn_backward_pair runs them when no dgrad epilogue wrote the partials:
-// workspace = [partial set A][partial set B][acc]; c1 / c2 go to rows 4, 5 of each coefficient block, where the paired second pass reads them
+// The two BatchNorms of a downsample block's tail (bn_bwd_pair, no dgrad epilogue wrote the partials): workspace = [partial set A]
+// [partial set B][acc]; c1 / c2 go to rows 4, 5 of each coefficient block, where the paired second pass reads them
 size_t r3m_bn_pair_workspace_bytes(long long rows, int C) { return 2 * bn_acc_off(rows, C) + bn_acc_bytes(C); }
 int r3m_bn_bwd_pair_dt(const void* dz, const unsigned* zbits, const void* y_a, float* coef_a, const void* y_b, float* coef_b, float* dgamma_a,
                        float* dbeta_a, void* dy_a, float* dgamma_b, float* dbeta_b, void* dy_b, void* ws, size_t ws_bytes, long long rows, int C,
@@ -551,30 +544,13 @@ int r3m_bn_bwd_pair_dt(const void* dz, const unsigned* zbits, const void* y_a, f
               "bn_bwd_pair: null argument");
   R3M_REQUIRE(rows >= 1 && C >= 8, "bn_bwd_pair: rows=%lld C=%d", rows, C);
   R3M_REQUIRE(ws_bytes >= r3m_bn_pair_workspace_bytes(rows, C), "bn_bwd_pair: workspace too small (need %zu)", r3m_bn_pair_workspace_bytes(rows, C));
-  float* partial = static_cast<float*>(ws);
-  const long long set = (long long)(bn_acc_off(rows, C) / 4);
-  double* acc = reinterpret_cast<double*>(static_cast<char*>(ws) + 2 * bn_acc_off(rows, C));
-  const int prow = bn_bwd_partial_rows(rows, C, dtype);
-  auto combine = [&](const float* p, float* coef, float* dgamma, float* dbeta) -> int {
-    if (int e = launch_bn_stats_reduce(p, prow, C, acc, S(stream))) return e;
-    return launch_bn_bwd_finalize_rows(acc, prow, rows, use_batch_stats, dgamma, dbeta, coef + 4LL * C, coef + 5LL * C, accumulate, C, S(stream));
-  };
-  auto sums = [&](const void* y, float* coef, float* dgamma, float* dbeta) -> int {
-    if (int e = launch_bn_bwd_reduce(dz, nullptr, zbits, y, coef + 2LL * C, coef + 3LL * C, coef, coef + C, partial, rows, C, dtype, S(stream))) return e;
-    return combine(partial, coef, dgamma, dbeta);
-  };
-  if (bn_bwd_reduce2_available(C, dtype)) {
-    if (int e = launch_bn_bwd_reduce2(dz, zbits, y_a, coef_a, y_b, coef_b, partial, set, rows, C, dtype, S(stream))) return e;
-    if (int e = combine(partial, coef_a, dgamma_a, dbeta_a)) return e;
-    if (int e = combine(partial + set, coef_b, dgamma_b, dbeta_b)) return e;
-  } else {
-    if (int e = sums(y_a, coef_a, dgamma_a, dbeta_a)) return e;
-    if (int e = sums(y_b, coef_b, dgamma_b, dbeta_b)) return e;
-  }
-  return launch_bn_bwd_apply2(dz, zbits, y_a, coef_a, dy_a, y_b, coef_b, dy_b, rows, C, dtype, S(stream));
+  const BnScratch w{static_cast<float*>(ws), reinterpret_cast<double*>(ws_at(ws, 2 * bn_acc_off(rows, C)))};
+  const BnBwdSide a{y_a, bn_coef_block(coef_a, C), bn_bwd_out(dgamma_a, dbeta_a, coef_a, C, accumulate), dy_a, true};
+  const BnBwdSide b{y_b, bn_coef_block(coef_b, C), bn_bwd_out(dgamma_b, dbeta_b, coef_b, C, accumulate), dy_b, true};
+  return bn_bwd_pair(dz, zbits, a, b, nullptr, 0, true, (long long)(bn_acc_off(rows, C) / 4), rows, C, use_batch_stats, w, dtype, S(stream));
 }
-// BatchNorm backward behind a dgrad whose epilogue wrote the first pass (r3m_conv2d_dgrad_bnred_dt), as the engine's bn_backward runs it
-// with fused_rows > 0: combine the partial rows (second sum x invstd), then the second pass. workspace: [acc][c1, c2]
+// BatchNorm backward behind a dgrad whose epilogue wrote the first pass (r3m_conv2d_dgrad_bnred_dt): bn_bwd with fused rows — combine
+// the partial rows (second sum x invstd), then the second pass. workspace: [acc][c1, c2]
 int r3m_bn_bwd_from_partials_dt(const void* dz, const unsigned* zbits, const void* y, const float* coef, const float* partials, int partial_rows,
                                 float* dgamma, float* dbeta, void* dy, void* ws, size_t ws_bytes, long long rows, int C, int use_batch_stats,
                                 int accumulate, int dtype, r3m_stream_t stream) {
@@ -582,12 +558,10 @@ int r3m_bn_bwd_from_partials_dt(const void* dz, const unsigned* zbits, const voi
   R3M_REQUIRE(dz && y && coef && partials && dgamma && dbeta && dy && ws, "bn_bwd_from_partials: null argument");
   R3M_REQUIRE(rows >= 1 && partial_rows >= 1, "bn_bwd_from_partials: rows=%lld partial_rows=%d", rows, partial_rows);
   R3M_REQUIRE(ws_bytes >= bn_acc_bytes(C) + (size_t)2 * C * 4, "bn_bwd_from_partials: workspace too small (need %zu)", bn_acc_bytes(C) + (size_t)2 * C * 4);
-  double* acc = static_cast<double*>(ws);
-  float* c12 = reinterpret_cast<float*>(static_cast<char*>(ws) + bn_acc_bytes(C));
-  const float *mean = coef, *invstd = coef + C, *scale = coef + 2 * C, *shift = coef + 3 * C;
-  if (int e = launch_bn_stats_reduce(partials, partial_rows, C, acc, S(stream))) return e;
-  if (int e = launch_bn_bwd_finalize_rows(acc, partial_rows, rows, use_batch_stats, dgamma, dbeta, c12, c12 + C, accumulate, C, S(stream), invstd)) return e;
-  return launch_bn_bwd_apply(dz, nullptr, zbits, y, scale, shift, mean, invstd, c12, c12 + C, dy, rows, C, dtype, S(stream));
+  const BnScratch w{nullptr, static_cast<double*>(ws)};   // no first pass: the rows come from the caller
+  float* c12 = reinterpret_cast<float*>(ws_at(ws, bn_acc_bytes(C)));
+  return bn_bwd(dz, nullptr, zbits, bn_side(y, coef, dgamma, dbeta, c12, dy, C, accumulate), partials, partial_rows, true, rows, C,
+                use_batch_stats, w, dtype, S(stream));
 }
 int r3m_debug_bn_geometry(long long rows, int C, int dtype, int* out, int cap) { return bn_debug_geometry(rows, C, dtype, out, cap) ? -1 : 14; }
 // stem tail fused: BatchNorm + ReLU + MaxPool(3,2,1) forward, and its backward (MaxPool gather inside both BN-backward passes)
@@ -595,7 +569,7 @@ int r3m_bn_relu_maxpool_fwd_dt(const void* y, const float* coef, void* p, unsign
                                r3m_stream_t stream) {
   R3M_REQUIRE(y && coef && p && am, "bn_relu_maxpool_fwd: null argument");
   if (check_dt(dtype, "bn_relu_maxpool_fwd")) return 1;
-  return launch_bn_relu_maxpool_fwd(y, coef + 2 * C, coef + 3 * C, p, am, N, Hi, Wi, C, dtype, S(stream));
+  return launch_bn_relu_maxpool_fwd(y, bn_coef_block(coef, C), p, am, N, Hi, Wi, C, dtype, S(stream));
 }
 int r3m_bn_maxpool_bwd_dt(const void* dp, const unsigned char* am, const void* y, const float* coef, float* dgamma, float* dbeta, void* dy,
                           void* ws, size_t ws_bytes, int N, int Hi, int Wi, int C, int use_batch_stats, int accumulate, int dtype,
@@ -604,15 +578,9 @@ int r3m_bn_maxpool_bwd_dt(const void* dp, const unsigned char* am, const void* y
   if (check_dt(dtype, "bn_maxpool_bwd")) return 1;
   const long long rows = (long long)N * Hi * Wi;
   R3M_REQUIRE(ws_bytes >= r3m_bn_workspace_bytes(rows, C), "bn_maxpool_bwd: workspace too small (need %zu)", r3m_bn_workspace_bytes(rows, C));
-  float* partial = static_cast<float*>(ws);
-  double* acc = reinterpret_cast<double*>(static_cast<char*>(ws) + bn_acc_off(rows, C));
-  float* c12 = reinterpret_cast<float*>(static_cast<char*>(ws) + bn_c12_off(rows, C));
-  const float *mean = coef, *invstd = coef + C, *scale = coef + 2 * C, *shift = coef + 3 * C;
-  if (int e = launch_bn_bwd_reduce_pool(dp, am, y, scale, shift, mean, invstd, partial, N, Hi, Wi, C, dtype, S(stream))) return e;
-  const int prow = bn_bwd_pool_partial_rows(N, Hi, Wi, C);
-  if (int e = launch_bn_stats_reduce(partial, prow, C, acc, S(stream))) return e;
-  if (int e = launch_bn_bwd_finalize_rows(acc, prow, rows, use_batch_stats, dgamma, dbeta, c12, c12 + C, accumulate, C, S(stream))) return e;
-  return launch_bn_bwd_apply_pool(dp, am, y, scale, shift, mean, invstd, c12, c12 + C, dy, N, Hi, Wi, C, dtype, S(stream));
+  const BnScratch w{static_cast<float*>(ws), reinterpret_cast<double*>(ws_at(ws, bn_acc_off(rows, C)))};
+  float* c12 = reinterpret_cast<float*>(ws_at(ws, bn_c12_off(rows, C)));
+  return bn_bwd_pool(dp, am, bn_side(y, coef, dgamma, dbeta, c12, dy, C, accumulate), true, N, Hi, Wi, C, use_batch_stats, w, dtype, S(stream));
 }
 int r3m_maxpool_fwd_dt(const void* z, void* p, unsigned char* am, int N, int Hi, int Wi, int C, int dtype, r3m_stream_t stream) {
   if (check_dt(dtype, "maxpool_fwd")) return 1;

@@ -34,6 +34,10 @@ int  check_launch(const char* what);  // hipGetLastError() -> 0 / code (+ messag
       return 1;                                 \
     }                                           \
   } while (0)
+#define TRY(x)                   \
+  do {                           \
+    if (int e_ = (x)) return e_; \
+  } while (0)
 
 static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
@@ -227,47 +231,57 @@ int launch_stem_wgrad_gen(const float* xn, const void* dY, float* dw147, float* 
 int launch_stem_input_grad_gen(const void* dz, int dt, const float* w147, float* dx, int F, int H, int W, int accumulate, hipStream_t s);
 int stem_gen_lds(int F, int H, int W, int* fwd, int* wgrad, int* dgrad);
 
-// ---- launchers (bn.hip) ----
-size_t bn_acc_bytes(int C);   // fp64 slice accumulator: [slices <= max(64, min(256, 131072 / C))][2][C]
-int launch_bn_stats_reduce(const float* partials, int rows, int C, double* acc /* bn_acc_bytes(C) */, hipStream_t s);
-int launch_bn_finalize_rows(const double* acc, int stat_rows, long long count, const float* gamma, const float* beta,
-                            float* running_mean, float* running_var, float momentum, float eps, float* mean,
-                            float* invstd, float* scale, float* shift, int C, hipStream_t s);
-int launch_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
-                          float eps, float* mean, float* invstd, float* scale, float* shift, int C, hipStream_t s);
+// ---- BatchNorm (bn.hip; the pooled stem tail: bn_pool.hip) ----
 // activation tensors are void*: fp32 (dt = DT_F32) or bf16 (DT_BF16); coefficients / partials / statistics are fp32
-int launch_bn_act_fwd(const void* Y, const float* scale, const float* shift, const void* R, const float* scale2,
-                      const float* shift2, void* Z, long long rows, int C, int relu, unsigned* maskbits, int dt, hipStream_t s);
+// One BatchNorm's per-channel vectors, [C] floats each. A by-value kernel argument: the field order is fixed.
+struct BnCoef { const float* scale; const float* shift; const float* mean; const float* invstd; const float* c1; const float* c2; };
+struct BnCoefOut { float* mean; float* invstd; float* scale; float* shift; };             // what a forward's coefficient pass writes
+struct BnBwdOut { float* dgamma; float* dbeta; float* c1; float* c2; int accumulate; };   // what a backward's combine writes (accumulate: sums +=)
+// A layer's coefficient block [6][C] = {mean, invstd, scale, shift, c1, c2}: these three know the row order, nobody else does
+static inline BnCoef bn_coef_block(const float* k, int C) { return {k + 2LL * C, k + 3LL * C, k, k + C, k + 4LL * C, k + 5LL * C}; }
+static inline BnCoefOut bn_coef_out(float* k, int C) { return {k, k + C, k + 2LL * C, k + 3LL * C}; }
+static inline BnBwdOut bn_bwd_out(float* dgamma, float* dbeta, float* k, int C, int accumulate) {
+  return {dgamma, dbeta, k + 4LL * C, k + 5LL * C, accumulate};
+}
+struct BnScratch { float* partial; double* acc; };   // partial rows [bn_bwd_partial_rows][2][C] (two sets for a pair), acc: bn_acc_bytes(C)
+// one BatchNorm of a backward: its input Y, coefficients, where the sums go, dY, and whether the sums are wanted at all
+struct BnBwdSide {
+  const void* Y; BnCoef K; BnBwdOut out; void* dY; bool sums;
+  BnCoef apply_coef() const { BnCoef k = K; k.c1 = out.c1; k.c2 = out.c2; return k; }   // the second pass reads c1 / c2 where the combine wrote them
+};
+size_t bn_acc_bytes(int C);   // fp64 slice accumulator: [slices <= max(64, min(256, 131072 / C))][2][C]
 int bn_bwd_partial_rows(long long rows, int C, int dt);
-int launch_bn_bwd_reduce(const void* dZ, const void* Zmask, const unsigned* Zbits, const void* Y, const float* scale,
-                         const float* shift, const float* mean, const float* invstd, float* partials, long long rows, int C,
-                         int dt, hipStream_t s);
-int launch_bn_bwd_finalize_rows(const double* acc, int stat_rows, long long count, int use_batch_stats, float* dgamma,
-                                float* dbeta, float* c1, float* c2, int accumulate, int C, hipStream_t s,
-                                const float* second_sum_scale = nullptr /* EPI_BNRED partials: sum(g (y - mean)) * invstd[c] */);
-int launch_bn_bwd_apply(const void* dZ, const void* Zmask, const unsigned* Zbits, const void* Y, const float* scale,
-                        const float* shift, const float* mean, const float* invstd, const float* c1, const float* c2, void* dY,
-                        long long rows, int C, int dt, hipStream_t s);
-// the two BatchNorms of a downsample block's tail (same masked gradient) in one pass; coefA / coefB = [6][C] {mean, invstd, scale, shift, c1, c2}
-int launch_bn_bwd_apply2(const void* dZ, const unsigned* Zbits, const void* YA, const float* coefA, void* dYA, const void* YB,
-                         const float* coefB, void* dYB, long long rows, int C, int dt, hipStream_t s);
-bool bn_bwd_reduce2_available(int C, int dt);
 int bn_debug_geometry(long long rows, int C, int dt, int* out, int cap);   // r3m_debug_bn_geometry: what the launchers pick, nothing launched
-int launch_bn_bwd_reduce2(const void* dZ, const unsigned* Zbits, const void* YA, const float* coefA, const void* YB, const float* coefB,
-                          float* partials, long long set_stride /* floats between the two partial sets */, long long rows, int C, int dt,
-                          hipStream_t s);
+int launch_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                          const BnCoefOut& o, int C, hipStream_t s);
+// Z = [relu](bn(Y) [+ R]); K2 != null: R is a second raw conv output with its own BatchNorm, Z = [relu](bn(Y) + bn2(R))
+int launch_bn_act_fwd(const void* Y, const BnCoef& K, const void* R, const BnCoef* K2, void* Z, long long rows, int C, int relu,
+                      unsigned* maskbits, int dt, hipStream_t s);
+// The host sequences, one per operation: the engine and the C ABI both run these and launch no backward pass themselves.
+// training coefficients: statistics partials of a forward conv -> stats-reduce -> finalize (+ running-statistics update)
+int bn_train_coeffs(const float* stats, int stats_rows, long long count, const float* gamma, const float* beta, float* running_mean,
+                    float* running_var, float momentum, float eps, const BnCoefOut& o, int C, double* acc, hipStream_t s);
+// partial rows [prow][2][C] -> dgamma / dbeta / c1 / c2. second_sum_scale = invstd for a dgrad epilogue's rows (EPI_BNRED: sum(g (y - mean)))
+int bn_bwd_combine(const float* partial, int prow, long long count, int use_batch_stats, const BnBwdOut& o, const float* second_sum_scale,
+                   int C, double* acc, hipStream_t s);
+// one BatchNorm(+ReLU / residual mask) backward: first pass (or, fused_rows > 0, the EPI_BNRED rows in `fused`) -> combine -> second
+// pass. b.sums / apply: a BatchNorm whose dY nobody reads only forms its sums, one without wanted sums only applies
+int bn_bwd(const void* dZ, const void* Zmask, const unsigned* Zbits, const BnBwdSide& b, const float* fused, int fused_rows, bool apply,
+           long long rows, int C, int use_batch_stats, const BnScratch& w, int dt, hipStream_t s);
+// the two BatchNorms of a downsample block's tail (same masked gradient): one first pass into two partial sets `set_stride` floats
+// apart where the kernel exists (bf16, no fused rows), else one after the other; ONE second pass. The joint launches run as long as
+// either side needs them (the wanted side sees the kernels of a full backward); the other side only loses its combine.
+int bn_bwd_pair(const void* dZ, const unsigned* Zbits, const BnBwdSide& a, const BnBwdSide& b, const float* fused_a, int fused_rows_a,
+                bool apply, long long set_stride, long long rows, int C, int use_batch_stats, const BnScratch& w, int dt, hipStream_t s);
 
-// ---- launchers (bn_pool.hip) ----
+// ---- the pooling family (bn_pool.hip) ----
 // stem tail fused (Z0 / dZ0 never materialised)
-int launch_bn_relu_maxpool_fwd(const void* Y, const float* scale, const float* shift, void* P, unsigned char* amax, int N, int Hi,
-                               int Wi, int C, int dt, hipStream_t s);
+int launch_bn_relu_maxpool_fwd(const void* Y, const BnCoef& K, void* P, unsigned char* amax, int N, int Hi, int Wi, int C, int dt,
+                               hipStream_t s);
 int bn_bwd_pool_partial_rows(int N, int Hi, int Wi, int C);
-int launch_bn_bwd_reduce_pool(const void* dP, const unsigned char* amax, const void* Y, const float* scale, const float* shift,
-                              const float* mean, const float* invstd, float* partials, int N, int Hi, int Wi, int C, int dt,
-                              hipStream_t s);
-int launch_bn_bwd_apply_pool(const void* dP, const unsigned char* amax, const void* Y, const float* scale, const float* shift,
-                             const float* mean, const float* invstd, const float* c1, const float* c2, void* dY, int N, int Hi, int Wi,
-                             int C, int dt, hipStream_t s);
+// the stem's BatchNorm backward with dZ gathered through the max-pool: reduce_pool -> combine -> apply_pool (b.sums / apply as bn_bwd)
+int bn_bwd_pool(const void* dP, const unsigned char* amax, const BnBwdSide& b, bool apply, int N, int Hi, int Wi, int C,
+                int use_batch_stats, const BnScratch& w, int dt, hipStream_t s);
 int launch_maxpool_fwd(const void* Z, void* P, unsigned char* amax, int N, int Hi, int Wi, int C, int dt, hipStream_t s);
 int launch_maxpool_bwd(const void* dP, const unsigned char* amax, void* dZ, int N, int Hi, int Wi, int C, int dt, hipStream_t s);
 int launch_avgpool_fwd(const void* X, float* H, int N, int HW, int C, int dt, hipStream_t s);

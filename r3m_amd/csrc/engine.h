@@ -31,6 +31,19 @@ struct BnRedArgs {
   int rows_out;              // partial rows written (all launches of the dgrad)
 };
 
+// A stride-2 dgrad runs one launch per output parity class (py, px) of the [Hi][Wi] input-gradient image, each over a dense Hg x Wg
+// grid of pixels; a class without pixels (a 1-wide image) has no launch. f(py, px, Hg, Wg) returns non-zero to stop with that value.
+template <class F>
+static inline int for_each_parity_class(int Hi, int Wi, F&& f) {
+  for (int py = 0; py < 2; ++py)
+    for (int px = 0; px < 2; ++px) {
+      const int Hg = (Hi - py + 1) / 2, Wg = (Wi - px + 1) / 2;
+      if (Hg <= 0 || Wg <= 0) continue;
+      if (int e = f(py, px, Hg, Wg)) return e;
+    }
+  return 0;
+}
+
 // ---- convolution launches ----
 // X / W / Y (and dY / Wt / dX / add0 / add1) are fp32 tensors, or bf16 tensors behind float-typed pointers when dt == DT_BF16
 int conv_forward_launch(const float* X, const float* W, float* Y, float* stats, const float* bias, const ConvGeom& c, int flags, int dt,

@@ -13,6 +13,8 @@
 // File order: the layer table and Plan (layout, options, RunState) -> plan_create -> the convolution launch helpers of engine.h ->
 // Ctx (one call's view of plan + buffers) and the tile-counter guard -> forward (stem_forward, block_forward, block_forward_fused,
 // plan_forward) -> backward (BatchNorm / dgrad / wgrad helpers, SideStream, block_backward, stem_backward, plan_backward) -> accessors.
+// The BatchNorm helpers only pick pointers, gradient destinations and work bits: the launch sequences themselves (bn_train_coeffs, bn_bwd,
+// bn_bwd_pair, bn_bwd_pool) are in bn.hip / bn_pool.hip, shared with the C ABI.
 #include "engine.h"
 #include "augment_dev.h"
 #ifndef R3M_BN_PAIR_DEFAULT
@@ -479,33 +481,30 @@ int conv_dgrad_launch(const float* dY, const float* Wt, float* dX, const float* 
     return launch_gather_gemm(g, s);
   }
   // stride 2: one launch per output parity class; class (py,px) only sees taps with (py+pad-kh), (px+pad-kw) even
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      GatherGemmParams q = g;
-      q.Hg = (Hi - py + 1) / 2; q.Wg = (Wi - px + 1) / 2;
-      if (q.Hg <= 0 || q.Wg <= 0) continue;
-      q.os = 2; q.ooy = py; q.oox = px;
-      q.M = N * q.Hg * q.Wg;
-      int t = 0;
-      for (int kh = 0; kh < k; ++kh) {
-        if ((py + pad - kh) & 1) continue;
-        for (int kw = 0; kw < k; ++kw) {
-          if ((px + pad - kw) & 1) continue;
-          q.dy[t] = (signed char)((py + pad - kh) / 2); q.dx[t] = (signed char)((px + pad - kw) / 2);
-          q.wt[t] = (unsigned char)(kh * k + kw); ++t;
-        }
+  return for_each_parity_class(Hi, Wi, [&](int py, int px, int Hg, int Wg) -> int {
+    GatherGemmParams q = g;
+    q.Hg = Hg; q.Wg = Wg;
+    q.os = 2; q.ooy = py; q.oox = px;
+    q.M = N * Hg * Wg;
+    int t = 0;
+    for (int kh = 0; kh < k; ++kh) {
+      if ((py + pad - kh) & 1) continue;
+      for (int kw = 0; kw < k; ++kw) {
+        if ((px + pad - kw) & 1) continue;
+        q.dy[t] = (signed char)((py + pad - kh) / 2); q.dx[t] = (signed char)((px + pad - kw) / 2);
+        q.wt[t] = (unsigned char)(kh * k + kw); ++t;
       }
-      q.ntaps = t;
-      q.simple_rows = 0;
-      R3M_REQUIRE(!(br && t == 0), "dgrad: EPI_BNRED on a parity class without taps (1x1 stride-2) is not supported");
-      if (t == 0 && (flags & EPI_ACCUM) && !(flags & EPI_MASKED_ADD)) continue;  // nothing to add
-      if (br) {                                          // every parity class appends its own partial rows
-        q.stats = br->partial + (long long)br->rows_out * 2 * q.Nc;
-        br->rows_out += bnred_partial_rows(q.M);
-      }
-      if (int e = launch_gather_gemm(q, s)) return e;
     }
-  return 0;
+    q.ntaps = t;
+    q.simple_rows = 0;
+    R3M_REQUIRE(!(br && t == 0), "dgrad: EPI_BNRED on a parity class without taps (1x1 stride-2) is not supported");
+    if (t == 0 && (flags & EPI_ACCUM) && !(flags & EPI_MASKED_ADD)) return 0;  // nothing to add
+    if (br) {                                          // every parity class appends its own partial rows
+      q.stats = br->partial + (long long)br->rows_out * 2 * q.Nc;
+      br->rows_out += bnred_partial_rows(q.M);
+    }
+    return launch_gather_gemm(q, s);
+  });
 }
 
 // The weight gradient of one convolution: fill the parameters, take the plan (wgrad.hip: route, tile, split-K factor — the one
@@ -533,11 +532,6 @@ WgradPlan conv_wgrad_plan(const ConvGeom& c, int dt) { return wgrad_plan(wgrad_p
 size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt) { return (size_t)conv_wgrad_plan(c, dt).split * c.w_elems(); }
 
 // ---------------------------------------------------------------------------------------------------------
-#define TRY(x)              \
-  do {                      \
-    if (int e_ = (x)) return e_; \
-  } while (0)
-
 // add_conv pushes five tensors per convolution: weight, BatchNorm weight, bias, running_mean, running_var
 static size_t tensor_of(const Plan& P, const ConvSpec& L) { return 5 * (size_t)(&L - P.convs.data()); }
 
@@ -563,7 +557,13 @@ struct Ctx {
   int work(const ConvSpec& L) const { return R.work[&L - P.convs.data()]; }
   float* partial() const { return arena + P.partial_off; }
   double* acc() const { return reinterpret_cast<double*>(arena + P.acc_off); }
-  float* coef(const ConvSpec& L, int which) const { return arena + L.coef_off + (long long)which * L.Co; }
+  BnScratch bn_scratch() const { return {partial(), acc()}; }
+  long long rows(const ConvSpec& L) const { return (long long)P.F * L.Ho * L.Wo; }
+  BnCoef coef(const ConvSpec& L) const { return bn_coef_block(arena + L.coef_off, L.Co); }
+  // layer L's part in a BatchNorm backward (bn.hip): sums into dgamma() / dbeta(), c1 / c2 into its coefficient block
+  BnBwdSide bn_side(const ConvSpec& L, float* dY, int work) const {
+    return {arena + L.Y_off, coef(L), bn_bwd_out(dgamma(L), dbeta(L), arena + L.coef_off, L.Co, bn_accumulate(L)), dY, (work & BW_BN_SUMS) != 0};
+  }
   // gradient buffer in role r (0 = D, 1 / 2 = A0 / A1, 3 = B, 4 = C), and the A buffer the next dY goes to
   float* G(int r) const { return arena + P.G_off[R.roles[r]]; }
   float* next_A(int* ai) const { *ai = R.a_next; R.a_next ^= 1; return G(1 + *ai); }
@@ -602,12 +602,10 @@ static const float* fwd_weights(Ctx& c, const ConvSpec& L) {
 static int bn_forward_coeffs(Ctx& c, const ConvSpec& L) {
   const float* gamma = c.params + L.gamma_off;
   const float* beta = c.params + L.beta_off;
-  if (!c.training)
-    return launch_bn_eval_coeffs(gamma, beta, c.bufs + L.rm_off, c.bufs + L.rv_off, 1e-5f, c.coef(L, 0), c.coef(L, 1), c.coef(L, 2),
-                                 c.coef(L, 3), L.Co, c.s);
-  TRY(launch_bn_stats_reduce(c.partial(), L.stats_rows, L.Co, c.acc(), c.s));
-  return launch_bn_finalize_rows(c.acc(), L.stats_rows, (long long)c.P.F * L.Ho * L.Wo, gamma, beta, c.bufs + L.rm_off, c.bufs + L.rv_off,
-                                 0.1f, 1e-5f, c.coef(L, 0), c.coef(L, 1), c.coef(L, 2), c.coef(L, 3), L.Co, c.s);
+  const BnCoefOut o = bn_coef_out(c.arena + L.coef_off, L.Co);
+  if (!c.training) return launch_bn_eval_coeffs(gamma, beta, c.bufs + L.rm_off, c.bufs + L.rv_off, 1e-5f, o, L.Co, c.s);
+  return bn_train_coeffs(c.partial(), L.stats_rows, c.rows(L), gamma, beta, c.bufs + L.rm_off, c.bufs + L.rv_off, 0.1f, 1e-5f, o, L.Co, c.acc(),
+                         c.s);
 }
 
 // conv -> BatchNorm coefficients (the raw output stays in Y)
@@ -636,8 +634,8 @@ static int stem_forward(Ctx& c, const float* x_nchw, const FrameSource* crop) {
   TRY(stem.forward(xn, c.params + L0.w_off, Y, c.training ? c.partial() : nullptr));
   TRY(bn_forward_coeffs(c, L0));
   // BatchNorm + ReLU + MaxPool in one pass over Y0
-  return launch_bn_relu_maxpool_fwd(Y, c.coef(L0, 2), c.coef(L0, 3), c.arena + P.P0_off, reinterpret_cast<unsigned char*>(c.arena + P.amax_off),
-                                    F, P.H1, P.W1, 64, dt, c.s);
+  return launch_bn_relu_maxpool_fwd(Y, c.coef(L0), c.arena + P.P0_off, reinterpret_cast<unsigned char*>(c.arena + P.amax_off), F, P.H1, P.W1, 64,
+                                    dt, c.s);
 }
 
 // One residual block, unfused: every conv leaves its raw output and coefficients, bn_act_fwd makes the activations and the block
@@ -649,20 +647,18 @@ static int block_forward(Ctx& c, const BlockSpec& B, const float* Xin, unsigned*
     const ConvSpec& L = P.convs[B.conv[j]];
     TRY(conv_bn(c, L, cur));
     if (j < B.nconv - 1) {
-      TRY(launch_bn_act_fwd(c.arena + L.Y_off, c.coef(L, 2), c.coef(L, 3), nullptr, nullptr, nullptr, c.arena + L.Z_off,
-                            (long long)P.F * L.Ho * L.Wo, L.Co, 1, nullptr, c.dt, c.s));
+      TRY(launch_bn_act_fwd(c.arena + L.Y_off, c.coef(L), nullptr, nullptr, c.arena + L.Z_off, c.rows(L), L.Co, 1, nullptr, c.dt, c.s));
       cur = c.arena + L.Z_off;
     }
   }
   const ConvSpec& LL = P.convs[B.conv[B.nconv - 1]];
   const long long rows = (long long)P.F * B.Ho * B.Wo;
   if (B.ds < 0)
-    return launch_bn_act_fwd(c.arena + LL.Y_off, c.coef(LL, 2), c.coef(LL, 3), Xin, nullptr, nullptr, c.arena + B.out_off, rows, B.Co, 1,
-                             mask, c.dt, c.s);
+    return launch_bn_act_fwd(c.arena + LL.Y_off, c.coef(LL), Xin, nullptr, c.arena + B.out_off, rows, B.Co, 1, mask, c.dt, c.s);
   const ConvSpec& Ld = P.convs[B.ds];
   TRY(conv_bn(c, Ld, Xin));
-  return launch_bn_act_fwd(c.arena + LL.Y_off, c.coef(LL, 2), c.coef(LL, 3), c.arena + Ld.Y_off, c.coef(Ld, 2), c.coef(Ld, 3),
-                           c.arena + B.out_off, rows, B.Co, 1, mask, c.dt, c.s);
+  const BnCoef Kd = c.coef(Ld);
+  return launch_bn_act_fwd(c.arena + LL.Y_off, c.coef(LL), c.arena + Ld.Y_off, &Kd, c.arena + B.out_off, rows, B.Co, 1, mask, c.dt, c.s);
 }
 
 // Inference: every convolution of the block stores its activated output itself — inner convs relu(bn(conv)), the downsample conv
@@ -680,7 +676,7 @@ static bool block_fusable(Ctx& c, const BlockSpec& B) {
 static int conv_bn_fused(Ctx& c, const ConvSpec& L, const float* X, float* out, int flags) {
   TRY(bn_forward_coeffs(c, L));
   TileCounters tc(c, TileCounters::FORWARD, L);
-  return conv_forward_launch_affine(X, fwd_weights(c, L), out, c.coef(L, 2), c.coef(L, 3), L.geom(c.P.F), flags, c.dt, c.s);
+  return conv_forward_launch_affine(X, fwd_weights(c, L), out, c.coef(L).scale, c.coef(L).shift, L.geom(c.P.F), flags, c.dt, c.s);
 }
 // *out: where the block's output is (the block input, or the downsample conv's Y)
 static int block_forward_fused(Ctx& c, const BlockSpec& B, float* Xin, float** out) {
@@ -740,56 +736,23 @@ int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const fl
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------
-// partial rows -> the parameter gradients and the two per-channel coefficients c1 / c2 the second pass needs.
-// from_dgrad: the partials are a dgrad epilogue's (EPI_BNRED): sum(g) and sum(g (y - mean)) per 64 rows
-static int bn_backward_combine(Ctx& c, const ConvSpec& L, const float* partial, int prow, bool from_dgrad = false) {
-  TRY(launch_bn_stats_reduce(partial, prow, L.Co, c.acc(), c.s));
-  return launch_bn_bwd_finalize_rows(c.acc(), prow, (long long)c.P.F * L.Ho * L.Wo, c.R.last_training, c.dgamma(L), c.dbeta(L), c.coef(L, 4),
-                                     c.coef(L, 5), c.bn_accumulate(L), L.Co, c.s, from_dgrad ? c.coef(L, 1) : nullptr);
-}
-// BatchNorm(+ReLU / residual mask) backward of layer L: dZ -> dY, parameter gradients into the flat gradient buffer
+// BatchNorm(+ReLU / residual mask) backward of layer L (bn.hip, bn_bwd): dZ -> dY, parameter gradients into the flat gradient buffer.
 // fused_rows > 0: the dgrad that produced dZ already wrote this BatchNorm's backward partials (EPI_BNRED) into the partial buffer:
 // the stand-alone first pass is skipped
-static int bn_backward_sums(Ctx& c, const ConvSpec& L, const float* dZ, const unsigned* Zbits, int fused_rows) {
-  if (fused_rows) return bn_backward_combine(c, L, c.partial(), fused_rows, true);
-  const long long rows = (long long)c.P.F * L.Ho * L.Wo;
-  TRY(launch_bn_bwd_reduce(dZ, nullptr, Zbits, c.arena + L.Y_off, c.coef(L, 2), c.coef(L, 3), c.coef(L, 0), c.coef(L, 1), c.partial(), rows,
-                           L.Co, c.dt, c.s));
-  return bn_backward_combine(c, L, c.partial(), bn_bwd_partial_rows(rows, L.Co, c.dt));
-}
 // work: BW_BN_SUMS / BW_BN_APPLY of this layer (a BatchNorm whose dY nobody reads only forms its parameter sums)
 static int bn_backward(Ctx& c, const ConvSpec& L, const float* dZ, const unsigned* Zbits, float* dY, int fused_rows, int work) {
-  if (work & BW_BN_SUMS) TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
-  if (!(work & BW_BN_APPLY)) return 0;
-  const long long rows = (long long)c.P.F * L.Ho * L.Wo;
-  return launch_bn_bwd_apply(dZ, nullptr, Zbits, c.arena + L.Y_off, c.coef(L, 2), c.coef(L, 3), c.coef(L, 0), c.coef(L, 1), c.coef(L, 4),
-                             c.coef(L, 5), dY, rows, L.Co, c.dt, c.s);
+  return bn_bwd(dZ, nullptr, Zbits, c.bn_side(L, dY, work), c.partial(), fused_rows, (work & BW_BN_APPLY) != 0, c.rows(L), L.Co,
+                c.R.last_training, c.bn_scratch(), c.dt, c.s);
 }
 // The two BatchNorms that feed a downsample block's add + ReLU (its last convolution's and the downsample convolution's) see the SAME
-// masked output gradient: their second passes run as ONE launch that reads dOut and the mask bits once (bn.hip, bn_bwd_apply_kernel with NB = 2).
-// The sums of the two are taken one after the other (they share the partial / accumulator scratch).
-// work / work_d: the BW_* bits of L / Ld. The joint launches run as long as either side needs them, so that the side that is wanted
-// sees the kernels and inputs of a full backward (bit-identical gradients); only the other side's combine is dropped, and its dY
-// (formed from stale c1 / c2) is never read.
+// masked output gradient: bn_bwd_pair (bn.hip) runs their second passes as ONE launch that reads dOut and the mask bits once.
+// work / work_d: the BW_* bits of L / Ld; the joint launches run as long as either side needs them.
 static int bn_backward_pair(Ctx& c, const ConvSpec& L, const ConvSpec& Ld, const float* dZ, const unsigned* Zbits, float* dY, float* dYd,
                             int fused_rows, int work, int work_d) {
   R3M_REQUIRE(L.Co == Ld.Co && L.Ho == Ld.Ho && L.Wo == Ld.Wo && Zbits, "bn_backward_pair: the two BatchNorms must have one shape and mask bits");
-  const long long rows = (long long)c.P.F * L.Ho * L.Wo;
-  if (!fused_rows && bn_bwd_reduce2_available(L.Co, c.dt)) {
-    // both first passes are stand-alone (bf16 plans): one launch, two partial sets, then the two combines one after the other
-    const int prow = bn_bwd_partial_rows(rows, L.Co, c.dt);
-    const long long set = (long long)prow * 2 * L.Co;
-    TRY(launch_bn_bwd_reduce2(dZ, Zbits, c.arena + L.Y_off, c.arena + L.coef_off, c.arena + Ld.Y_off, c.arena + Ld.coef_off, c.partial(), set,
-                              rows, L.Co, c.dt, c.s));
-    if (work & BW_BN_SUMS) TRY(bn_backward_combine(c, L, c.partial(), prow));
-    if (work_d & BW_BN_SUMS) TRY(bn_backward_combine(c, Ld, c.partial() + set, prow));
-  } else {
-    if (work & BW_BN_SUMS) TRY(bn_backward_sums(c, L, dZ, Zbits, fused_rows));
-    if (work_d & BW_BN_SUMS) TRY(bn_backward_sums(c, Ld, dZ, Zbits, 0));
-  }
-  if (!((work | work_d) & BW_BN_APPLY)) return 0;
-  return launch_bn_bwd_apply2(dZ, Zbits, c.arena + L.Y_off, c.arena + L.coef_off, dY, c.arena + Ld.Y_off, c.arena + Ld.coef_off, dYd, rows,
-                              L.Co, c.dt, c.s);
+  const long long set = (long long)bn_bwd_partial_rows(c.rows(L), L.Co, c.dt) * 2 * L.Co;   // the second partial set right behind the first
+  return bn_bwd_pair(dZ, Zbits, c.bn_side(L, dY, work), c.bn_side(Ld, dYd, work_d), c.partial(), fused_rows, ((work | work_d) & BW_BN_APPLY) != 0,
+                     set, c.rows(L), L.Co, c.R.last_training, c.bn_scratch(), c.dt, c.s);
 }
 
 static int wgrad(Ctx& c, const ConvSpec& L, const float* X, const float* dY) {
@@ -808,7 +771,8 @@ static int dgrad(Ctx& c, const ConvSpec& L, const float* dY, float* dX, int flag
   // 1x1 stride-2 dgrads leave three of four parity classes without taps (plain zero / no-op launches): not fused
   const bool fuse = bn_of && fused_rows_out && c.P.fuse_bnred && !(L.stride == 2 && L.k == 1);
   if (!fuse) return conv_dgrad_launch(dY, Wt, dX, add0, nullptr, addbits, L.geom(c.P.F), flags, c.dt, c.s);
-  BnRedArgs br{c.arena + bn_of->Y_off, bn_bits, c.coef(*bn_of, 2), c.coef(*bn_of, 3), c.coef(*bn_of, 0), c.partial(), 0};
+  const BnCoef K = c.coef(*bn_of);
+  BnRedArgs br{c.arena + bn_of->Y_off, bn_bits, K.scale, K.shift, K.mean, c.partial(), 0};
   TRY(conv_dgrad_launch(dY, Wt, dX, add0, nullptr, addbits, L.geom(c.P.F), flags, c.dt, c.s, &br));
   *fused_rows_out = br.rows_out;
   return 0;
@@ -996,17 +960,9 @@ static int stem_backward(Ctx& c, float* dx, int dx_accumulate, int work) {
   const int F = P.F, dt = c.dt;
   const ConvSpec& L0 = P.convs[0];
   float* Gc = c.G(4);
-  const float* Y = c.arena + L0.Y_off;
   // MaxPool backward gathered inside both BatchNorm-backward passes (no dZ0 tensor)
   const unsigned char* am = reinterpret_cast<const unsigned char*>(c.arena + P.amax_off);
-  if (work & BW_BN_SUMS) {
-    TRY(launch_bn_bwd_reduce_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.partial(), F, P.H1, P.W1, 64, dt,
-                                  c.s));
-    TRY(bn_backward_combine(c, L0, c.partial(), bn_bwd_pool_partial_rows(F, P.H1, P.W1, 64)));
-  }
-  if (work & BW_BN_APPLY)
-    TRY(launch_bn_bwd_apply_pool(c.G(0), am, Y, c.coef(L0, 2), c.coef(L0, 3), c.coef(L0, 0), c.coef(L0, 1), c.coef(L0, 4), c.coef(L0, 5), Gc, F,
-                                 P.H1, P.W1, 64, dt, c.s));
+  TRY(bn_bwd_pool(c.G(0), am, c.bn_side(L0, Gc, work), (work & BW_BN_APPLY) != 0, F, P.H1, P.W1, 64, c.R.last_training, c.bn_scratch(), dt, c.s));
   TRY(c.R.side.join());   // the stem wgrad shares the split-K scratch with the side stream's wgrads
   const Stem stem(P, dt, c.R.stem_gen != 0, c.s);
   if (work & BW_WGRAD) TRY(stem.wgrad(c.arena + P.col_off, Gc, c.grads + L0.w_off, c.arena + P.wgp_off, c.accumulate));
