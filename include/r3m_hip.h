@@ -88,6 +88,20 @@ int r3m_debug_wgrad_route(int N, int H, int W, int Ci, int Co, int k, int stride
      13    the cap on the slice count for this C (256 at C = 64 ... 64 at C = 2048)
    Returns the number of ints written (14), -1 on error (cap < 14, bad rows / C / dtype). */
 int r3m_debug_bn_geometry(long long rows, int C, int dtype, int* out, int cap);
+/* Diagnostic, runs without a GPU: the launch geometry of the fused stem tail of csrc/bn_pool.hip (r3m_bn_relu_maxpool_fwd_dt,
+   r3m_bn_maxpool_bwd_dt) for y [N, Hi, Wi, C] of `dtype` -- the struct the launchers themselves launch from, nothing is launched. out[0..17]:
+     0-1    pooled extents Ho, Wo
+     2-6    forward: 1 = the bf16 row-walking kernel (C a power of two <= 2048), 0 = the one-output-per-thread kernel; segments of 8 output
+            rows per frame (0 for the latter); blocks; threads per block; items per block (Wo * C / 8 for the row-walking kernel, whose
+            threads loop over them; 256 for the other)
+     7-14   backward reduce (first pass): quad rows per block rq; blocks = partial rows; threads; items per quad row (Wo * C / out[17]);
+            threads per channel vector; the groups of the second LDS stage (min(out[11], 8)); dynamic LDS bytes; the partial rows the
+            workspace of r3m_bn_workspace_bytes(N * Hi * Wi, C) holds (out[8] <= out[14])
+     15-16  backward apply (second pass): blocks, threads
+     17     elements per lane (4 fp32 | 8 bf16)
+   The backward takes C a power of two in 8..1024; for any other C out[7..16] are 0 (r3m_bn_maxpool_bwd_dt refuses it).
+   Returns the number of ints written (18), -1 on error (cap < 18, unknown dtype, N / Hi / Wi < 1, C not a positive multiple of 8). */
+int r3m_debug_pool_geometry(int N, int Hi, int Wi, int C, int dtype, int* out, int cap);
 void r3m_profile_enable(int on);
 /* which kernel classes are bracketed while profiling is on: bit k = class k (0 conv fwd/dgrad 128-wide, 1 64-wide, 2 / 3 the weight
    gradients); default all. Each bracket costs the stream two event records. Returns the old mask. */

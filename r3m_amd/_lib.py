@@ -33,6 +33,7 @@ SIGNATURES = {
     "r3m_debug_wgrad_route": (c_i, [c_i] * 9 + [C.POINTER(c_i), c_i]),
     "r3m_debug_conv_fuses_affine": (c_i, [c_i] * 10),
     "r3m_debug_bn_geometry": (c_i, [c_ll, c_i, c_i, C.POINTER(c_i), c_i]),
+    "r3m_debug_pool_geometry": (c_i, [c_i] * 5 + [C.POINTER(c_i), c_i]),
     "r3m_profile_enable": (None, [c_i]),
     "r3m_profile_classes": (C.c_uint, [C.c_uint]),
     "r3m_profile_collect": (c_i, [C.POINTER(c_d), C.POINTER(c_ll), C.POINTER(c_d)]),

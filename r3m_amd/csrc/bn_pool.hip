@@ -252,21 +252,77 @@ static inline int ilog2_exact(int v) { int l = 0; while ((1 << l) < v) ++l; retu
 // threads of a block that owns Wo x CV (pixel, channel-vector) items: all of them when they fit, else 1024 (a multiple of CV <= 256)
 static inline int pool_row_threads(int items) { return items >= 1024 ? 1024 : (items + 63) / 64 * 64; }
 
+// Quad rows per block of the pooled reduce: 8, or more when that would give more partial rows than the plain fp32 reduce of the
+// same tensor writes (the size every BatchNorm workspace is laid out for).
+static inline void pool_reduce_geometry(int N, int Hi, int Wi, int C, int* rq, int* nblk, int* cap_out = nullptr) {
+  const int Ho = (Hi + 2 - 3) / 2 + 1;
+  const int quad_rows = N * Ho;
+  const int cap = bn_bwd_partial_rows((long long)N * Hi * Wi, C, DT_F32);
+  int r = ceil_div(quad_rows, cap);
+  if (r < 8) r = 8;
+  *rq = r;
+  *nblk = ceil_div(quad_rows, r);
+  if (cap_out) *cap_out = cap;
+}
+
+// Every launch figure of the fused stem tail at one shape. The three launchers below take their grids, blocks and LDS sizes from
+// here and pool_debug_geometry (r3m_debug_pool_geometry) reports the same struct, so the two cannot drift.
+struct PoolGeometry {
+  int Ho, Wo, V, CV;                                      // pooled extents; elements per lane (4 fp32 | 8 bf16); channel vectors C / V
+  // forward: the bf16 row-walking kernel (fwd_rows = 1: one block per (frame, segment of POOL_SEG output rows), fwd_items = Wo x CV
+  // items per block) or the one-output-per-thread kernel (fwd_rows = 0: no segments, 256 outputs per block of 256 threads)
+  int fwd_rows, fwd_segs, fwd_blocks, fwd_threads, fwd_items;
+  long long fwd_total;                                    // (pixel, channel-vector) outputs of the whole tensor
+  // backward (bwd_ok = 0: the backward refuses this C and the fields below are 0). reduce: blocks = partial rows, per_cv = threads
+  // of a block that share one channel vector, G = the groups the kernel's second LDS stage adds them in (min(per_cv, 8))
+  int bwd_ok, rq, red_blocks, red_threads, red_items, per_cv, G, red_lds, red_cap;
+  int app_blocks, app_threads;
+};
+
+static PoolGeometry pool_geometry(int N, int Hi, int Wi, int C, int dt) {
+  PoolGeometry g = {};
+  g.Ho = (Hi + 2 - 3) / 2 + 1;
+  g.Wo = (Wi + 2 - 3) / 2 + 1;
+  g.V = dt == DT_BF16 ? 4 * PoolVec<bf16_t>::V4 : 4 * PoolVec<float>::V4;
+  g.CV = C / g.V;
+  g.fwd_total = (long long)N * g.Ho * g.Wo * g.CV;
+  g.fwd_rows = dt == DT_BF16 && is_pow2(C) && C <= 2048;
+  if (g.fwd_rows) {
+    g.fwd_segs = ceil_div(g.Ho, POOL_SEG);
+    g.fwd_blocks = N * g.fwd_segs;
+    g.fwd_items = g.Wo * g.CV;
+    g.fwd_threads = pool_row_threads(g.fwd_items);
+  } else {
+    g.fwd_blocks = ceil_div(g.fwd_total, 256);
+    g.fwd_items = 256;
+    g.fwd_threads = 256;
+  }
+  g.bwd_ok = is_pow2(C) && C >= 8 && C <= 1024;
+  if (g.bwd_ok) {
+    pool_reduce_geometry(N, Hi, Wi, C, &g.rq, &g.red_blocks, &g.red_cap);
+    g.red_items = g.Wo * g.CV;
+    g.red_threads = pool_row_threads(g.red_items);
+    g.per_cv = g.red_threads / g.CV;                      // bn_bwd_reduce_pool_kernel: nt >> cv_log2
+    g.G = g.per_cv < 8 ? g.per_cv : 8;
+    g.red_lds = (int)((size_t)2 * (g.V / 4) * g.red_threads * sizeof(f32x4));
+    g.app_blocks = N * g.Ho;
+    g.app_threads = pool_row_threads(g.Wo * g.CV);
+  }
+  return g;
+}
+
 int launch_bn_relu_maxpool_fwd(const void* Y, const BnCoef& K, void* P, unsigned char* amax, int N, int Hi, int Wi, int C, int dt,
                                hipStream_t s) {
-  const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
   R3M_REQUIRE(C % 8 == 0, "bn_relu_maxpool_fwd: C=%d must be a multiple of 8", C);
-  if (dt == DT_BF16 && is_pow2(C) && C <= 2048) {
-    const int CV = C / 8, segs = ceil_div(Ho, POOL_SEG);
-    hipLaunchKernelGGL(bn_relu_maxpool_fwd16_kernel, dim3(N * segs), dim3(pool_row_threads(Wo * CV)), 0, s,
-                       static_cast<const bf16_t*>(Y), K.scale, K.shift, static_cast<bf16_t*>(P), amax, Hi, Wi, Ho, Wo, CV, ilog2_exact(CV), segs);
+  const PoolGeometry g = pool_geometry(N, Hi, Wi, C, dt);
+  if (g.fwd_rows) {
+    hipLaunchKernelGGL(bn_relu_maxpool_fwd16_kernel, dim3(g.fwd_blocks), dim3(g.fwd_threads), 0, s, static_cast<const bf16_t*>(Y), K.scale,
+                       K.shift, static_cast<bf16_t*>(P), amax, Hi, Wi, g.Ho, g.Wo, g.CV, ilog2_exact(g.CV), g.fwd_segs);
     return check_launch("bn_relu_maxpool_fwd16");
   }
   DT_DISPATCH(dt, "bn_relu_maxpool_fwd", {
-    constexpr int V = 4 * PoolVec<T>::V4;
-    const long long total = (long long)N * Ho * Wo * (C / V);
-    hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<T>), dim3(ceil_div(total, 256)), dim3(256), 0, s, static_cast<const T*>(Y), K.scale,
-                       K.shift, static_cast<T*>(P), amax, total, Hi, Wi, Ho, Wo, C / V);
+    hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<T>), dim3(g.fwd_blocks), dim3(g.fwd_threads), 0, s, static_cast<const T*>(Y), K.scale,
+                       K.shift, static_cast<T*>(P), amax, g.fwd_total, Hi, Wi, g.Ho, g.Wo, g.CV);
   });
   return check_launch("bn_relu_maxpool_fwd");
 }
@@ -446,18 +502,6 @@ __global__ __launch_bounds__(1024) void bn_bwd_apply_pool_kernel(const T* __rest
   }
 }
 
-// Quad rows per block of the pooled reduce: 8, or more when that would give more partial rows than the plain fp32 reduce of the
-// same tensor writes (the size every BatchNorm workspace is laid out for).
-static inline void pool_reduce_geometry(int N, int Hi, int Wi, int C, int* rq, int* nblk) {
-  const int Ho = (Hi + 2 - 3) / 2 + 1;
-  const int quad_rows = N * Ho;
-  const int cap = bn_bwd_partial_rows((long long)N * Hi * Wi, C, DT_F32);
-  int r = ceil_div(quad_rows, cap);
-  if (r < 8) r = 8;
-  *rq = r;
-  *nblk = ceil_div(quad_rows, r);
-}
-
 // rows of the partial buffer the pooled reduce writes
 int bn_bwd_pool_partial_rows(int N, int Hi, int Wi, int C) {
   int rq, nblk;
@@ -467,32 +511,39 @@ int bn_bwd_pool_partial_rows(int N, int Hi, int Wi, int C) {
 
 static int launch_bn_bwd_reduce_pool(const void* dP, const unsigned char* amax, const void* Y, const BnCoef& K, float* partials, int N,
                                      int Hi, int Wi, int C, int dt, hipStream_t s) {
-  R3M_REQUIRE(is_pow2(C) && C >= 8 && C <= 1024, "bn_bwd_reduce_pool: C=%d must be a power of two in [8, 1024]", C);
-  const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-  int rq, nblk;
-  pool_reduce_geometry(N, Hi, Wi, C, &rq, &nblk);
+  const PoolGeometry g = pool_geometry(N, Hi, Wi, C, dt);
+  R3M_REQUIRE(g.bwd_ok, "bn_bwd_reduce_pool: C=%d must be a power of two in [8, 1024]", C);
   DT_DISPATCH(dt, "bn_bwd_reduce_pool", {
-    constexpr int V4 = PoolVec<T>::V4, V = 4 * V4;
-    const int CV = C / V, nt = pool_row_threads(Wo * CV);
-    hipLaunchKernelGGL((bn_bwd_reduce_pool_kernel<T>), dim3(nblk), dim3(nt), (size_t)2 * V4 * nt * sizeof(f32x4), s,
-                       static_cast<const T*>(dP), amax, static_cast<const T*>(Y), K.scale, K.shift, K.mean, K.invstd, partials, N * Ho, rq, C,
-                       CV, ilog2_exact(CV), Hi, Wi, Ho, Wo);
+    hipLaunchKernelGGL((bn_bwd_reduce_pool_kernel<T>), dim3(g.red_blocks), dim3(g.red_threads), (size_t)g.red_lds, s,
+                       static_cast<const T*>(dP), amax, static_cast<const T*>(Y), K.scale, K.shift, K.mean, K.invstd, partials, N * g.Ho, g.rq,
+                       C, g.CV, ilog2_exact(g.CV), Hi, Wi, g.Ho, g.Wo);
   });
   return check_launch("bn_bwd_reduce_pool");
 }
 
 static int launch_bn_bwd_apply_pool(const void* dP, const unsigned char* amax, const void* Y, const BnCoef& K, void* dY, int N, int Hi,
                                     int Wi, int C, int dt, hipStream_t s) {
-  const int Ho = (Hi + 2 - 3) / 2 + 1, Wo = (Wi + 2 - 3) / 2 + 1;
-  R3M_REQUIRE(is_pow2(C) && C >= 8 && C <= 1024, "bn_bwd_apply_pool: C=%d must be a power of two in [8, 1024]", C);
+  const PoolGeometry g = pool_geometry(N, Hi, Wi, C, dt);
+  R3M_REQUIRE(g.bwd_ok, "bn_bwd_apply_pool: C=%d must be a power of two in [8, 1024]", C);
   DT_DISPATCH(dt, "bn_bwd_apply_pool", {
-    constexpr int V = 4 * PoolVec<T>::V4;
-    const int CV = C / V;
-    hipLaunchKernelGGL((bn_bwd_apply_pool_kernel<T>), dim3(N * Ho), dim3(pool_row_threads(Wo * CV)), 0, s, static_cast<const T*>(dP),
-                       amax, static_cast<const T*>(Y), K.scale, K.shift, K.mean, K.invstd, K.c1, K.c2, static_cast<T*>(dY), CV,
-                       ilog2_exact(CV), Hi, Wi, Ho, Wo);
+    hipLaunchKernelGGL((bn_bwd_apply_pool_kernel<T>), dim3(g.app_blocks), dim3(g.app_threads), 0, s, static_cast<const T*>(dP), amax,
+                       static_cast<const T*>(Y), K.scale, K.shift, K.mean, K.invstd, K.c1, K.c2, static_cast<T*>(dY), g.CV, ilog2_exact(g.CV),
+                       Hi, Wi, g.Ho, g.Wo);
   });
   return check_launch("bn_bwd_apply_pool");
+}
+
+// What the launchers above pick for [N, Hi, Wi, C] of dtype dt, without launching anything (r3m_debug_pool_geometry; the index names
+// are in include/r3m_hip.h)
+int pool_debug_geometry(int N, int Hi, int Wi, int C, int dt, int* out, int cap) {
+  R3M_REQUIRE(out && cap >= 18, "debug_pool_geometry: the output buffer needs 18 ints");
+  R3M_REQUIRE(dt == DT_F32 || dt == DT_BF16, "debug_pool_geometry: unknown dtype %d", dt);
+  R3M_REQUIRE(N >= 1 && Hi >= 1 && Wi >= 1 && C >= 8 && C % 8 == 0, "debug_pool_geometry: N=%d Hi=%d Wi=%d C=%d", N, Hi, Wi, C);
+  const PoolGeometry g = pool_geometry(N, Hi, Wi, C, dt);
+  const int v[18] = {g.Ho, g.Wo, g.fwd_rows, g.fwd_segs, g.fwd_blocks, g.fwd_threads, g.fwd_items, g.rq, g.red_blocks, g.red_threads,
+                     g.red_items, g.per_cv, g.G, g.red_lds, g.red_cap, g.app_blocks, g.app_threads, g.V};
+  for (int i = 0; i < 18; ++i) out[i] = v[i];
+  return 0;
 }
 
 int bn_bwd_pool(const void* dP, const unsigned char* amax, const BnBwdSide& b, bool apply, int N, int Hi, int Wi, int C,

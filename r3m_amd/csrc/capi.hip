@@ -564,6 +564,9 @@ int r3m_bn_bwd_from_partials_dt(const void* dz, const unsigned* zbits, const voi
                 use_batch_stats, w, dtype, S(stream));
 }
 int r3m_debug_bn_geometry(long long rows, int C, int dtype, int* out, int cap) { return bn_debug_geometry(rows, C, dtype, out, cap) ? -1 : 14; }
+int r3m_debug_pool_geometry(int N, int Hi, int Wi, int C, int dtype, int* out, int cap) {
+  return pool_debug_geometry(N, Hi, Wi, C, dtype, out, cap) ? -1 : 18;
+}
 // stem tail fused: BatchNorm + ReLU + MaxPool(3,2,1) forward, and its backward (MaxPool gather inside both BN-backward passes)
 int r3m_bn_relu_maxpool_fwd_dt(const void* y, const float* coef, void* p, unsigned char* am, int N, int Hi, int Wi, int C, int dtype,
                                r3m_stream_t stream) {

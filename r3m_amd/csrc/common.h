@@ -279,6 +279,7 @@ int bn_bwd_pair(const void* dZ, const unsigned* Zbits, const BnBwdSide& a, const
 int launch_bn_relu_maxpool_fwd(const void* Y, const BnCoef& K, void* P, unsigned char* amax, int N, int Hi, int Wi, int C, int dt,
                                hipStream_t s);
 int bn_bwd_pool_partial_rows(int N, int Hi, int Wi, int C);
+int pool_debug_geometry(int N, int Hi, int Wi, int C, int dt, int* out, int cap);   // r3m_debug_pool_geometry: what the launchers pick, nothing launched
 // the stem's BatchNorm backward with dZ gathered through the max-pool: reduce_pool -> combine -> apply_pool (b.sums / apply as bn_bwd)
 int bn_bwd_pool(const void* dP, const unsigned char* amax, const BnBwdSide& b, bool apply, int N, int Hi, int Wi, int C,
                 int use_batch_stats, const BnScratch& w, int dt, hipStream_t s);

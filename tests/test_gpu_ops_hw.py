@@ -24,7 +24,7 @@ import torch.nn.functional as F
 
 from r3m_amd import _lib
 from route_sig import plan_convs
-from util import DEV, EPS_BF16, check_conv_bf16, check_conv_fp32, check_dgrad_bnred, nchw, nhwc, q_bf16, rel_err, rnd
+from util import DEV, EPS_BF16, check_conv_bf16, check_conv_fp32, check_dgrad_bnred, check_stem_tail_fused_vs_torch, nchw, nhwc, q_bf16, rel_err, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -256,58 +256,7 @@ def test_stem_tail_fused_vs_torch_hw(hip, H, W, dtype):
     float64 with the same coefficients. The inputs are kept away from the ReLU kink, and a max-pool window never holds two different
     positive values that a rounding could reorder or that are equal: y is drawn from a grid of well separated levels, distinct inside
     every 3 x 3 window (the zeros behind the ReLU still tie), so the float64 argmax is the only argmax the kernel can pick."""
-    N, C = 2, 64
-    dt = 0 if dtype == "fp32" else 1
-    tdt = torch.float32 if dt == 0 else torch.bfloat16
-    rows = N * H * W
-    # level index = 7 * (a per-channel permutation of the pixel's place in a 3 x 3 lattice) + a random 0..6: distinct inside any window
-    g9 = torch.Generator().manual_seed(60)
-    perm = torch.stack([torch.randperm(9, generator=g9) for _ in range(C)], 1)                       # [9][C]
-    place = ((torch.arange(H) % 3) * 3).view(H, 1) + (torch.arange(W) % 3).view(1, W)               # [H][W]
-    idx = perm[place.reshape(-1)].view(1, H, W, C) * 7 + torch.floor(rnd((N, H, W, C), 61, 0.0, 7.0)).long().clamp(0, 6)
-    y = ((idx - 31).float() / 4.0 + 0.125).reshape(rows, C)                                          # levels k/4 + 1/8, exact in bf16
-    gam = rnd((C,), 62, 0.5, 1.5)
-    m, v = y.double().mean(0), y.double().var(0, unbiased=False)
-    inv = 1.0 / torch.sqrt(v + 1e-5)
-    # shift each channel's zero crossing to the middle between two levels: |scale * y + shift| >= scale / 8
-    sc = (gam.double() * inv)
-    sh = -sc * (torch.round(m * 4.0) / 4.0)
-    coef = torch.stack([m, inv, sc, sh]).float().contiguous()
-    c = coef.double()
-    yr = y.double().requires_grad_(True)
-    t = yr * c[2] + c[3]
-    assert float(t.detach().abs().min()) > 1e-3
-    zr = torch.relu(t).reshape(N, H, W, C).permute(0, 3, 1, 2)
-    p_ref = F.max_pool2d(zr, 3, 2, 1)
-    Ho, Wo = p_ref.shape[2], p_ref.shape[3]
-    dp = rnd((N, Ho, Wo, C), 64)
-    dp = dp if dt == 0 else q_bf16(dp)
-    p_ref.backward(nchw(dp).double())
-    g = yr.grad / c[2]                          # dz routed by the pool and masked by the ReLU, as the kernel's first pass sees it
-    if dt == 1:                                 # a pixel that is the maximum of up to four windows: the kernel rounds the sum of their
-        g = q_bf16(g.float()).double()          # pooled gradients to bf16, as the unfused sequence stores dz (csrc/bn_pool.hip pool_quad)
-    yhat = (y.double() - c[0]) * c[1]
-    db_ref, dg_ref = g.sum(0), (g * yhat).sum(0)
-    dy_ref = c[2] * (g - g.mean(0) - yhat * (g * yhat).mean(0))
-
-    yd, coefd = y.to(DEV).to(tdt), coef.to(DEV)
-    pd = torch.full((N, Ho, Wo, C), float("nan"), dtype=tdt, device=DEV)
-    am = torch.full((N, Ho, Wo, C), 255, dtype=torch.uint8, device=DEV)
-    assert hip.r3m_bn_relu_maxpool_fwd_dt(yd.data_ptr(), coefd.data_ptr(), pd.data_ptr(), am.data_ptr(), N, H, W, C, dt, st()) == 0, \
-        hip.r3m_last_error()
-    e = rel_err(nchw(pd.float().cpu()).numpy(), p_ref.detach().numpy())[0]
-    assert e < (1e-5 if dt == 0 else EPS_BF16), f"fused BatchNorm + ReLU + max-pool forward {e}"
-    dpd = dp.to(DEV).to(tdt)
-    wsb = hip.r3m_bn_workspace_bytes(rows, C)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-    dg, db = torch.full((C,), float("nan"), device=DEV), torch.full((C,), float("nan"), device=DEV)
-    dyd = torch.full((rows, C), float("nan"), dtype=tdt, device=DEV)
-    assert hip.r3m_bn_maxpool_bwd_dt(dpd.data_ptr(), am.data_ptr(), yd.data_ptr(), coefd.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                     dyd.data_ptr(), ws.data_ptr(), wsb, N, H, W, C, 1, 0, dt, st()) == 0, hip.r3m_last_error()
-    # tolerances of test_bn_train_fwd_bwd (fp32) / test_bn_bf16_fwd_bwd (bf16)
-    assert rel_err(dg.cpu().numpy(), dg_ref.numpy())[0] < (1e-4 if dt == 0 else 2e-4)
-    assert rel_err(db.cpu().numpy(), db_ref.numpy())[0] < (1e-4 if dt == 0 else 2e-4)
-    assert rel_err(dyd.float().cpu().numpy(), dy_ref.numpy())[0] < (2e-4 if dt == 0 else EPS_BF16)
+    check_stem_tail_fused_vs_torch(hip, 2, H, W, 64, dtype)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
