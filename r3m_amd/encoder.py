@@ -5,8 +5,9 @@ torchvision.models.resnet{18,34,50} with fc = Identity — what the reference bu
 Design (MI355X-first, not a translation of torchvision's module graph):
   * the network is ONE native plan in C++ (r3m_amd/csrc/engine.hip): forward and backward are single C calls that enqueue
     the whole kernel sequence on the current HIP stream; Python owns only memory (torch allocator) and autograd glue;
-  * parameters are views into ONE flat fp32 buffer (torchvision order), gradients views into a second one: the fused Adam
-    step and the RCCL gradient all-reduce work on contiguous slices, no per-tensor loops, no bucket copies;
+  * parameters are views into ONE flat fp32 buffer (torchvision order), gradients views into a second one (flat_grads.py keeps
+    the rule for what it holds): the fused Adam step and the RCCL gradient all-reduce work on contiguous slices, no per-tensor
+    loops, no bucket copies;
   * conv weights are logical OIHW tensors with channels_last strides == the OHWI image the kernels read, so
     load_state_dict()/state_dict() interchange with reference checkpoints needs no layout conversion.
 
@@ -20,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .flat_grads import GradLedger, flat_view
 
 
 class _Node(nn.Module):
@@ -46,23 +48,26 @@ def _tensor_table(size):
         L.r3m_resnet_destroy(h)
 
 
+FEATURE_LAYERS = ("layer1", "layer2", "layer3", "layer4")   # torchvision's stages: feature map k is convnet.layerk's output
+
+
 class _EncoderFn(torch.autograd.Function):
-    """h = encoder(x). Backward writes the gradients of the parameters that require grad straight into the module's flat gradient
-    buffer (none when no parameter does) and returns d/dx when x requires grad."""
+    """h = encoder(x), or (h, *maps) with the stage outputs `layers` (indices into FEATURE_LAYERS) as fp32 NCHW tensors. Backward
+    writes the gradients of the parameters that require grad straight into the module's flat gradient buffer (none when no parameter
+    does) and returns d/dx when x requires grad."""
 
     @staticmethod
-    def forward(ctx, x, anchor, module, training, crop=None):
-        h = module._run_forward(x, training, crop, saved=True)
-        ctx.module = module
-        ctx.slot, ctx.generation = module._last_forward
+    def forward(ctx, x, anchor, module, training, crop, layers):
+        if layers is not None:
+            ctx.set_materialize_grads(False)     # an output the loss did not use arrives as None -> a null pointer, not a zero tensor
+        h, maps, ctx.slot, ctx.generation = module._run_forward(x, training, crop, saved=True, layers=layers)
+        ctx.module, ctx.layers = module, layers
         if 0 <= ctx.slot < len(module._ring):
-            # the slot stays "live" while this graph node exists and has not run its backward: forwards that need no backward
-            # (no_grad / eval calls between a training forward and its backward) must not take it (_pick_slot)
-            module._ring[ctx.slot].waiting = weakref.ref(ctx)
-        return h
+            module._ring[ctx.slot].hold(ctx)
+        return h if layers is None else (h,) + tuple(maps[k] for k in layers)
 
     @staticmethod
-    def backward(ctx, dh):
+    def backward(ctx, dh, *dmaps):
         m = ctx.module
         # The data-parallel stage hook starts an ASYNC all-reduce on a slice of the flat gradient buffer. With several live forwards
         # ((h1 + h2).backward()) every backward accumulates into the same buffer, so only the LAST outstanding one may fire it: an
@@ -71,66 +76,17 @@ class _EncoderFn(torch.autograd.Function):
         # exception before backward — stops counting when its node is collected; round 5 kept a manual counter that such a forward
         # left raised for good, silently costing every later step its comm / compute overlap: ADVICE r5).
         others = sum(1 for sl in m._ring if sl.live and sl.waiting() is not ctx)
-        params, input_grad = any(p.requires_grad for p in m.parameters()), ctx.needs_input_grad[0]
-        if params and not input_grad:          # the pre-training backward
-            dx = m._run_backward(dh.contiguous(), ctx.generation, ctx.slot, fire_hooks=others == 0)
-        else:
-            dx = m._run_backward(dh.contiguous(), ctx.generation, ctx.slot, fire_hooks=others == 0, params=params, input_grad=input_grad)
+        grads = None
+        if ctx.layers is not None:
+            grads = [None] * 4
+            for k, d in zip(ctx.layers, dmaps):
+                if d is not None:
+                    grads[k] = d.float().contiguous()
+        dx = m._run_backward(None if dh is None else dh.contiguous(), ctx.generation, ctx.slot, fire_hooks=others == 0,
+                             params=any(p.requires_grad for p in m.parameters()), input_grad=ctx.needs_input_grad[0], dmaps=grads)
         if 0 <= ctx.slot < len(m._ring):
-            w = m._ring[ctx.slot].waiting
-            if w is not None and w() is ctx:
-                m._ring[ctx.slot].waiting = None
-        return dx, None, None, None, None
-
-
-FEATURE_LAYERS = ("layer1", "layer2", "layer3", "layer4")   # torchvision's stages: feature map k is convnet.layerk's output
-
-
-class _NoEmbeddingGrad:
-    """Stands in for dh in a backward whose loss did not use the embedding: a null pointer on the device of the feature-map
-    gradients (r3m_resnet_backward_features: dh == NULL, zeros flow down from the pool instead of a zero tensor through a kernel)."""
-
-    def __init__(self, device):
-        self.device = device
-
-    def contiguous(self):
-        return self
-
-    def data_ptr(self):
-        return None
-
-
-class _FeaturesFn(torch.autograd.Function):
-    """(h, *maps) = encoder(x) with the requested stage outputs as fp32 NCHW tensors. The slot, generation and stage-hook
-    bookkeeping is _EncoderFn's own code, run on this node's ctx; the maps and their gradients travel through the module
-    (_feat_request -> _run_forward -> _feat_result, _feat_grads -> _run_backward)."""
-
-    @staticmethod
-    def forward(ctx, x, anchor, module, training, layers):
-        ctx.set_materialize_grads(False)     # an output the loss did not use arrives as None -> a null pointer, not a zero tensor
-        module._feat_request = layers
-        try:
-            h = _EncoderFn.forward(ctx, x, anchor, module, training)
-        finally:
-            module._feat_request = None
-        maps, module._feat_result = module._feat_result, None
-        ctx.layers = layers
-        return (h,) + tuple(maps[k] for k in layers)
-
-    @staticmethod
-    def backward(ctx, dh, *dmaps):
-        m = ctx.module
-        grads = [None] * 4
-        for k, d in zip(ctx.layers, dmaps):
-            if d is not None:
-                grads[k] = d.contiguous() if d.dtype == torch.float32 else d.float().contiguous()
-        if dh is None:
-            dh = _NoEmbeddingGrad(next(g for g in grads if g is not None).device)
-        m._feat_grads = grads
-        try:
-            return _EncoderFn.backward(ctx, dh)
-        finally:
-            m._feat_grads = None
+            m._ring[ctx.slot].release(ctx)
+        return dx, None, None, None, None, None
 
 
 PRECISIONS = {"fp32": 0, "bf16": 1}   # R3M_DT_F32 / R3M_DT_BF16 (include/r3m_hip.h)
@@ -148,6 +104,16 @@ class _LiveSlot:
     @property
     def live(self):
         return self.waiting is not None and self.waiting() is not None
+
+    def hold(self, node):
+        """the slot stays live while autograd node `node` exists and has not run its backward: forwards that need no backward
+        (no_grad / eval calls between a training forward and its backward) must not take it (_pick_slot)"""
+        self.waiting = weakref.ref(node)
+
+    def release(self, node):
+        """node's backward has run; a slot that a later forward took over stays that forward's"""
+        if self.waiting is not None and self.waiting() is node:
+            self.waiting = None
 
 
 def _pick_slot(live, pos, saved):
@@ -203,39 +169,22 @@ class HipResNet(nn.Module):
         bn_i = 0
         for name, kind, off, shape in table:
             parent, leaf = self._resolve(name)
-            n = int(math.prod(shape))
-            if kind == 0:
-                O, I, kh, kw = shape
-                t = nn.Parameter(flat_p[off:off + n].view(O, kh, kw, I).permute(0, 3, 1, 2))  # logical OIHW, physical OHWI
-                parent.register_parameter(leaf, t)
-            elif kind in (1, 2):
-                t = nn.Parameter(flat_p[off:off + n].view(shape))
-                parent.register_parameter(leaf, t)
+            if kind <= 2:
+                parent.register_parameter(leaf, nn.Parameter(flat_view(flat_p, off, shape)))
             else:
-                t = flat_b[off:off + n].view(shape)
-                parent.register_buffer(leaf, t)
+                parent.register_buffer(leaf, flat_view(flat_b, off, shape))
                 if kind == 4:
                     parent.register_buffer("num_batches_tracked", flat_nbt[bn_i])
                     bn_i += 1
         self.fc = nn.Identity()   # models_r3m.py:62
         self._flat_p, self._flat_b, self._flat_nbt = flat_p, flat_b, flat_nbt
-        self._flat_g = None
+        # the flat gradient buffer and what it holds, per parameter tensor in flat-buffer order
+        self._grads = GradLedger([(off, int(math.prod(shape))) for _, kind, off, shape in table if kind <= 2])
         self._ring = [_LiveSlot() for _ in range(self.max_live_forwards)]   # _plans / _arena below are slot 0's
         self._ring_pos = 0
         self._scratch = None          # _LiveSlot for forwards without a backward while every ring slot is live (_pick_slot)
-        self._last_forward = (0, 0)   # (slot, generation) of the most recent forward
-        self._grad_fresh = True
-        # per parameter tensor, in flat-buffer order (_param_ranges): its gradient was written since zero_grad() / its range of the
-        # flat gradient buffer may hold something other than zeros
-        self._param_ranges = [(off, int(math.prod(shape))) for _, kind, off, shape in table if kind <= 2]
-        self._g_written = [False] * len(self._param_ranges)
-        self._g_dirty = [False] * len(self._param_ranges)
-        self._g_viewed = [False] * len(self._param_ranges)      # flat_grads() has given this tensor its .grad view
         self._plan_masks = {}     # native handle -> the trainable mask it was last given (absent: all trainable, the plan's default)
         self._stage_hook = None   # callable(stage, offset, count) after each backward stage (data-parallel wrapper)
-        # forward_features: the stage outputs the running call wants (indices 0..3), what its forward produced ({index: [F,C,H,W]}),
-        # and the gradients its backward was handed ([4], None = none); all None outside such a call
-        self._feat_request = self._feat_result = self._feat_grads = None
         self.reset_parameters()
 
     @property
@@ -251,14 +200,17 @@ class HipResNet(nn.Module):
         return self._ring[0].arena
 
     @_arena.setter
-    def _arena(self, v):          # assigning None drops EVERY slot's arena (re-flatten / device move)
-        if v is None:
-            for sl in self._ring:
-                sl.arena = None
-            if self._scratch is not None:
-                self._scratch.arena = None
-        else:
-            self._ring[0].arena = v
+    def _arena(self, v):
+        self._ring[0].arena = v
+
+    @property
+    def _flat_g(self):            # the flat gradient buffer, None until somebody asked for it (flat_grads)
+        return self._grads.buffer
+
+    def _drop_arenas(self):
+        """release every slot's activation arena (re-flatten / device move)"""
+        for sl in self._ring + ([self._scratch] if self._scratch is not None else []):
+            sl.arena = None
 
     # ---- structure -------------------------------------------------------------------------------------------
     def _resolve(self, dotted):
@@ -321,14 +273,7 @@ class HipResNet(nn.Module):
         bn_i = 0
         with torch.no_grad():
             for name, kind, off, shape, t in slots:
-                n = int(math.prod(shape))
-                if kind == 0:
-                    O, I, kh, kw = shape
-                    v = flat_p[off:off + n].view(O, kh, kw, I).permute(0, 3, 1, 2)
-                elif kind in (1, 2):
-                    v = flat_p[off:off + n].view(shape)
-                else:
-                    v = flat_b[off:off + n].view(shape)
+                v = flat_view(flat_p if kind <= 2 else flat_b, off, shape)
                 v.copy_(t)
                 if kind <= 2:
                     t.data = v
@@ -342,8 +287,8 @@ class HipResNet(nn.Module):
                         parent._buffers["num_batches_tracked"] = flat_nbt[bn_i]
                         bn_i += 1
         self._flat_p, self._flat_b, self._flat_nbt = flat_p, flat_b, flat_nbt
-        self._drop_grads()
-        self._arena = None
+        self._grads.drop()          # (every .grad was cleared above)
+        self._drop_arenas()
 
     def _apply(self, fn, *a, **k):
         super()._apply(fn, *a, **k)
@@ -354,54 +299,26 @@ class HipResNet(nn.Module):
         self._ensure()
         return self._flat_p
 
-    def _drop_grads(self):
-        """forget the flat gradient buffer (re-flatten, copies): nothing written, nothing to accumulate onto"""
-        self._flat_g = None
-        self._g_viewed = [False] * len(self._param_ranges)
-        self._grad_fresh = True
-        self._g_written = [False] * len(self._param_ranges)
-        self._g_dirty = [False] * len(self._param_ranges)
-
     def _params_in_order(self):
-        """the parameter tensors in flat-buffer order (the order of _param_ranges / _g_written)"""
+        """the parameter tensors in flat-buffer order (the order of param_ranges() / grads_written())"""
         return [t for _, kind, _, _, t in self._named_slots() if kind <= 2]
-
-    def _grad_view(self, t, off):
-        if t.dim() == 4:
-            O, I, kh, kw = t.shape
-            return self._flat_g[off:off + t.numel()].view(O, kh, kw, I).permute(0, 3, 1, 2)
-        return self._flat_g[off:off + t.numel()].view(t.shape)
 
     def flat_grads(self):
         """The flat gradient buffer. `.grad` views into it are attached to the parameters that require grad (whoever fills the buffer
         by hand sees the values through them) or whose gradient a backward has written since zero_grad(); a frozen parameter's .grad
         stays None (unless the user left one there), as torch leaves it. Ranges no backward wrote hold zeros."""
         self._ensure()
-        if self._flat_g is None:
-            self._flat_g = torch.zeros_like(self._flat_p)
-        self._attach_grad_views()
-        return self._flat_g
-
-    def _attach_grad_views(self, params=None):
-        viewed = self._g_viewed
-        if all(viewed):
-            return
-        params = params or self._params_in_order()
-        for i, (t, (off, _)) in enumerate(zip(params, self._param_ranges)):
-            if not viewed[i] and (self._g_written[i] or t.requires_grad):
-                if t.grad is None:
-                    t.grad = self._grad_view(t, off)
-                viewed[i] = True
+        return self._grads.grads(self._flat_p, self._params_in_order)
 
     def param_ranges(self):
         """[(offset, count)] of every parameter tensor in the flat buffers, ascending and gap-free (optimizers: the units that can be
         frozen one by one)"""
-        return self._param_ranges
+        return self._grads.ranges
 
     def grads_written(self):
         """per param_ranges() entry: a backward wrote this tensor's gradient since zero_grad() (torch: `p.grad is not None` after
         zero_grad(set_to_none=True))"""
-        return self._g_written
+        return self._grads.written
 
     def _ensure(self):
         if not self._is_flat():
@@ -410,30 +327,11 @@ class HipResNet(nn.Module):
     def mark_grads_stale(self):
         """Called by the optimizer's zero_grad(): the next backward overwrites instead of accumulating, and until one arrives no
         parameter has a gradient."""
-        self._grad_fresh = True
-        self._g_written = [False] * len(self._param_ranges)
+        self._grads.mark_stale()
 
-    def _zero_grad_ranges(self, idx):
-        """zero the flat-gradient ranges of the parameter tensors idx (ascending), neighbours in one fill"""
-        a = b = None
-        for i in idx:
-            off, n = self._param_ranges[i]
-            if b == off:
-                b = off + n
-                continue
-            if a is not None:
-                self._flat_g[a:b].zero_()
-            a, b = off, off + n
-        if a is not None:
-            self._flat_g[a:b].zero_()
-
-    def _begin_param_backward(self, h):
-        """Before stage 0 of a backward that writes parameter gradients: hand the plan the trainable mask (requires_grad of every
-        parameter) when it changed, and keep the rule 'gradient of a tensor = sum over the backwards since zero_grad() in which it was
-        trainable, never-written ranges are zero': a tensor that turns trainable inside an accumulation window starts from zero, a
-        tensor frozen since the last window loses its stale values (and its .grad view)."""
-        params = self._params_in_order()
-        req = [t.requires_grad for t in params]
+    def _send_trainable(self, h, req):
+        """Before stage 0 of a backward that writes parameter gradients: hand plan h the trainable mask (req: requires_grad of every
+        parameter, flat-buffer order) when it changed. Returns whether some tensor is frozen."""
         mask = None
         if not all(req):
             it = iter(req)
@@ -444,25 +342,6 @@ class HipResNet(nn.Module):
                 self._plan_masks.pop(h, None)
             else:
                 self._plan_masks[h] = mask
-        fresh, written, dirty = self._grad_fresh, self._g_written, self._g_dirty
-        if fresh:
-            stale = [i for i, r in enumerate(req) if not r and dirty[i]]
-            for i, r in enumerate(req):
-                if r or not (dirty[i] or self._g_viewed[i]):
-                    continue
-                dirty[i] = False
-                g = params[i].grad                   # frozen now: its view of the flat buffer goes, a .grad the user put there stays
-                if g is not None and g.device == self._flat_g.device and g.data_ptr() == self._flat_g.data_ptr() + self._param_ranges[i][0] * 4:
-                    params[i].grad = None
-                self._g_viewed[i] = False
-        else:
-            stale = [i for i, r in enumerate(req) if r and not written[i] and dirty[i]]
-        if stale:
-            self._zero_grad_ranges(stale)
-        for i, r in enumerate(req):
-            if r:
-                written[i] = dirty[i] = True
-        self._attach_grad_views(params)              # .grad views for the tensors this backward writes first
         return mask is not None
 
     def stage_range(self, stage):
@@ -533,10 +412,8 @@ class HipResNet(nn.Module):
         hook belong to THIS object (a copied integer handle would be destroyed twice); the copy re-creates them lazily. The
         reference R3M deep-copies cleanly (plain nn.Module), so must this."""
         st = self.__dict__.copy()
-        st.update(_ring=[_LiveSlot() for _ in self._ring], _ring_pos=0, _scratch=None, _last_forward=(0, 0), _flat_g=None,
-                  _stage_hook=None, _grad_fresh=True, _plan_masks={}, _g_viewed=[False] * len(self._param_ranges),
-                  _g_written=[False] * len(self._param_ranges),
-                  _g_dirty=[False] * len(self._param_ranges))
+        st.update(_ring=[_LiveSlot() for _ in self._ring], _ring_pos=0, _scratch=None, _stage_hook=None, _plan_masks={},
+                  _grads=GradLedger(self._grads.ranges))
         return st
 
     def __setstate__(self, st):
@@ -544,10 +421,11 @@ class HipResNet(nn.Module):
         for p in self.parameters():      # gradients were views of the dropped flat buffer
             p.grad = None
 
-    def _run_forward(self, x, training, crop=None, saved=False):
+    def _run_forward(self, x, training, crop=None, saved=False, layers=None):
         """x: [F,3,H,W] fp32 frames, or None with crop = augment.CroppedClips (raw clips + boxes, resampled in the stem pre-pass).
         saved: the call comes from autograd (_EncoderFn) and a backward will read this forward's activations.
-        Inside forward_features (self._feat_request set) the requested stage outputs are left in self._feat_result."""
+        layers: the stage outputs wanted as well (indices 0..3 = layer1..layer4; frames only), or None.
+        Returns (h, {index: [F,C,H,W] fp32} or None, slot, the slot's generation)."""
         L = _lib.lib()
         src = crop.raw if crop is not None else x
         F = src.shape[0]
@@ -566,38 +444,34 @@ class HipResNet(nn.Module):
         # 1 train / 0 eval with the activations kept for a backward / 2 inference: eval statistics and nothing kept — BatchNorm, residual
         # join and ReLU ride in the convolutions' stores (what load_r3m(...).eval() under no_grad runs, /root/reference/r3m/__init__.py:72-75)
         mode = 1 if training else (0 if saved else 2)
-        want = self._feat_request
+        maps = ptrs = None
         with _lib.on(src):
-            if want is not None:
-                maps = {k: torch.empty((F,) + self._feature_shape(h, k), dtype=torch.float32, device=src.device) for k in want}
-                ptrs = (C.c_void_p * 4)(*[_lib.ptr(maps.get(k)) for k in range(4)])
-                _lib.check(L.r3m_resnet_forward_features(h, x.data_ptr(), self._flat_p.data_ptr(), self._flat_b.data_ptr(),
-                                                         arena.data_ptr(), out.data_ptr(), ptrs, mode, _lib.stream_ptr(x.device)),
-                           "resnet_forward_features")
-                self._feat_result = maps
-            elif crop is not None:
+            if crop is not None:
                 _lib.check(L.r3m_resnet_forward_crop(h, crop.raw.data_ptr(), 1 if crop.raw.dtype == torch.uint8 else 0,
                                                      crop.boxes.data_ptr(), crop.frames_per_box, crop.raw.shape[-2], crop.raw.shape[-1],
                                                      self._flat_p.data_ptr(), self._flat_b.data_ptr(), arena.data_ptr(),
                                                      out.data_ptr(), mode, _lib.stream_ptr(src.device)),
                            "resnet_forward_crop")
             else:
-                _lib.check(L.r3m_resnet_forward(h, x.data_ptr(), self._flat_p.data_ptr(), self._flat_b.data_ptr(),
-                                                arena.data_ptr(), out.data_ptr(), mode,
-                                                _lib.stream_ptr(x.device)), "resnet_forward")
+                if layers is not None:
+                    maps = {k: torch.empty((F,) + self._feature_shape(h, k), dtype=torch.float32, device=x.device) for k in layers}
+                    ptrs = (C.c_void_p * 4)(*[_lib.ptr(maps.get(k)) for k in range(4)])
+                _lib.check(L.r3m_resnet_forward_features(h, x.data_ptr(), self._flat_p.data_ptr(), self._flat_b.data_ptr(),
+                                                         arena.data_ptr(), out.data_ptr(), ptrs, mode, _lib.stream_ptr(x.device)),
+                           "resnet_forward_features")
         if training:
             self._flat_nbt += 1
         slot.generation += 1
         slot.F, slot.hw = F, hw
-        self._last_forward = (si, slot.generation)
-        return out
+        return out, maps, si, slot.generation
 
-    def _run_backward(self, dh, generation, si=0, fire_hooks=True, params=True, input_grad=False):
-        """params: write the gradients of the parameters that require grad into the flat gradient buffer (False: frozen encoder — no
+    def _run_backward(self, dh, generation, si, fire_hooks, params, input_grad, dmaps=None):
+        """dh: gradient of the embedding, or None when the loss did not use it (then dmaps has an entry: zeros flow down from the
+        pool instead of a zero tensor through a kernel). dmaps: [4] gradients of the stage outputs (fp32 NCHW, None = none), or None.
+        params: write the gradients of the parameters that require grad into the flat gradient buffer (False: frozen encoder — no
         weight-gradient launch, the buffer is neither created nor touched, no stage hook fires). With some parameters frozen the
         engine runs only what the trainable ones (and the input gradient) need; all four stage hooks still fire, in order.
-        input_grad: return d/d(frames) [F,3,H,W] fp32.
-        Inside a forward_features backward (self._feat_grads set) the stage outputs' gradients join, and dh may be the null stand-in."""
+        input_grad: return d/d(frames) [F,3,H,W] fp32."""
         slot = self._slot(si)
         if generation != slot.generation or slot.arena is None:
             raise RuntimeError(f"r3m_amd: the encoder ran {len(self._ring)} other forward(s) before this backward; its saved "
@@ -605,31 +479,30 @@ class HipResNet(nn.Module):
                                f"max_live_forwards=k (R3M(..., max_live_forwards=k)) to keep k forwards alive at once")
         L = _lib.lib()
         h = self._plan(slot.F, si, slot.hw)
-        g = self.flat_grads() if params else None
-        accumulate = 0 if self._grad_fresh else 1
-        partial = self._begin_param_backward(h) if params else False
-        dx = torch.empty((slot.F, 3) + tuple(slot.hw), dtype=torch.float32, device=dh.device) if input_grad else None
-        dmaps = None if self._feat_grads is None else (C.c_void_p * 4)(*[_lib.ptr(d) for d in self._feat_grads])
-        with _lib.on(dh):
+        g, accumulate, partial = None, 0, False
+        if params:
+            g = self.flat_grads()
+            ps = self._params_in_order()
+            req = [t.requires_grad for t in ps]
+            partial = self._send_trainable(h, req)
+            accumulate = self._grads.begin(ps, req)
+        lead = dh if dh is not None else next(d for d in dmaps if d is not None)
+        dev = lead.device
+        dx = torch.empty((slot.F, 3) + tuple(slot.hw), dtype=torch.float32, device=dev) if input_grad else None
+        if dmaps is not None:                        # every stage carries the same array; the stage that owns an entry reads it
+            dmaps = (C.c_void_p * 4)(*[_lib.ptr(d) for d in dmaps])
+        with _lib.on(lead):
             for stage in range(4):
-                if dmaps is not None:                # every stage carries the same array; the stage that owns an entry reads it
-                    _lib.check(L.r3m_resnet_backward_features(h, dh.data_ptr(), dmaps, self._flat_p.data_ptr(), _lib.ptr(g),
-                                                              slot.arena.data_ptr(), stage, stage + 1, accumulate,
-                                                              _lib.ptr(dx) if stage == 3 or partial else None, 0,
-                                                              _lib.stream_ptr(dh.device)), "resnet_backward_features")
-                elif g is not None and dx is None:   # the pre-training path: unchanged launch sequence
-                    _lib.check(L.r3m_resnet_backward(h, dh.data_ptr(), self._flat_p.data_ptr(), g.data_ptr(), slot.arena.data_ptr(),
-                                                     stage, stage + 1, accumulate, _lib.stream_ptr(dh.device)), "resnet_backward")
-                else:
-                    _lib.check(L.r3m_resnet_backward_ex(h, dh.data_ptr(), self._flat_p.data_ptr(), _lib.ptr(g), slot.arena.data_ptr(),
-                                                        # (frozen tensors: stage 0 plans the backward and must know dx is wanted)
-                                                        stage, stage + 1, accumulate, _lib.ptr(dx) if stage == 3 or partial else None, 0,
-                                                        _lib.stream_ptr(dh.device)), "resnet_backward_ex")
+                _lib.check(L.r3m_resnet_backward_features(h, _lib.ptr(dh), dmaps, self._flat_p.data_ptr(), _lib.ptr(g),
+                                                          slot.arena.data_ptr(), stage, stage + 1, accumulate,
+                                                          # (frozen tensors: stage 0 plans the backward and must know dx is wanted)
+                                                          _lib.ptr(dx) if stage == 3 or partial else None, 0,
+                                                          _lib.stream_ptr(dev)), "resnet_backward_features")
                 if g is not None and self._stage_hook is not None and fire_hooks:
                     off, cnt = self.stage_range(stage)
                     self._stage_hook(stage, off, cnt)
         if g is not None:
-            self._grad_fresh = False
+            self._grads.finish()
         return dx
 
     @staticmethod
@@ -656,47 +529,27 @@ class HipResNet(nn.Module):
         if isinstance(x, CroppedClips):
             raise TypeError("forward_features: CroppedClips input is not supported (the crop-fed forward exports no feature maps); "
                             "resample the clips first and pass [F,3,H,W] frames")
-        if not x.is_cuda:
-            raise RuntimeError("r3m_amd: the encoder runs on MI355X through libr3m_hip.so only; got a CPU tensor "
-                               "(no CPU / eager fallback exists — the CPU oracle lives under oracle/ for tests)")
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
-            raise ValueError(f"expected [F,3,H,W] frames, got {tuple(x.shape)}")
-        if tuple(x.shape[2:]) != (224, 224):
-            self.check_input_hw(x.shape[2], x.shape[3])
-        self._ensure()
-        if self._flat_p.device != x.device:
-            raise RuntimeError(f"encoder parameters on {self._flat_p.device}, input on {x.device}")
-        x = x.contiguous()
-        if x.dtype != torch.float32:
-            x = x.float()
+        x, _ = self._prepare_frames(x)
         idx = tuple(FEATURE_LAYERS.index(name) for name in layers)
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or x.requires_grad):
-            anchor = next((p for p in self.parameters() if p.requires_grad), None)
-            if anchor is None:
-                anchor = next(self.parameters())
-            h, *maps = _FeaturesFn.apply(x, anchor, self, self.training, idx)
+            h, *maps = _EncoderFn.apply(x, self._anchor(), self, self.training, None, idx)
         else:
-            self._feat_request = idx
-            try:
-                h = self._run_forward(x, self.training)
-            finally:
-                self._feat_request = None
-            got, self._feat_result = self._feat_result, None
+            h, got, _, _ = self._run_forward(x, self.training, layers=idx)
             maps = [got[k] for k in idx]
         return h, dict(zip(layers, maps))
 
-    def forward(self, x):
-        """x: [F,3,H,W] float32 CUDA tensor with values in 0..255, any H and W in 32..512 (torchvision's ResNet takes any size; 224 x 224
-        runs the specialised stem kernels, other sizes the general ones). The /255 and Normalize of R3M.forward are fused into the stem
-        kernel. Returns [F, outdim]."""
+    def _prepare_frames(self, x):
+        """What every forward starts with: refuse what the engine cannot take, re-flatten if needed, coerce. x: [F,3,H,W] frames or
+        augment.CroppedClips. Returns (contiguous fp32 frames, None) or (None, the clips)."""
         if not x.is_cuda:
             raise RuntimeError("r3m_amd: the encoder runs on MI355X through libr3m_hip.so only; got a CPU tensor "
                                "(no CPU / eager fallback exists — the CPU oracle lives under oracle/ for tests)")
         from .augment import CroppedClips
-        crop = x if isinstance(x, CroppedClips) else None
-        if crop is not None and tuple(crop.out_hw) != (224, 224):
-            raise ValueError(f"CroppedClips must resample to 224x224, got {crop.out_hw}")
-        if crop is None:
+        crop = isinstance(x, CroppedClips)
+        if crop:
+            if tuple(x.out_hw) != (224, 224):
+                raise ValueError(f"CroppedClips must resample to 224x224, got {x.out_hw}")
+        else:
             if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1:
                 raise ValueError(f"expected [F,3,H,W] frames, got {tuple(x.shape)}")
             if tuple(x.shape[2:]) != (224, 224):
@@ -704,18 +557,20 @@ class HipResNet(nn.Module):
         self._ensure()
         if self._flat_p.device != x.device:
             raise RuntimeError(f"encoder parameters on {self._flat_p.device}, input on {x.device}")
-        if crop is None:
-            x = x.contiguous()
-            if x.dtype != torch.float32:
-                x = x.float()
+        return (None, x) if crop else (x.contiguous().float(), None)
+
+    def _anchor(self):
+        """what makes autograd record the node: a parameter that requires grad, when there is one — the first may be frozen"""
+        p = next((p for p in self.parameters() if p.requires_grad), None)
+        return p if p is not None else next(self.parameters())
+
+    def forward(self, x):
+        """x: [F,3,H,W] float32 CUDA tensor with values in 0..255, any H and W in 32..512 (torchvision's ResNet takes any size; 224 x 224
+        runs the specialised stem kernels, other sizes the general ones). The /255 and Normalize of R3M.forward are fused into the stem
+        kernel. Returns [F, outdim]."""
+        x, crop = self._prepare_frames(x)
         # a graph is recorded when anything upstream wants a gradient: the parameters (training) or the frames (obs.grad: the
         # encoder as a differentiable reward / perceptual loss, parameters frozen or not)
-        needs_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                                  or (crop is None and x.requires_grad))
-        if needs_grad:
-            # (what makes autograd record the node: a parameter that requires grad, when there is one — the first may be frozen)
-            anchor = next((p for p in self.parameters() if p.requires_grad), None)
-            if anchor is None:
-                anchor = next(self.parameters())
-            return _EncoderFn.apply(None if crop is not None else x, anchor, self, self.training, crop)
-        return self._run_forward(None if crop is not None else x, self.training, crop)
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or (crop is None and x.requires_grad)):
+            return _EncoderFn.apply(x, self._anchor(), self, self.training, crop, None)
+        return self._run_forward(x, self.training, crop)[0]

@@ -378,7 +378,7 @@ class DistributedR3M(nn.Module):
         self._reduce_heads()
         self._flush_held()          # a backward that stopped before the last stage (partial stage range) leaves nothing behind
         conv = self.module.convnet
-        if self._stages_seen == 0 and conv._flat_g is not None and not conv._grad_fresh:
+        if self._stages_seen == 0 and conv._grads.pending():
             # encoder gradients exist but no backward fired the stage hooks (several live forwards of which one was never
             # backpropagated): reduce the whole buffer now — correct, just not overlapped
             g = conv.flat_grads()

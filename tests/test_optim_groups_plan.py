@@ -212,7 +212,7 @@ def test_group_builders_on_the_encoders(size):
     assert all(g["weight_decay"] == (0.05 if i % 2 == 0 else 0.0) for i, g in enumerate(both))
     opt = FusedAdamW([net], param_groups=both)
     assert len(opt.param_groups) == 10                                                     # every tensor named: no rest group
-    net._g_written = [True] * len(net.param_ranges())
+    net._grads.mark_all_written()
     p = opt._plan(0, net)
     # every range is one run of neighbours with one (lr, wd); adjacent ranges differ; together they cover the buffer
     assert p.offs[0] == 0 and p.offs[-1] + p.counts[-1] == net.flat_params().numel()

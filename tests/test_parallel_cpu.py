@@ -140,18 +140,17 @@ def _worker(rank, world, port, q):
         conv = m3.convnet
         fired = []
 
-        def fake_forward(x, training, crop=None, saved=False):
+        def fake_forward(x, training, crop=None, saved=False, layers=None):
             from r3m_amd.encoder import _pick_slot
             slot, conv._ring_pos = _pick_slot([sl.live for sl in conv._ring], conv._ring_pos, saved)     # as the real forward does
-            conv._last_forward = (slot, 0)
-            return torch.ones((x.shape[0], conv.outdim))
+            return torch.ones((x.shape[0], conv.outdim)), None, slot, 0
 
-        def fake_backward(dh, generation, si=0, fire_hooks=True):
+        def fake_backward(dh, generation, si, fire_hooks, params, input_grad, dmaps=None):
             gb = conv.flat_grads()
-            if conv._grad_fresh:
+            if conv._grads.fresh:
                 gb.zero_()
             gb += float(rank + 1)
-            conv._grad_fresh = False
+            conv._grads.finish()
             fired.append(fire_hooks)
             if fire_hooks and conv._stage_hook is not None:
                 for stage in range(4):
@@ -162,8 +161,8 @@ def _worker(rank, world, port, q):
         x = torch.zeros((5, 3, 224, 224))
         for step in range(2):
             m3.encoder_opt.zero_grad()
-            h1 = _EncoderFn.apply(x, anchor, conv, True, None)
-            h2 = _EncoderFn.apply(x, anchor, conv, True, None)
+            h1 = _EncoderFn.apply(x, anchor, conv, True, None, None)
+            h2 = _EncoderFn.apply(x, anchor, conv, True, None, None)
             assert conv._awaiting == 2
             fired.clear()
             before = net3.sync.launched
@@ -177,8 +176,8 @@ def _worker(rank, world, port, q):
         # the whole buffer itself (and says so once); when the graph is dropped the count falls back by itself
         import warnings
         m3.encoder_opt.zero_grad()
-        h1 = _EncoderFn.apply(x, anchor, conv, True, None)
-        h2 = _EncoderFn.apply(x, anchor, conv, True, None)
+        h1 = _EncoderFn.apply(x, anchor, conv, True, None, None)
+        h2 = _EncoderFn.apply(x, anchor, conv, True, None, None)
         fired.clear()
         before = net3.sync.launched
         h2.sum().backward()
@@ -191,9 +190,9 @@ def _worker(rank, world, port, q):
         assert net3.sync.launched == before + 1 and conv._awaiting == 0
         # ... and the NEXT step overlaps again: a dropped forward leaves nothing behind
         m3.encoder_opt.zero_grad()
-        hd = _EncoderFn.apply(x, anchor, conv, True, None)       # a grad-enabled forward nobody differentiates
+        hd = _EncoderFn.apply(x, anchor, conv, True, None, None)       # a grad-enabled forward nobody differentiates
         del hd
-        h1 = _EncoderFn.apply(x, anchor, conv, True, None)
+        h1 = _EncoderFn.apply(x, anchor, conv, True, None, None)
         fired.clear()
         h1.sum().backward()
         assert fired == [True]
@@ -203,9 +202,9 @@ def _worker(rank, world, port, q):
         assert torch.allclose(g3, torch.full_like(g3, sum(range(1, world + 1)) / world))
         # two SEPARATE backward() calls in one step: the second would add into slices that are being reduced — refused
         m3.encoder_opt.zero_grad()
-        h1 = _EncoderFn.apply(x, anchor, conv, True, None)
+        h1 = _EncoderFn.apply(x, anchor, conv, True, None, None)
         h1.sum().backward()
-        h2 = _EncoderFn.apply(x, anchor, conv, True, None)
+        h2 = _EncoderFn.apply(x, anchor, conv, True, None, None)
         try:
             h2.sum().backward()
             raise AssertionError("second encoder backward before finish_gradient_sync() was accepted")

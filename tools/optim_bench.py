@@ -33,7 +33,7 @@ def main():
     m, v = torch.zeros_like(p), torch.zeros_like(p)
     n = p.numel()
     opt = FusedAdamW([net], lr=1e-4, param_groups=no_decay_groups(net, 0.05))
-    net._g_written = [True] * len(net.param_ranges())            # as after a backward with everything trainable
+    net._grads.mark_all_written()                                # as after a backward with everything trainable
     plan = opt._plan(0, net)
     launches = (len(plan.offs) + 63) // 64
     print(f"ResNet-50: {n} elements, {len(net.param_ranges())} tensors; no_decay_groups -> {len(plan.offs)} merged ranges, "
