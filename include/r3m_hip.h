@@ -467,6 +467,48 @@ int r3m_langrew_call_backward(const float* dscore, const float* params, float* g
                               void* workspace, size_t workspace_bytes, int R, int D, int hidden, int lang_dim, int accumulate,
                               r3m_stream_t stream);
 
+/* ---------------- sentence features: the DistilBERT forward of LangEncoder (r3m/models/models_language.py:13-35) ----------------
+ * What the reference reaches through transformers' DistilBertModel under no_grad, then last_hidden_state.mean(1). Inference only,
+ * fp32, no dropout. The model is six HOST ints, dims = {vocab, max_pos, dim, n_layers, n_heads, ffn_dim} (distilbert-base-uncased:
+ * {30522, 512, 768, 6, 12, 3072}), and one flat fp32 DEVICE parameter buffer of r3m_text_num_params(dims) floats (66 362 880 for
+ * distilbert-base). r3m_text_tensor_info enumerates the buffer under HuggingFace's own state-dict names (index <
+ * r3m_text_num_tensors): offset and count in floats, ndim 1 or 2, shape2 = {rows, columns} ({n, 1} for a vector). Linear weights
+ * stay [out][in]; a layer's q, k and v weights, then their biases, are adjacent, so QKV is one [3 dim, dim] Linear. Every offset is
+ * a multiple of 4 floats: a 16-byte-aligned buffer keeps every tensor 16-byte aligned. The queries run without a GPU; num_params /
+ * num_tensors return -1 and workspace_bytes returns 0 for dims or shapes they refuse.
+ * Supported: dim % 64 == 0, ffn_dim % 64 == 0, head_dim = dim / n_heads a multiple of 32, 1 <= T <= min(max_pos, 128), B >= 1,
+ * B * T * max(3 dim, ffn_dim) < 2^31, and T keys and values of one head within a CU's LDS (4 (T (2 head_dim + 4) + 4 head_dim + 4 T)
+ * bytes <= 160 KiB: head_dim 64 up to T = 128, head_dim 192 up to T = 102). Anything else returns non-zero before any HIP call.
+ * r3m_text_forward: ids, mask int32 [B,T] (mask != 0: a real token); feats [B,dim]; hidden: the last hidden state [B,T,dim], or
+ * NULL. pool 0: mean over ALL T positions, padding included (models_language.py:34); pool 1: mean over the positions with
+ * mask != 0, the count clamped to at least 1. 2 + 8 n_layers launches on `stream`, no allocation, no synchronisation.
+ * Padded query rows are computed like any other row (they attend to the real keys; pool 0 averages them in). An id outside
+ * [0, vocab) is CLAMPED into the table by the embedding kernel, so a bad id never reads outside the parameter buffer; callers that
+ * want an error validate ids on the host (r3m_amd.text.HipDistilBert does). */
+long long r3m_text_num_params(const int* dims);
+int r3m_text_num_tensors(const int* dims);
+int r3m_text_tensor_info(const int* dims, int index, char* name, int name_cap, long long* offset, long long* count, int* ndim,
+                         int* shape2);
+size_t r3m_text_workspace_bytes(const int* dims, int B, int T);
+int r3m_text_forward(const int* ids, const int* mask, const float* params, float* feats, float* hidden, void* workspace,
+                     size_t workspace_bytes, int B, int T, const int* dims, int pool, r3m_stream_t stream);
+/* The model's own kernels, one by one (all pointers 16-byte aligned, C a multiple of 4).
+ * r3m_text_embed: y[b,t,:] = LayerNorm(word[clamp(ids[b,t], 0, vocab - 1)] + pos[t]); word [vocab][C], pos [>= T][C].
+ * r3m_layernorm_fwd: y = LayerNorm(x (+ residual, may be NULL)) over the last dimension of [rows][C], biased variance, two passes (a
+ *   row of equal values has variance exactly 0); the model uses eps = 1e-12. y may alias x or residual.
+ * r3m_bias_gelu: x = gelu(x + bias[column]) in place on [rows][C], the exact erf form (HuggingFace "gelu").
+ * r3m_attention_fwd: qkv [B*T][3 dim] (q | k | v, dim = n_heads * head_dim, head h at columns h * head_dim) -> out [B*T][dim] =
+ *   softmax(q k^T / sqrt(head_dim), keys with mask == 0 scored as the most negative finite float) v, per sentence and head. A row
+ *   whose keys are all masked comes out as the plain average of v, not NaN. One workgroup per (sentence, head), K and V in LDS.
+ * r3m_text_pool: feats [B][C] from hidden [B][T][C], pool as above; B <= 65535. */
+int r3m_text_embed(const int* ids, const float* word, const float* pos, const float* gamma, const float* beta, float* y, int B, int T,
+                   int C, int vocab, float eps, r3m_stream_t stream);
+int r3m_layernorm_fwd(const float* x, const float* residual, const float* gamma, const float* beta, float* y, long long rows, int C,
+                      float eps, r3m_stream_t stream);
+int r3m_bias_gelu(float* x, const float* bias, long long rows, int C, r3m_stream_t stream);
+int r3m_attention_fwd(const float* qkv, const int* mask, float* out, int B, int T, int n_heads, int head_dim, r3m_stream_t stream);
+int r3m_text_pool(const float* hidden, const int* mask, float* feats, int B, int T, int C, int pool, r3m_stream_t stream);
+
 /* ---------------- objective (r3m/trainer.py:39-152, R3M.sim models_r3m.py:102-107) ----------------------------
  * alle [B,5,D] (e0, eg, es0, es1, es2 per clip); perm/iperm [6][B] int32: the reference's torch.randperm draws in
  * order (es0-perm, es2-perm) x 3 (trainer.py:136-137) and their inverses. Writes d(full_loss)/d(alle) to dalle

@@ -137,6 +137,16 @@ SIGNATURES = {
     "r3m_langrew_call_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "r3m_langrew_call_forward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_f]),
     "r3m_langrew_call_backward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_text_num_params": (c_ll, [C.POINTER(c_i)]),
+    "r3m_text_num_tensors": (c_i, [C.POINTER(c_i)]),
+    "r3m_text_tensor_info": (c_i, [C.POINTER(c_i), c_i, C.c_char_p, c_i, C.POINTER(c_ll), C.POINTER(c_ll), C.POINTER(c_i), C.POINTER(c_i)]),
+    "r3m_text_workspace_bytes": (c_sz, [C.POINTER(c_i), c_i, c_i]),
+    "r3m_text_forward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, C.POINTER(c_i), c_i, c_f]),
+    "r3m_text_embed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_fl, c_f]),
+    "r3m_layernorm_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_ll, c_i, c_fl, c_f]),
+    "r3m_bias_gelu": (c_i, [c_f, c_f, c_ll, c_i, c_f]),
+    "r3m_attention_fwd": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_text_pool": (c_i, [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "r3m_loss_workspace_bytes": (c_sz, [c_i]),
     "r3m_loss_tcn_lp": (c_i, [c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_fl, c_fl, c_fl, c_f]),
     "r3m_loss_lang_infonce": (c_i, [c_f, c_f, c_f, c_f, c_sz, c_i, c_fl, c_f]),

@@ -7,9 +7,10 @@ What changes is the schedule, not the math: the reference calls get_reward 15 ti
 time on the same sentences (trainer.py:72-92). Here the sentence features are computed once per step and the 15 MLP
 evaluations are one batched [15B, 2D+768] pass in csrc/lang.hip (`LanguageReward.batched_scores`).
 
-DistilBERT itself is a frozen feature extractor outside the kernel scope: LangEncoder accepts
-precomputed [B,768] features (BASELINE config 3: "frozen DistilBERT text feats"), a sentence->feature cache, or, when the
-HuggingFace weights are on disk, runs the model once per batch with the reference's mean-over-all-positions pooling.
+DistilBERT itself is a frozen feature extractor: LangEncoder accepts precomputed [B,768] features (BASELINE config 3:
+"frozen DistilBERT text feats"), a sentence->feature cache, or, when the HuggingFace weights are on disk, runs the model once
+per batch with the reference's mean-over-all-positions pooling — through transformers in eager torch by default, or on the
+HIP path (use_native(), native=True: r3m_amd/text.py, csrc/text.hip).
 """
 import math
 
@@ -29,14 +30,16 @@ class LangEncoder(nn.Module):
     Features are computed ONCE per call; Trainer.update calls this once per step where the reference re-runs DistilBERT in each
     of its 15 get_reward calls on the same sentences (trainer.py:72-92)."""
 
-    def __init__(self, device, finetune=False, scratch=False, mask_padding=False):
+    def __init__(self, device, finetune=False, scratch=False, mask_padding=False, native=False):
         super().__init__()
+        self.native = bool(native)    # the locally found HuggingFace weights are converted to the HIP text model (r3m_amd/text.py)
         self.device = device
         self.modelname = "distilbert-base-uncased"
         self.lang_size = 768
         self.mask_padding = bool(mask_padding)
         self.feature_cache = {}       # sentence -> [768] tensor (offline-precomputed features)
-        self._hf = None               # (tokenizer, model): use_backend(), or loaded lazily from local files only
+        self._hf = None               # (tokenizer, model): use_backend() / use_native(), or loaded lazily from local files only
+        self._pooled = False          # the model of _hf is a HipDistilBert asked for pooled features (use_native, native=True)
         self.encoder_calls = 0        # transformer passes so far (tests: once per step, none on cache hits)
 
     def use_backend(self, tokenizer, model):
@@ -46,7 +49,23 @@ class LangEncoder(nn.Module):
         model = model.to(self.device).eval()
         for p in model.parameters():
             p.requires_grad_(False)
-        self._hf = (tokenizer, model)
+        self._hf, self._pooled = (tokenizer, model), False
+        return self
+
+    def use_native(self, tokenizer, model_or_state_dict, n_heads=None):
+        """Run the text model on the HIP path (r3m_amd/text.py, csrc/text.hip): encode() becomes one HipDistilBert.features call.
+        model_or_state_dict: a transformers DistilBertModel, a HipDistilBert, or a state dict under HuggingFace's names (then n_heads
+        is required: no tensor shape carries it). Like the `_hf` tuple the module stays OFF the module tree: state_dict(),
+        parameters() and the optimizer's owners are what they were."""
+        from .text import HipDistilBert
+        m = model_or_state_dict
+        if isinstance(m, dict):
+            if n_heads is None:
+                raise ValueError("LangEncoder.use_native: a state dict needs n_heads")
+            m = HipDistilBert.from_state_dict(m, n_heads, self.device)
+        elif not isinstance(m, HipDistilBert):
+            m = HipDistilBert.from_hf(m, self.device)
+        self._hf, self._pooled = (tokenizer, m.to(self.device)), True
         return self
 
     def train(self, mode=True):       # the frozen text model stays in eval mode whatever the step does (trainer.py:31)
@@ -60,6 +79,9 @@ class LangEncoder(nn.Module):
         tok, model = self._load_hf()
         with torch.no_grad():
             enc = tok(list(langs), return_tensors="pt", padding=True)
+            if self._pooled:                         # HipDistilBert: the transformer and the pooling in one native call
+                self.encoder_calls += 1
+                return model.features(enc["input_ids"], enc["attention_mask"], mask_padding=self.mask_padding)
             am = enc["attention_mask"].to(self.device)
             out = model(enc["input_ids"].to(self.device), attention_mask=am).last_hidden_state
             self.encoder_calls += 1
@@ -93,6 +115,9 @@ class LangEncoder(nn.Module):
                     f"({self.modelname}) are not available locally ({type(e).__name__}). Pass precomputed [B,768] "
                     "features instead of strings, or fill LangEncoder.feature_cache.") from e
             model.eval()
+            if self.native:                          # convert the loaded weights, drop the HuggingFace model
+                from .text import HipDistilBert
+                model, self._pooled = HipDistilBert.from_hf(model, self.device), True
             self._hf = (tok, model)
         return self._hf
 

@@ -34,7 +34,7 @@ class _NormalizeSpec(nn.Module):
 
 class R3M(nn.Module):
     def __init__(self, device, lr, hidden_dim, size=34, l2weight=1.0, l1weight=1.0, langweight=1.0, tcnweight=0.0,
-                 l2dist=True, bs=16, precision="fp32", max_live_forwards=1, weight_decay=0.0, grad_clip=0.0):
+                 l2dist=True, bs=16, precision="fp32", max_live_forwards=1, weight_decay=0.0, grad_clip=0.0, native_text=False):
         super().__init__()
         self.device = device
         self.use_tb = False
@@ -62,7 +62,7 @@ class R3M(nn.Module):
 
         if self.langweight > 0.0:
             from .models_language import LangEncoder, LanguageReward
-            self.lang_enc = LangEncoder(self.device, 0, 0)
+            self.lang_enc = LangEncoder(self.device, 0, 0, native=native_text)   # native_text: DistilBERT on the HIP path (r3m_amd/text.py)
             self.lang_rew = LanguageReward(None, self.outdim, hidden_dim, self.lang_enc.lang_size, simfunc=self.sim, precision=precision)
             owners.append(self.lang_rew)
 
