@@ -525,7 +525,8 @@ int r3m_loss_finalize(void* workspace, size_t workspace_bytes, int B, int have_l
                       float l1weight, float tcnweight, float langweight, r3m_stream_t stream);
 
 /* ---------------- optimizer: torch.optim.Adam(params, lr) defaults (models_r3m.py:76; trainer.py:156-158) -------
- * one pass over the flat buffers; step counts from 1; grad_scale multiplies g on the fly (1/world_size for SUM all-reduce) */
+ * one pass over the flat buffers; step counts from 1; grad_scale multiplies g on the fly (1/world_size for SUM all-reduce).
+ * n is a positive multiple of 4: n == 0 is refused on the host like any other bad n (only the ranged forms may have nothing to do) */
 int r3m_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long long n, double lr, double beta1,
                   double beta2, double eps, long long step, float grad_scale, r3m_stream_t stream);
 /* torch.optim.SGD on the same flat buffers (momentum / dampening / weight_decay / nesterov as torch defines them; momentum_buf may

@@ -3,21 +3,99 @@
 // /root/reference/r3m/models/models_r3m.py:76 and steps at /root/reference/r3m/trainer.py:156-158
 // (betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad). One HBM pass: read p,g,m,v - write p,m,v.
 //
-// The *_ranges forms step only some [offset, count) ranges of the buffer, each with its own step count (partial-freeze
-// fine-tuning: torch.optim.Adam skips parameters without a gradient and keeps `step` per parameter). Both forms run the same
-// element loop (adam_span / sgd_span), so a range gets bit for bit what the whole-buffer kernel gives the same elements.
-//
-// The *_groups forms are the ranged steps of fine-tuning: a learning rate and a weight decay per range (parameter groups, AdamW / L2
-// decay) and an optional clip coefficient read from device memory; sqnorm_* and clip_coef_kernel form that coefficient
-// (torch.nn.utils.clip_grad_norm_) as a deterministic fp64 sum over ranges. All of it at the end of this file.
+// One step kernel and one launcher per optimizer (adam_step_kernel / launch_adam, sgd_step_kernel / launch_sgd) serve all three forms
+// of the C API. The kernel steps up to OPT_MAX_RANGES sorted, disjoint [offset, count) ranges of the buffer, each with its own step
+// count, learning rate and weight decay (StepTable), and an optional clip coefficient read from device memory:
+//   *_step_groups  the general form: parameter groups (AdamW / L2 decay, lr per group) after torch.nn.utils.clip_grad_norm_
+//   *_step_ranges  one lr for all ranges, Adam without decay, no coefficient (partial-freeze fine-tuning: torch.optim.Adam skips
+//                  parameters without a gradient and keeps `step` per parameter)
+//   *_step         the same with the one range [0, n)
+// A block picks the element loop of its range (adam_span_t<COEF, DECAY> / sgd_span_t<COEF>), so a range gets bit for bit the same
+// result through every form that describes it. One exception to "one kernel", kept for its speed: a call with a single range and
+// nothing for a table to say (no coefficient, Adam: no decay) -- the step of every run that freezes nothing -- goes to
+// adam_whole_kernel / sgd_whole_kernel, eight lines around the same element loop. sqnorm_* and clip_coef_kernel at the end of this
+// file form the clip coefficient as a deterministic fp64 sum over ranges.
 #include "common.h"
-#include <cstring>
 
 namespace r3m {
 
+// ---- the range tables ---------------------------------------------------------------------------------------------
+// Up to OPT_MAX_RANGES ranges per launch. The table travels BY VALUE in the kernel arguments (no device table, no allocation, no
+// upload). Range r owns blocks [first_block[r], first_block[r + 1]); a block finds its range by scanning first_block, which is uniform
+// over the block (scalar loads from the argument segment), then runs the element loop on that range with its own grid stride.
+constexpr int OPT_MAX_RANGES = 64;
+struct RangeTable {                   // where the ranges lie: all that the gradient norm needs
+  int first_block[OPT_MAX_RANGES + 1];
+  int n;
+  long long off4[OPT_MAX_RANGES];     // offset / 4
+  long long n4[OPT_MAX_RANGES];       // count / 4
+};
+struct StepTable {                    // and how each range steps
+  RangeTable r;
+  float a[OPT_MAX_RANGES];            // Adam: -lr_r / bias_correction1 ; SGD: 1.f on the range's first step
+  float b[OPT_MAX_RANGES];            // Adam: sqrt(bias_correction2) ; SGD: lr_r
+  float wd[OPT_MAX_RANGES];           // Adam L2 and SGD: weight_decay_r ; AdamW: (float)(1 - lr_r * weight_decay_r), 1.f = no decay
+};
+static_assert(sizeof(StepTable) == sizeof(RangeTable) + 3 * 256 && sizeof(StepTable) + 64 <= 4096,
+              "the range table travels in the kernel arguments (4 KiB)");
+
+__device__ __forceinline__ int range_of_block(const RangeTable& t) {
+  int r = 0;
+  while (r + 1 < t.n && (int)blockIdx.x >= t.first_block[r + 1]) ++r;
+  return r;
+}
+
+static int opt_grid(long long n4) {
+  int grid = ceil_div(n4, 256);
+  return grid > 256 * 16 ? 256 * 16 : grid;
+}
+
+// host checks shared by both optimizers and the gradient norm (no step counts there); nothing is launched when one fails
+static int check_ranges(const char* what, const long long* off, const long long* count, const long long* step, int n_ranges,
+                        bool with_step = true) {
+  R3M_REQUIRE(n_ranges >= 0, "%s: n_ranges=%d", what, n_ranges);
+  R3M_REQUIRE(n_ranges == 0 || (off && count && (step || !with_step)), "%s: null range arrays", what);
+  long long end = 0;
+  for (int i = 0; i < n_ranges; ++i) {
+    R3M_REQUIRE(off[i] >= 0 && count[i] >= 0 && off[i] % 4 == 0 && count[i] % 4 == 0,
+                "%s: range %d = [%lld, +%lld): offsets and counts must be non-negative multiples of 4", what, i, off[i], count[i]);
+    R3M_REQUIRE(off[i] >= end, "%s: range %d starts at %lld, before the end %lld of the range before it (ranges must be sorted and disjoint)",
+                what, i, off[i], end);
+    R3M_REQUIRE(!with_step || step[i] >= 1, "%s: range %d has step=%lld, must be >= 1", what, i, step[i]);
+    end = off[i] + count[i];
+  }
+  return 0;
+}
+// the same, and the per-range learning rates and weight decays where the call brings them (a NaN fails `>= 0`)
+static int check_step_ranges(const char* what, const StepRanges& r) {
+  if (int e = check_ranges(what, r.off, r.count, r.step, r.n)) return e;
+  for (int i = 0; i < r.n; ++i) {
+    R3M_REQUIRE(!r.lrs || r.lrs[i] >= 0.0, "%s: range %d has lr=%g, must be >= 0", what, i, r.lrs[i]);
+    R3M_REQUIRE(!r.wds || r.wds[i] >= 0.0, "%s: range %d has weight_decay=%g, must be >= 0", what, i, r.wds[i]);
+  }
+  return 0;
+}
+// the next up-to-OPT_MAX_RANGES non-empty ranges from *i on -> t, which comes zeroed (offsets, counts, block shares; src[r]: where
+// table entry r came from); returns the grid
+static int fill_ranges(RangeTable& t, const long long* off, const long long* count, int n_ranges, int* i, int* src) {
+  int blocks = 0;
+  for (; *i < n_ranges && t.n < OPT_MAX_RANGES; ++*i) {
+    if (count[*i] == 0) continue;
+    const int r = t.n++;
+    src[r] = *i;
+    t.off4[r] = off[*i] / 4;
+    t.n4[r] = count[*i] / 4;
+    t.first_block[r] = blocks;
+    blocks += opt_grid(t.n4[r]);
+  }
+  for (int r = t.n; r <= OPT_MAX_RANGES; ++r) t.first_block[r] = blocks;
+  return blocks;
+}
+
+// ---- Adam ---------------------------------------------------------------------------------------------------------
 // f32x4 groups i, i + stride, ... < n4 of the buffers.
 // COEF: the gradient is also multiplied by `coef` (gradient clipping). DECAY 1: gr += wd * p (torch.optim.Adam(weight_decay=)),
-// DECAY 2: p *= wd, wd = (float)(1 - lr * weight_decay) (AdamW), before the update. <false, 0> is the plain step: adam_span below.
+// DECAY 2: p *= wd, wd = (float)(1 - lr * weight_decay) (AdamW), before the update. <false, 0> is the plain step.
 template <bool COEF, int DECAY>
 __device__ __forceinline__ void adam_span_t(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                             long long i, long long stride, long long n4, float beta2, float one_minus_beta1,
@@ -46,19 +124,45 @@ __device__ __forceinline__ void adam_span_t(float* __restrict__ p, const float* 
     *reinterpret_cast<f32x4*>(v + i * 4) = vv;
   }
 }
-__device__ __forceinline__ void adam_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                          long long i, long long stride, long long n4, float beta2, float one_minus_beta1,
-                                          float one_minus_beta2, float neg_step_size, float bc2_sqrt, float eps, float grad_scale) {
-  adam_span_t<false, 0>(p, g, m, v, i, stride, n4, beta2, one_minus_beta1, one_minus_beta2, neg_step_size, bc2_sqrt, eps, grad_scale, 0.f, 0.f);
+
+template <bool COEF>
+__device__ __forceinline__ void adam_step_block(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                float* __restrict__ v, const StepTable& t, float beta2, float one_minus_beta1,
+                                                float one_minus_beta2, float eps, float grad_scale, float coef, int decoupled) {
+  const int r = range_of_block(t.r);
+  const long long o = t.r.off4[r] * 4;
+  const int blocks = t.r.first_block[r + 1] - t.r.first_block[r];
+  const long long i = (long long)(blockIdx.x - t.r.first_block[r]) * 256 + threadIdx.x, stride = (long long)blocks * 256;
+  const float wd = t.wd[r];
+  if (decoupled ? wd == 1.f : wd == 0.f)
+    adam_span_t<COEF, 0>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.a[r], t.b[r], eps,
+                         grad_scale, coef, 0.f);
+  else if (decoupled)
+    adam_span_t<COEF, 2>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.a[r], t.b[r], eps,
+                         grad_scale, coef, wd);
+  else
+    adam_span_t<COEF, 1>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.a[r], t.b[r], eps,
+                         grad_scale, coef, wd);
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, long long n4, float beta1, float beta2,
-                                                    float one_minus_beta1, float one_minus_beta2, float neg_step_size,
-                                                    float bc2_sqrt, float eps, float grad_scale) {
-  adam_span(p, g, m, v, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, n4, beta2, one_minus_beta1, one_minus_beta2,
-            neg_step_size, bc2_sqrt, eps, grad_scale);
-  (void)beta1;
+__global__ __launch_bounds__(256) void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, const StepTable t, float beta2, float one_minus_beta1,
+                                                         float one_minus_beta2, float eps, float grad_scale,
+                                                         const float* __restrict__ coef, int decoupled) {
+  if (coef)       // the same address for every lane: one scalar load
+    adam_step_block<true>(p, g, m, v, t, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, *coef, decoupled);
+  else
+    adam_step_block<false>(p, g, m, v, t, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, 0.f, decoupled);
+}
+
+// One range without decay or coefficient, the step of every run that freezes nothing: the table has nothing to say, and the plain
+// grid-stride launch spares each block the look-up (2 % on ResNet-50's buffer: profiles/optim_groups.txt). The same element loop.
+__global__ __launch_bounds__(256) void adam_whole_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, long long n4, float beta2, float one_minus_beta1,
+                                                          float one_minus_beta2, float neg_step_size, float bc2_sqrt, float eps,
+                                                          float grad_scale) {
+  adam_span_t<false, 0>(p, g, m, v, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, n4, beta2, one_minus_beta1,
+                        one_minus_beta2, neg_step_size, bc2_sqrt, eps, grad_scale, 0.f, 0.f);
 }
 
 // bias corrections of one step count, formed in double (torch.optim.Adam's python scalars)
@@ -68,108 +172,42 @@ static void adam_bias_corrections(double lr, double beta1, double beta2, long lo
   *neg_step = (float)(-(lr / bc1));
   *bc2s = (float)sqrt(bc2);
 }
-static int opt_grid(long long n4) {
-  int grid = ceil_div(n4, 256);
-  return grid > 256 * 16 ? 256 * 16 : grid;
-}
 
-int launch_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2, double eps,
-                long long step, float grad_scale, hipStream_t s) {
-  R3M_REQUIRE(n % 4 == 0, "adam: n=%lld must be a multiple of 4", n);
-  R3M_REQUIRE(step >= 1, "adam: step=%lld must be >= 1", step);
-  float neg_step, bc2s;
-  adam_bias_corrections(lr, beta1, beta2, step, &neg_step, &bc2s);
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(adam_kernel, dim3(opt_grid(n4)), dim3(256), 0, s, p, g, m, v, n4, (float)beta1, (float)beta2, (float)(1.0 - beta1),
-                     (float)(1.0 - beta2), neg_step, bc2s, (float)eps, grad_scale);
-  return check_launch("adam");
-}
-
-// ---- ranged steps ---------------------------------------------------------------------------------------------
-// Up to OPT_MAX_RANGES ranges per launch. The table travels BY VALUE in the kernel arguments (no device table, no allocation, no
-// upload). Range r owns blocks [first_block[r], first_block[r + 1]); a block finds its range by scanning first_block, which is uniform
-// over the block (scalar loads from the argument segment), then runs the whole-buffer loop on that range with its own grid stride.
-constexpr int OPT_MAX_RANGES = 64;
-struct RangeTable {
-  int first_block[OPT_MAX_RANGES + 1];
-  int n;
-  long long off4[OPT_MAX_RANGES];     // offset / 4
-  long long n4[OPT_MAX_RANGES];       // count / 4
-  float a[OPT_MAX_RANGES];            // Adam: -lr / bias_correction1 ; SGD: 1.f on the range's first step
-  float b[OPT_MAX_RANGES];            // Adam: sqrt(bias_correction2)
-};
-
-__device__ __forceinline__ int range_of_block(const RangeTable& t) {
-  int r = 0;
-  while (r + 1 < t.n && (int)blockIdx.x >= t.first_block[r + 1]) ++r;
-  return r;
-}
-
-__global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, const RangeTable t, float beta2, float one_minus_beta1,
-                                                           float one_minus_beta2, float eps, float grad_scale) {
-  const int r = range_of_block(t);
-  const long long o = t.off4[r] * 4;
-  const int blocks = t.first_block[r + 1] - t.first_block[r];
-  adam_span(p + o, g + o, m + o, v + o, (long long)(blockIdx.x - t.first_block[r]) * 256 + threadIdx.x, (long long)blocks * 256, t.n4[r], beta2,
-            one_minus_beta1, one_minus_beta2, t.a[r], t.b[r], eps, grad_scale);
-}
-
-// host checks shared by both optimizers; nothing is launched when one fails
-// (with_step = false: ranges without step counts, the gradient norm)
-static int check_ranges(const char* what, const long long* off, const long long* count, const long long* step, int n_ranges,
-                        bool with_step = true) {
-  R3M_REQUIRE(n_ranges >= 0, "%s: n_ranges=%d", what, n_ranges);
-  R3M_REQUIRE(n_ranges == 0 || (off && count && (step || !with_step)), "%s: null range arrays", what);
-  long long end = 0;
-  for (int i = 0; i < n_ranges; ++i) {
-    R3M_REQUIRE(off[i] >= 0 && count[i] >= 0 && off[i] % 4 == 0 && count[i] % 4 == 0,
-                "%s: range %d = [%lld, +%lld): offsets and counts must be non-negative multiples of 4", what, i, off[i], count[i]);
-    R3M_REQUIRE(off[i] >= end, "%s: range %d starts at %lld, before the end %lld of the range before it (ranges must be sorted and disjoint)",
-                what, i, off[i], end);
-    R3M_REQUIRE(!with_step || step[i] >= 1, "%s: range %d has step=%lld, must be >= 1", what, i, step[i]);
-    end = off[i] + count[i];
+int launch_adam(const char* what, float* p, const float* g, float* m, float* v, const StepRanges& r, double beta1, double beta2, double eps,
+                int decoupled, float grad_scale, const float* clip_coef, hipStream_t s) {
+  if (int e = check_step_ranges(what, r)) return e;
+  if (r.n == 1 && r.count[0] > 0 && !clip_coef && (r.wds ? r.wds[0] : r.wd) == 0.0) {
+    const long long o = r.off[0], n4 = r.count[0] / 4;
+    float neg_step, bc2s;
+    adam_bias_corrections(r.lrs ? r.lrs[0] : r.lr, beta1, beta2, r.step[0], &neg_step, &bc2s);
+    hipLaunchKernelGGL(adam_whole_kernel, dim3(opt_grid(n4)), dim3(256), 0, s, p + o, g + o, m + o, v + o, n4, (float)beta2,
+                       (float)(1.0 - beta1), (float)(1.0 - beta2), neg_step, bc2s, (float)eps, grad_scale);
+    return check_launch(what);
   }
-  return 0;
-}
-// the next up-to-OPT_MAX_RANGES non-empty ranges from *i on -> t (offsets, counts, block shares); returns the grid
-static int fill_ranges(RangeTable& t, const long long* off, const long long* count, int n_ranges, int* i, int* src) {
-  memset(&t, 0, sizeof t);
-  int blocks = 0;
-  for (; *i < n_ranges && t.n < OPT_MAX_RANGES; ++*i) {
-    if (count[*i] == 0) continue;
-    const int r = t.n++;
-    src[r] = *i;
-    t.off4[r] = off[*i] / 4;
-    t.n4[r] = count[*i] / 4;
-    t.first_block[r] = blocks;
-    blocks += opt_grid(t.n4[r]);
-  }
-  for (int r = t.n; r <= OPT_MAX_RANGES; ++r) t.first_block[r] = blocks;
-  return blocks;
-}
-
-int launch_adam_ranges(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
-                       int n_ranges, double lr, double beta1, double beta2, double eps, float grad_scale, hipStream_t s) {
-  if (int e = check_ranges("adam_ranges", off, count, step, n_ranges)) return e;
-  for (int i = 0; i < n_ranges;) {
-    RangeTable t;
+  for (int i = 0; i < r.n;) {
+    StepTable t = {};
     int src[OPT_MAX_RANGES];
-    const int grid = fill_ranges(t, off, count, n_ranges, &i, src);
+    const int grid = fill_ranges(t.r, r.off, r.count, r.n, &i, src);
     if (!grid) break;
-    for (int r = 0; r < t.n; ++r) adam_bias_corrections(lr, beta1, beta2, step[src[r]], &t.a[r], &t.b[r]);
-    hipLaunchKernelGGL(adam_ranges_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, t, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
-                       (float)eps, grad_scale);
-    if (int e = check_launch("adam_ranges")) return e;
+    for (int k = 0; k < t.r.n; ++k) {
+      const double lr = r.lrs ? r.lrs[src[k]] : r.lr, wd = r.wds ? r.wds[src[k]] : r.wd;
+      adam_bias_corrections(lr, beta1, beta2, r.step[src[k]], &t.a[k], &t.b[k]);
+      // AdamW: param.mul_(1 - lr * weight_decay), the factor a python (double) scalar
+      t.wd[k] = decoupled ? (wd == 0.0 ? 1.f : (float)(1.0 - lr * wd)) : (float)wd;
+    }
+    hipLaunchKernelGGL(adam_step_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, t, (float)beta2, (float)(1.0 - beta1),
+                       (float)(1.0 - beta2), (float)eps, grad_scale, clip_coef, decoupled ? 1 : 0);
+    if (int e = check_launch(what)) return e;
   }
   return 0;
 }
 
+// ---- SGD ----------------------------------------------------------------------------------------------------------
 // Fused SGD over a flat buffer, torch.optim.SGD semantics (momentum, dampening, weight decay, Nesterov):
 //   g' = g*grad_scale + wd*p ; buf = (first step) g' : momentum*buf + (1-dampening)*g' ; d = nesterov ? g' + momentum*buf : buf ; p -= lr*d
 // The reference trains with Adam only (models_r3m.py:76); BASELINE.json's north_star names "the SGD/Adam step", so the plain
 // optimizer is provided on the same flat-buffer layout (one HBM pass: read p, g, buf - write p, buf).
-// COEF: the gradient is also multiplied by `coef` (gradient clipping); <false> is the plain step: sgd_span below.
+// COEF: the gradient is also multiplied by `coef` (gradient clipping); <false> is the plain step.
 template <bool COEF>
 __device__ __forceinline__ void sgd_span_t(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long i,
                                            long long stride, long long n4, float lr, float momentum, float one_minus_damp, float wd,
@@ -195,177 +233,57 @@ __device__ __forceinline__ void sgd_span_t(float* __restrict__ p, const float* _
     if (buf) *reinterpret_cast<f32x4*>(buf + i * 4) = bb;
   }
 }
-__device__ __forceinline__ void sgd_span(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long i,
-                                         long long stride, long long n4, float lr, float momentum, float one_minus_damp, float wd,
-                                         int nesterov, int first, float grad_scale) {
-  sgd_span_t<false>(p, g, buf, i, stride, n4, lr, momentum, one_minus_damp, wd, nesterov, first, grad_scale, 0.f);
-}
 
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long long n4,
-                                                   float lr, float momentum, float one_minus_damp, float wd, int nesterov, int first,
-                                                   float grad_scale) {
-  sgd_span(p, g, buf, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, n4, lr, momentum, one_minus_damp, wd, nesterov,
-           first, grad_scale);
-}
-
-__global__ __launch_bounds__(256) void sgd_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                          const RangeTable t, float lr, float momentum, float one_minus_damp, float wd,
-                                                          int nesterov, float grad_scale) {
-  const int r = range_of_block(t);
-  const long long o = t.off4[r] * 4;
-  const int blocks = t.first_block[r + 1] - t.first_block[r];
-  sgd_span(p + o, g + o, buf ? buf + o : nullptr, (long long)(blockIdx.x - t.first_block[r]) * 256 + threadIdx.x, (long long)blocks * 256,
-           t.n4[r], lr, momentum, one_minus_damp, wd, nesterov, t.a[r] != 0.f, grad_scale);
-}
-
-static int check_sgd(double momentum, double dampening, int nesterov, const float* momentum_buf) {
-  R3M_REQUIRE(momentum == 0.0 || momentum_buf, "sgd: momentum needs a momentum buffer");
-  R3M_REQUIRE(!nesterov || (momentum > 0.0 && dampening == 0.0), "sgd: nesterov needs momentum > 0 and dampening = 0");
-  return 0;
-}
-
-int launch_sgd(float* p, const float* g, float* momentum_buf, long long n, double lr, double momentum, double dampening,
-               double weight_decay, int nesterov, long long step, float grad_scale, hipStream_t s) {
-  R3M_REQUIRE(n % 4 == 0, "sgd: n=%lld must be a multiple of 4", n);
-  R3M_REQUIRE(step >= 1, "sgd: step=%lld must be >= 1", step);
-  if (int e = check_sgd(momentum, dampening, nesterov, momentum_buf)) return e;
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(sgd_kernel, dim3(opt_grid(n4)), dim3(256), 0, s, p, g, momentum != 0.0 ? momentum_buf : nullptr, n4, (float)lr,
-                     (float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov, step == 1 ? 1 : 0, grad_scale);
-  return check_launch("sgd");
-}
-
-int launch_sgd_ranges(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
-                      int n_ranges, double lr, double momentum, double dampening, double weight_decay, int nesterov, float grad_scale,
-                      hipStream_t s) {
-  if (int e = check_ranges("sgd_ranges", off, count, step, n_ranges)) return e;
-  if (int e = check_sgd(momentum, dampening, nesterov, momentum_buf)) return e;
-  for (int i = 0; i < n_ranges;) {
-    RangeTable t;
-    int src[OPT_MAX_RANGES];
-    const int grid = fill_ranges(t, off, count, n_ranges, &i, src);
-    if (!grid) break;
-    for (int r = 0; r < t.n; ++r) t.a[r] = step[src[r]] == 1 ? 1.f : 0.f;
-    hipLaunchKernelGGL(sgd_ranges_kernel, dim3(grid), dim3(256), 0, s, p, g, momentum != 0.0 ? momentum_buf : nullptr, t, (float)lr,
-                       (float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov, grad_scale);
-    if (int e = check_launch("sgd_ranges")) return e;
-  }
-  return 0;
-}
-
-// ---- grouped steps: a learning rate and a weight decay per range, and an optional clip coefficient -----------------------------
-// The fine-tuning forms of the ranged steps (parameter groups: torch.optim.AdamW / Adam(weight_decay=) / SGD with per-group lr and
-// weight_decay, after torch.nn.utils.clip_grad_norm_). The table gains one float per range; a block picks the element loop of its
-// range: a range without decay and a launch without coefficient run adam_span / sgd_span themselves, so they give the bits of
-// r3m_adam_step_ranges / r3m_sgd_step_ranges.
-struct GroupTable {
-  RangeTable r;                       // Adam: a = -lr_r / bias_correction1, b = sqrt(bias_correction2) ; SGD: a = first step, b = lr_r
-  float wd[OPT_MAX_RANGES];           // Adam L2 and SGD: weight_decay_r ; AdamW: (float)(1 - lr_r * weight_decay_r), 1.f = no decay
-};
-static_assert(sizeof(GroupTable) == sizeof(RangeTable) + 256 && sizeof(GroupTable) + 64 <= 4096,
-              "the range table travels in the kernel arguments (4 KiB)");
-
-template <bool COEF>
-__device__ __forceinline__ void adam_group_block(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                 float* __restrict__ v, const GroupTable& t, float beta2, float one_minus_beta1,
-                                                 float one_minus_beta2, float eps, float grad_scale, float coef, int decoupled) {
-  const int r = range_of_block(t.r);
-  const long long o = t.r.off4[r] * 4;
-  const int blocks = t.r.first_block[r + 1] - t.r.first_block[r];
-  const long long i = (long long)(blockIdx.x - t.r.first_block[r]) * 256 + threadIdx.x, stride = (long long)blocks * 256;
-  const float wd = t.wd[r];
-  if (decoupled ? wd == 1.f : wd == 0.f)
-    adam_span_t<COEF, 0>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.r.a[r], t.r.b[r], eps,
-                         grad_scale, coef, 0.f);
-  else if (decoupled)
-    adam_span_t<COEF, 2>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.r.a[r], t.r.b[r], eps,
-                         grad_scale, coef, wd);
-  else
-    adam_span_t<COEF, 1>(p + o, g + o, m + o, v + o, i, stride, t.r.n4[r], beta2, one_minus_beta1, one_minus_beta2, t.r.a[r], t.r.b[r], eps,
-                         grad_scale, coef, wd);
-}
-
-__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, const GroupTable t, float beta2, float one_minus_beta1,
-                                                           float one_minus_beta2, float eps, float grad_scale,
-                                                           const float* __restrict__ coef, int decoupled) {
-  if (coef)       // the same address for every lane: one scalar load
-    adam_group_block<true>(p, g, m, v, t, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, *coef, decoupled);
-  else
-    adam_group_block<false>(p, g, m, v, t, beta2, one_minus_beta1, one_minus_beta2, eps, grad_scale, 0.f, decoupled);
-}
-
-__global__ __launch_bounds__(256) void sgd_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
-                                                          const GroupTable t, float momentum, float one_minus_damp, int nesterov,
-                                                          float grad_scale, const float* __restrict__ coef) {
+__global__ __launch_bounds__(256) void sgd_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                        const StepTable t, float momentum, float one_minus_damp, int nesterov,
+                                                        float grad_scale, const float* __restrict__ coef) {
   const int r = range_of_block(t.r);
   const long long o = t.r.off4[r] * 4;
   const int blocks = t.r.first_block[r + 1] - t.r.first_block[r];
   const long long i = (long long)(blockIdx.x - t.r.first_block[r]) * 256 + threadIdx.x, stride = (long long)blocks * 256;
   float* b = buf ? buf + o : nullptr;
   if (coef)
-    sgd_span_t<true>(p + o, g + o, b, i, stride, t.r.n4[r], t.r.b[r], momentum, one_minus_damp, t.wd[r], nesterov, t.r.a[r] != 0.f, grad_scale,
+    sgd_span_t<true>(p + o, g + o, b, i, stride, t.r.n4[r], t.b[r], momentum, one_minus_damp, t.wd[r], nesterov, t.a[r] != 0.f, grad_scale,
                      *coef);
   else
-    sgd_span(p + o, g + o, b, i, stride, t.r.n4[r], t.r.b[r], momentum, one_minus_damp, t.wd[r], nesterov, t.r.a[r] != 0.f, grad_scale);
+    sgd_span_t<false>(p + o, g + o, b, i, stride, t.r.n4[r], t.b[r], momentum, one_minus_damp, t.wd[r], nesterov, t.a[r] != 0.f, grad_scale,
+                      0.f);
 }
 
-static int check_groups(const char* what, const long long* off, const long long* count, const long long* step, const double* lr,
-                        const double* weight_decay, int n_ranges) {
-  if (int e = check_ranges(what, off, count, step, n_ranges)) return e;
-  R3M_REQUIRE(n_ranges == 0 || (lr && weight_decay), "%s: null lr / weight_decay arrays", what);
-  for (int i = 0; i < n_ranges; ++i) {
-    R3M_REQUIRE(lr[i] >= 0.0, "%s: range %d has lr=%g, must be >= 0", what, i, lr[i]);
-    R3M_REQUIRE(weight_decay[i] >= 0.0, "%s: range %d has weight_decay=%g, must be >= 0", what, i, weight_decay[i]);
+// one range without coefficient: as adam_whole_kernel
+__global__ __launch_bounds__(256) void sgd_whole_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                         long long n4, float lr, float momentum, float one_minus_damp, float wd,
+                                                         int nesterov, int first, float grad_scale) {
+  sgd_span_t<false>(p, g, buf, (long long)blockIdx.x * 256 + threadIdx.x, (long long)gridDim.x * 256, n4, lr, momentum, one_minus_damp, wd,
+                    nesterov, first, grad_scale, 0.f);
+}
+
+int launch_sgd(const char* what, float* p, const float* g, float* momentum_buf, const StepRanges& r, double momentum, double dampening,
+               int nesterov, float grad_scale, const float* clip_coef, hipStream_t s) {
+  if (int e = check_step_ranges(what, r)) return e;
+  R3M_REQUIRE(momentum == 0.0 || momentum_buf, "sgd: momentum needs a momentum buffer");
+  R3M_REQUIRE(!nesterov || (momentum > 0.0 && dampening == 0.0), "sgd: nesterov needs momentum > 0 and dampening = 0");
+  float* buf = momentum != 0.0 ? momentum_buf : nullptr;
+  if (r.n == 1 && r.count[0] > 0 && !clip_coef) {
+    const long long o = r.off[0], n4 = r.count[0] / 4;
+    hipLaunchKernelGGL(sgd_whole_kernel, dim3(opt_grid(n4)), dim3(256), 0, s, p + o, g + o, buf ? buf + o : nullptr, n4,
+                       (float)(r.lrs ? r.lrs[0] : r.lr), (float)momentum, (float)(1.0 - dampening), (float)(r.wds ? r.wds[0] : r.wd), nesterov,
+                       r.step[0] == 1 ? 1 : 0, grad_scale);
+    return check_launch(what);
   }
-  return 0;
-}
-
-int launch_adam_groups(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
-                       const double* lr, const double* weight_decay, int n_ranges, double beta1, double beta2, double eps, int decoupled,
-                       float grad_scale, const float* clip_coef, hipStream_t s) {
-  if (int e = check_groups("adam_groups", off, count, step, lr, weight_decay, n_ranges)) return e;
-  R3M_REQUIRE(n_ranges == 0 || (p && g && m && v), "adam_groups: null buffer");
-  for (int i = 0; i < n_ranges;) {
-    GroupTable t;
+  for (int i = 0; i < r.n;) {
+    StepTable t = {};
     int src[OPT_MAX_RANGES];
-    const int grid = fill_ranges(t.r, off, count, n_ranges, &i, src);
+    const int grid = fill_ranges(t.r, r.off, r.count, r.n, &i, src);
     if (!grid) break;
-    for (int r = 0; r < OPT_MAX_RANGES; ++r) t.wd[r] = 0.f;
-    for (int r = 0; r < t.r.n; ++r) {
-      const int k = src[r];
-      adam_bias_corrections(lr[k], beta1, beta2, step[k], &t.r.a[r], &t.r.b[r]);
-      // AdamW: param.mul_(1 - lr * weight_decay), the factor a python (double) scalar
-      t.wd[r] = decoupled ? (weight_decay[k] == 0.0 ? 1.f : (float)(1.0 - lr[k] * weight_decay[k])) : (float)weight_decay[k];
+    for (int k = 0; k < t.r.n; ++k) {
+      t.a[k] = r.step[src[k]] == 1 ? 1.f : 0.f;
+      t.b[k] = (float)(r.lrs ? r.lrs[src[k]] : r.lr);
+      t.wd[k] = (float)(r.wds ? r.wds[src[k]] : r.wd);
     }
-    hipLaunchKernelGGL(adam_groups_kernel, dim3(grid), dim3(256), 0, s, p, g, m, v, t, (float)beta2, (float)(1.0 - beta1),
-                       (float)(1.0 - beta2), (float)eps, grad_scale, clip_coef, decoupled ? 1 : 0);
-    if (int e = check_launch("adam_groups")) return e;
-  }
-  return 0;
-}
-
-int launch_sgd_groups(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
-                      const double* lr, const double* weight_decay, int n_ranges, double momentum, double dampening, int nesterov,
-                      float grad_scale, const float* clip_coef, hipStream_t s) {
-  if (int e = check_groups("sgd_groups", off, count, step, lr, weight_decay, n_ranges)) return e;
-  if (int e = check_sgd(momentum, dampening, nesterov, momentum_buf)) return e;
-  R3M_REQUIRE(n_ranges == 0 || (p && g), "sgd_groups: null buffer");
-  for (int i = 0; i < n_ranges;) {
-    GroupTable t;
-    int src[OPT_MAX_RANGES];
-    const int grid = fill_ranges(t.r, off, count, n_ranges, &i, src);
-    if (!grid) break;
-    for (int r = 0; r < OPT_MAX_RANGES; ++r) t.wd[r] = 0.f;
-    for (int r = 0; r < t.r.n; ++r) {
-      const int k = src[r];
-      t.r.a[r] = step[k] == 1 ? 1.f : 0.f;
-      t.r.b[r] = (float)lr[k];
-      t.wd[r] = (float)weight_decay[k];
-    }
-    hipLaunchKernelGGL(sgd_groups_kernel, dim3(grid), dim3(256), 0, s, p, g, momentum != 0.0 ? momentum_buf : nullptr, t, (float)momentum,
+    hipLaunchKernelGGL(sgd_step_kernel, dim3(grid), dim3(256), 0, s, p, g, buf, t, (float)momentum,
                        (float)(1.0 - dampening), nesterov, grad_scale, clip_coef);
-    if (int e = check_launch("sgd_groups")) return e;
+    if (int e = check_launch(what)) return e;
   }
   return 0;
 }
@@ -420,7 +338,7 @@ int launch_grad_sqnorm_ranges(const float* g, const long long* off, const long l
   if (int e = check_ranges("grad_sqnorm_ranges", off, count, nullptr, n_ranges, false)) return e;
   bool launched = false;
   for (int i = 0; i < n_ranges;) {
-    RangeTable t;
+    RangeTable t = {};
     int src[OPT_MAX_RANGES];
     const int grid = fill_ranges(t, off, count, n_ranges, &i, src);
     if (!grid) break;

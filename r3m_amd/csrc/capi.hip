@@ -690,27 +690,39 @@ int r3m_loss_finalize(void* ws, size_t ws_bytes, int B, int have_lang, float* me
   return launch_loss_finalize(static_cast<float*>(ws), B, have_lang, metrics, l2w, l1w, tcnw, langw, S(stream));
 }
 
+// The optimizer steps: every form is one view of its ranges handed to the one launcher of its optimizer (adam.hip). The whole-buffer
+// forms are the one range [0, n); they and the ranged forms carry one lr (and SGD one weight decay) for all ranges and no coefficient.
 int r3m_adam_step(float* p, const float* g, float* m, float* v, long long n, double lr, double b1, double b2, double eps,
                   long long step, float grad_scale, r3m_stream_t stream) {
-  return launch_adam(p, g, m, v, n, lr, b1, b2, eps, step, grad_scale, S(stream));
+  R3M_REQUIRE(n % 4 == 0, "adam: n=%lld must be a multiple of 4", n);
+  R3M_REQUIRE(n > 0, "adam: n=%lld must be > 0 (an empty buffer is not stepped)", n);
+  R3M_REQUIRE(step >= 1, "adam: step=%lld must be >= 1", step);
+  const long long off = 0;
+  return launch_adam("adam", p, g, m, v, {&off, &n, &step, 1, nullptr, nullptr, lr, 0.0}, b1, b2, eps, 0, grad_scale, nullptr, S(stream));
 }
 
 int r3m_sgd_step(float* p, const float* g, float* momentum_buf, long long n, double lr, double momentum, double dampening,
                  double weight_decay, int nesterov, long long step, float grad_scale, r3m_stream_t stream) {
   R3M_REQUIRE(p && g, "sgd_step: null argument");
-  return launch_sgd(p, g, momentum_buf, n, lr, momentum, dampening, weight_decay, nesterov, step, grad_scale, S(stream));
+  R3M_REQUIRE(n % 4 == 0, "sgd: n=%lld must be a multiple of 4", n);
+  R3M_REQUIRE(n > 0, "sgd: n=%lld must be > 0 (an empty buffer is not stepped)", n);
+  R3M_REQUIRE(step >= 1, "sgd: step=%lld must be >= 1", step);
+  const long long off = 0;
+  return launch_sgd("sgd", p, g, momentum_buf, {&off, &n, &step, 1, nullptr, nullptr, lr, weight_decay}, momentum, dampening, nesterov,
+                    grad_scale, nullptr, S(stream));
 }
 
 int r3m_adam_step_ranges(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
                          int n_ranges, double lr, double b1, double b2, double eps, float grad_scale, r3m_stream_t stream) {
-  return launch_adam_ranges(p, g, m, v, off, count, step, n_ranges, lr, b1, b2, eps, grad_scale, S(stream));
+  return launch_adam("adam_ranges", p, g, m, v, {off, count, step, n_ranges, nullptr, nullptr, lr, 0.0}, b1, b2, eps, 0, grad_scale, nullptr,
+                     S(stream));
 }
 
 int r3m_sgd_step_ranges(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
                         int n_ranges, double lr, double momentum, double dampening, double weight_decay, int nesterov, float grad_scale,
                         r3m_stream_t stream) {
-  return launch_sgd_ranges(p, g, momentum_buf, off, count, step, n_ranges, lr, momentum, dampening, weight_decay, nesterov, grad_scale,
-                           S(stream));
+  return launch_sgd("sgd_ranges", p, g, momentum_buf, {off, count, step, n_ranges, nullptr, nullptr, lr, weight_decay}, momentum, dampening,
+                    nesterov, grad_scale, nullptr, S(stream));
 }
 
 size_t r3m_grad_sqnorm_workspace_bytes(void) { return grad_sqnorm_workspace_bytes(); }
@@ -729,18 +741,24 @@ int r3m_clip_coef(const double* sqnorm, double max_norm, float grad_scale, float
   return launch_clip_coef(sqnorm, max_norm, grad_scale, coef_norm, S(stream));
 }
 
+// a learning rate and a weight decay per range (null arrays would mean "one for all" to the launcher: refused here) and an optional
+// device clip coefficient
 int r3m_adam_step_groups(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
                          const double* lr, const double* weight_decay, int n_ranges, double b1, double b2, double eps, int decoupled,
                          float grad_scale, const float* clip_coef, r3m_stream_t stream) {
-  return launch_adam_groups(p, g, m, v, off, count, step, lr, weight_decay, n_ranges, b1, b2, eps, decoupled, grad_scale, clip_coef,
-                            S(stream));
+  R3M_REQUIRE(n_ranges <= 0 || (lr && weight_decay), "adam_groups: null lr / weight_decay arrays");
+  R3M_REQUIRE(n_ranges <= 0 || (p && g && m && v), "adam_groups: null buffer");
+  return launch_adam("adam_groups", p, g, m, v, {off, count, step, n_ranges, lr, weight_decay, 0.0, 0.0}, b1, b2, eps, decoupled, grad_scale,
+                     clip_coef, S(stream));
 }
 
 int r3m_sgd_step_groups(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
                         const double* lr, const double* weight_decay, int n_ranges, double momentum, double dampening, int nesterov,
                         float grad_scale, const float* clip_coef, r3m_stream_t stream) {
-  return launch_sgd_groups(p, g, momentum_buf, off, count, step, lr, weight_decay, n_ranges, momentum, dampening, nesterov, grad_scale,
-                           clip_coef, S(stream));
+  R3M_REQUIRE(n_ranges <= 0 || (lr && weight_decay), "sgd_groups: null lr / weight_decay arrays");
+  R3M_REQUIRE(n_ranges <= 0 || (p && g), "sgd_groups: null buffer");
+  return launch_sgd("sgd_groups", p, g, momentum_buf, {off, count, step, n_ranges, lr, weight_decay, 0.0, 0.0}, momentum, dampening, nesterov,
+                    grad_scale, clip_coef, S(stream));
 }
 
 }  // extern "C"

@@ -300,23 +300,19 @@ int launch_tcn_lp_loss(const float* alle, const int* perm, const int* iperm, flo
 int launch_lang_infonce(const float* scores, const float* mask, float* dscore, float* ws, int B, float langw, hipStream_t s);
 int launch_loss_finalize(float* ws, int B, int have_lang, float* metrics, float l2w, float l1w, float tcnw, float langw,
                          hipStream_t s);
-int launch_adam(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2, double eps,
-                long long step, float grad_scale, hipStream_t s);
-int launch_sgd(float* p, const float* g, float* momentum_buf, long long n, double lr, double momentum, double dampening,
-               double weight_decay, int nesterov, long long step, float grad_scale, hipStream_t s);
-// the same steps over disjoint, sorted [off, off + count) ranges of the flat buffers with a step count each (host arrays)
-int launch_adam_ranges(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
-                       int n_ranges, double lr, double beta1, double beta2, double eps, float grad_scale, hipStream_t s);
-int launch_sgd_ranges(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
-                      int n_ranges, double lr, double momentum, double dampening, double weight_decay, int nesterov, float grad_scale,
-                      hipStream_t s);
-// the ranged steps with a learning rate and a weight decay per range (host arrays) and an optional device clip coefficient
-int launch_adam_groups(float* p, const float* g, float* m, float* v, const long long* off, const long long* count, const long long* step,
-                       const double* lr, const double* weight_decay, int n_ranges, double beta1, double beta2, double eps, int decoupled,
-                       float grad_scale, const float* clip_coef, hipStream_t s);
-int launch_sgd_groups(float* p, const float* g, float* momentum_buf, const long long* off, const long long* count, const long long* step,
-                      const double* lr, const double* weight_decay, int n_ranges, double momentum, double dampening, int nesterov,
-                      float grad_scale, const float* clip_coef, hipStream_t s);
+// What one optimizer call steps: n disjoint, sorted [off, off + count) ranges of the flat buffers with a step count each (host arrays;
+// offsets and counts multiples of 4), and a learning rate and a weight decay per range (lrs / wds) or, where those are null, lr / wd
+// for every range. `what` names the call in messages. clip_coef: null, or a device scalar that the gradient is multiplied by.
+struct StepRanges {
+  const long long *off, *count, *step;
+  int n;
+  const double *lrs, *wds;
+  double lr, wd;
+};
+int launch_adam(const char* what, float* p, const float* g, float* m, float* v, const StepRanges& r, double beta1, double beta2, double eps,
+                int decoupled, float grad_scale, const float* clip_coef, hipStream_t s);
+int launch_sgd(const char* what, float* p, const float* g, float* momentum_buf, const StepRanges& r, double momentum, double dampening,
+               int nesterov, float grad_scale, const float* clip_coef, hipStream_t s);
 // deterministic fp64 sum of squares of the gradients over ranges -> *sqnorm (device), and the clip coefficient from it
 size_t grad_sqnorm_workspace_bytes();
 int launch_grad_sqnorm_ranges(const float* g, const long long* off, const long long* count, int n_ranges, double* sqnorm, int accumulate,

@@ -22,68 +22,6 @@ def _dd(v):
     return (C.c_double * len(v))(*v)
 
 
-class _PerTensorSteps:
-    """Step counts per parameter TENSOR of an owner, as torch.optim keeps them per parameter: a tensor that got no gradient (frozen,
-    requires_grad False) is not stepped and its count — hence its Adam bias correction — stays behind. Kept as each tensor's lag
-    behind the owner's count `_steps[i]` (None: no tensor lags, the state of every run that never froze anything), so code that sets
-    `_steps` by hand keeps meaning "every tensor at that step".
-
-    Owners that expose param_ranges() / grads_written() (HipResNet) are stepped tensor by tensor; the others (the language head,
-    whose tensors are not 4-aligned) stay all-or-nothing through has_grads()."""
-
-    def _advance(self, i, owner, hyper=None):
-        """Advance the counts of owner i's tensors that received a gradient since zero_grad(). Returns None when there is nothing to
-        step, "all" when the whole flat buffer steps with one count (self._steps[i], already advanced), else (offsets, counts, steps)
-        of the merged ranges: neighbouring tensors with equal counts form one range.
-
-        `hyper` (parameter groups): one (lr, weight_decay) per param_ranges() entry. Neighbours then merge only when step count,
-        learning rate and weight decay are all equal, and the ranges come back as (offsets, counts, steps, hypers)."""
-        if not hasattr(owner, "param_ranges"):
-            if not getattr(owner, "has_grads", lambda: True)():
-                return None
-            self._steps[i] += 1
-            return "all"
-        written = owner.grads_written()
-        if not any(written):
-            return None
-        lag = self._lag[i]
-        if lag is None and all(written) and hyper is None:
-            self._steps[i] += 1
-            return "all"
-        ranges = owner.param_ranges()
-        base = self._steps[i]
-        steps = [base] * len(ranges) if lag is None else [base - l for l in lag]
-        steps = [s + 1 if w else s for s, w in zip(steps, written)]
-        base = max(steps)
-        self._steps[i] = base
-        lag = [base - s for s in steps]
-        self._lag[i] = lag if any(lag) else None
-        offs, counts, rsteps, rhyper = [], [], [], []
-        for k, ((off, n), s, w) in enumerate(zip(ranges, steps, written)):
-            if not w:
-                continue
-            h = None if hyper is None else hyper[k]
-            if offs and offs[-1] + counts[-1] == off and rsteps[-1] == s and rhyper[-1] == h:
-                counts[-1] += n
-            else:
-                offs.append(off); counts.append(n); rsteps.append(s); rhyper.append(h)
-        if len(offs) == 1 and offs[0] == 0 and counts[0] == owner.flat_params().numel():
-            return "all"
-        return (offs, counts, rsteps) if hyper is None else (offs, counts, rsteps, rhyper)
-
-    def tensor_steps(self, i):
-        """absolute step count per tensor of owner i (None: every tensor at self._steps[i])"""
-        return None if self._lag[i] is None else [self._steps[i] - l for l in self._lag[i]]
-
-    def _load_tensor_steps(self, sd):
-        ts = sd.get("tensor_steps")        # absent in snapshots from before per-tensor counts: every tensor at its owner's step
-        self._lag = [None] * len(self.owners)
-        for i, t in enumerate(ts or []):
-            if t is not None:
-                lag = [self._steps[i] - int(s) for s in t]
-                self._lag[i] = lag if any(lag) else None
-
-
 class _StepPlan:
     """What one owner steps now: sorted ranges with a step count, a learning rate and a weight decay each. `whole`: one range over the
     whole flat buffer."""
@@ -153,22 +91,49 @@ def _make_groups(what, owners, param_groups, defaults, optimizer_wide):
     return groups
 
 
-class _Grouped(_PerTensorSteps):
-    """Parameter groups and gradient clipping, shared by FusedAdam and FusedSGD."""
-    _plain_weight_decay = False      # whether the plain entry points take a (global) weight decay: r3m_sgd_step does
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What FusedAdam and FusedSGD share: the owners protocol, step counts per parameter tensor, parameter groups turned into ranges,
+    gradient clipping and the snapshot.
 
-    def _init_common(self, owners):
-        n = len(owners)
-        self._steps = [0] * n
-        self._lag = [None] * n                 # per-tensor lag behind _steps (_PerTensorSteps)
+    Step counts per parameter TENSOR of an owner, as torch.optim keeps them per parameter: a tensor that got no gradient (frozen,
+    requires_grad False) is not stepped and its count — hence its Adam bias correction — stays behind. Kept as each tensor's lag
+    behind the owner's count `_steps[i]` (None: no tensor lags, the state of every run that never froze anything), so code that sets
+    `_steps` by hand keeps meaning "every tensor at that step".
+
+    Owners that expose param_ranges() / grads_written() (HipResNet) are stepped tensor by tensor; the others (the language head,
+    whose tensors are not 4-aligned) stay all-or-nothing through has_grads()."""
+    _name = None                     # the class name in messages (FusedAdamW speaks as FusedAdam)
+    _plain_weight_decay = False      # whether the plain entry points take a (global) weight decay: r3m_sgd_step does
+    _moments = ()                    # (attribute, snapshot key) of the per-owner state buffers; the first leads in messages
+    _mismatch = _elements = None     # load_state_dict's refusals
+
+    def __init__(self, owners, defaults, param_groups, optimizer_wide):
+        if defaults["weight_decay"] < 0 or defaults["lr"] < 0:
+            raise ValueError(f"{self._name}: lr={defaults['lr']} and weight_decay={defaults['weight_decay']} must be >= 0")
+        self.owners = list(owners)
+        if param_groups is None:
+            params = [p for o in self.owners for p in o.parameters()]
+        else:
+            params = _make_groups(type(self).__name__, self.owners, param_groups, defaults, optimizer_wide + ("max_grad_norm",))
+        super().__init__(params, defaults)
+        n = len(self.owners)
+        self._steps = [0] * n                  # torch.optim.Adam keeps `step` per parameter: an owner that receives its first gradient
+        self._lag = [None] * n                 # later (the language head) starts its bias correction then; per-tensor lag behind _steps
         self._range_groups = [None] * n        # per owner: (address of its flat buffer, group index of each range) -- found again by address
         self._clip_bufs = {}                   # device -> (fp64 accumulator [1], {coef, norm} [2], workspace)
         self.last_grad_norm = None             # device scalar: the gradient norm of the last clipped step, before clipping
         self.grad_scale = 1.0
+        for attr, _ in self._moments:
+            setattr(self, attr, [None] * n)
 
-    def _common_state(self):
-        return dict(owners=self.owners, _steps=self._steps, _lag=self._lag, grad_scale=self.grad_scale,
-                    _range_groups=[None] * len(self.owners), _clip_bufs={}, last_grad_norm=None)     # device scratch is re-created
+    def __getstate__(self):
+        # Optimizer.__getstate__ keeps defaults/state/param_groups only; deepcopy(R3M) and pickling must keep the owners
+        # protocol and the moments too (the reference's torch.optim.Adam deep-copies with its state).
+        st = super().__getstate__()
+        st.update(owners=self.owners, _steps=self._steps, _lag=self._lag, grad_scale=self.grad_scale,
+                  _range_groups=[None] * len(self.owners), _clip_bufs={}, last_grad_norm=None,      # device scratch is re-created
+                  **{attr: getattr(self, attr) for attr, _ in self._moments})
+        return st
 
     @property
     def max_grad_norm(self):
@@ -183,6 +148,10 @@ class _Grouped(_PerTensorSteps):
         # Gradients live in persistent flat buffers; "zeroing" = the next backward overwrites them (no memset pass).
         for o in self.owners:
             o.mark_grads_stale()
+
+    def tensor_steps(self, i):
+        """absolute step count per tensor of owner i (None: every tensor at self._steps[i])"""
+        return None if self._lag[i] is None else [self._steps[i] - l for l in self._lag[i]]
 
     # ---- groups -> ranges ----
     def _groups_of_ranges(self, i, owner):
@@ -222,18 +191,37 @@ class _Grouped(_PerTensorSteps):
         return pairs[0] if all(p == pairs[0] for p in pairs) else pairs
 
     def _plan(self, i, owner):
-        """Advance owner i's step counts and return its _StepPlan (None: nothing to step)."""
+        """Advance the step counts of owner i's tensors that received a gradient since zero_grad() and return what to step now as a
+        _StepPlan (None: nothing). Neighbouring tensors form one range when step count, learning rate and weight decay are all equal."""
         h = self._hyper(i, owner)
         per_range = isinstance(h, list)
-        todo = self._advance(i, owner, h if per_range else None)
-        if todo is None:
+        n = owner.flat_params().numel()
+        ranged = hasattr(owner, "param_ranges")
+        written = owner.grads_written() if ranged else [getattr(owner, "has_grads", lambda: True)()]
+        if not any(written):
             return None
-        if todo == "all":                      # with per-range pairs: every range merged into one, so the pairs are all equal
-            lr, wd = h[0] if per_range else h
-            return _StepPlan(True, [0], [owner.flat_params().numel()], [self._steps[i]], [lr], [wd])
-        offs, counts, steps = todo[:3]
-        hy = todo[3] if per_range else [h] * len(offs)
-        return _StepPlan(False, offs, counts, steps, [a for a, _ in hy], [b for _, b in hy])
+        lag = self._lag[i]
+        if not ranged or (lag is None and all(written) and not per_range):      # the whole flat buffer at one step count
+            self._steps[i] += 1
+            return _StepPlan(True, [0], [n], [self._steps[i]], [h[0]], [h[1]])
+        ranges = owner.param_ranges()
+        base = self._steps[i]
+        steps = [base] * len(ranges) if lag is None else [base - l for l in lag]
+        steps = [s + 1 if w else s for s, w in zip(steps, written)]
+        base = max(steps)
+        self._steps[i] = base
+        lag = [base - s for s in steps]
+        self._lag[i] = lag if any(lag) else None
+        plan = _StepPlan(False, [], [], [], [], [])
+        for (off, count), s, w, (lr, wd) in zip(ranges, steps, written, h if per_range else [h] * len(ranges)):
+            if not w:
+                continue
+            if plan.offs and (plan.offs[-1] + plan.counts[-1], plan.steps[-1], plan.lrs[-1], plan.wds[-1]) == (off, s, lr, wd):
+                plan.counts[-1] += count
+            else:
+                plan.offs.append(off); plan.counts.append(count); plan.steps.append(s); plan.lrs.append(lr); plan.wds.append(wd)
+        plan.whole = plan.offs == [0] and plan.counts == [n]
+        return plan
 
     # ---- clipping ----
     def _clip_scratch(self, device):
@@ -245,13 +233,13 @@ class _Grouped(_PerTensorSteps):
             self._clip_bufs[device] = b
         return b
 
-    def _begin_step(self, what):
+    def _begin_step(self):
         """Advance the step counts of every owner, then (max_grad_norm) take ONE gradient norm over exactly the ranges about to be
         stepped, all owners in order, and form the clip coefficient on the device. -> ([(i, owner, plan)], coefficient pointer or None)"""
         plans = []
         for i, o in enumerate(self.owners):
             if not o.flat_params().is_cuda:
-                raise RuntimeError(f"r3m_amd.{what}: parameters must live on the GPU (HIP kernel, no CPU fallback)")
+                raise RuntimeError(f"r3m_amd.{self._name}: parameters must live on the GPU (HIP kernel, no CPU fallback)")
             plan = self._plan(i, o)            # what torch.optim steps: the tensors with a gradient since zero_grad()
             if plan is not None:
                 plans.append((i, o, plan))
@@ -261,7 +249,7 @@ class _Grouped(_PerTensorSteps):
         L = _lib.lib()
         dev = plans[0][1].flat_params().device
         if any(o.flat_params().device != dev for _, o, _ in plans):
-            raise RuntimeError(f"r3m_amd.{what}: max_grad_norm needs every owner on one device (one norm over all of them)")
+            raise RuntimeError(f"r3m_amd.{self._name}: max_grad_norm needs every owner on one device (one norm over all of them)")
         acc, coef_norm, ws = self._clip_scratch(dev)
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
@@ -273,16 +261,51 @@ class _Grouped(_PerTensorSteps):
         self.last_grad_norm = coef_norm[1]
         return plans, coef_norm.data_ptr()
 
-    def _load_groups(self, what, sd):
-        saved = sd["param_groups"]
-        if len(saved) == len(self.param_groups):
-            for g, s in zip(self.param_groups, saved):      # keys a snapshot from before lacks keep the constructor's values
+    # ---- state: enough to resume (the reference never saved optimizer state, train_representation.py:123-130; torch's own state_dict
+    # would drop the moment buffers, the step counts and grad_scale, which all live outside Optimizer.state) ----
+    def state_dict(self):
+        return {"steps": list(self._steps), "tensor_steps": [self.tensor_steps(i) for i in range(len(self.owners))],
+                **{key: [None if t is None else t.cpu() for t in getattr(self, attr)] for attr, key in self._moments},
+                "grad_scale": float(self.grad_scale), "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+
+    def _saved_steps(self, sd):
+        return sd["steps"]
+
+    def load_state_dict(self, sd):
+        what, n = f"{self._name}.load_state_dict", len(self.owners)
+        steps = [int(s) for s in self._saved_steps(sd)]
+        saved = [(attr, sd[key]) for attr, key in self._moments]
+        if len(steps) != n or any(len(s) != n for _, s in saved):
+            # e.g. saved with langweight=0 (encoder only) and resumed with a language head, or the reverse: silently
+            # mis-assigning moments between owners would be worse than refusing
+            raise ValueError(what + self._mismatch.format(k=len(steps), e=len(saved[0][1]), n=n,
+                                                          names=", ".join(type(o).__name__ for o in self.owners)))
+        for i, o in enumerate(self.owners):
+            t = saved[0][1][i]
+            if t is not None and t.numel() != o.flat_params().numel():
+                raise ValueError(what + self._elements.format(i=i, t=type(o).__name__, k=t.numel(), n=o.flat_params().numel()))
+        self._steps = steps
+        ts = sd.get("tensor_steps")        # absent in snapshots from before per-tensor counts: every tensor at its owner's step
+        self._lag = [None] * n
+        for i, t in enumerate(ts or []):
+            if t is not None:
+                lag = [self._steps[i] - int(s) for s in t]
+                self._lag[i] = lag if any(lag) else None
+        for attr, s in saved:
+            for i, o in enumerate(self.owners):
+                if s[i] is not None:        # an owner the snapshot holds no buffer for keeps what it has
+                    getattr(self, attr)[i] = s[i].to(o.flat_params().device)
+        groups = sd["param_groups"]
+        if len(groups) == len(self.param_groups):
+            for g, s in zip(self.param_groups, groups):     # keys a snapshot from before lacks keep the constructor's values
                 g.update(s)
-        elif len(saved) != 1:                               # one group: a snapshot from before parameter groups; the constructor's hold
-            raise ValueError(f"{what}.load_state_dict: the snapshot has {len(saved)} parameter groups, this optimizer {len(self.param_groups)}")
+        elif len(groups) != 1:                              # one group: a snapshot from before parameter groups; the constructor's hold
+            raise ValueError(f"{what}: the snapshot has {len(groups)} parameter groups, this optimizer {len(self.param_groups)}")
+        if "grad_scale" in sd:              # absent in older snapshots: the optimizer keeps the one it has
+            self.grad_scale = float(sd["grad_scale"])
 
 
-class FusedAdam(_Grouped, torch.optim.Optimizer):
+class FusedAdam(_FlatOptimizer):
     """`owners` are modules exposing flat_params() / flat_grads() / mark_grads_stale() (HipResNet, LanguageReward).
 
     weight_decay: torch.optim.Adam's L2 term (g += wd * p), or with decoupled_weight_decay torch.optim.AdamW's (p *= 1 - lr * wd).
@@ -293,30 +316,17 @@ class FusedAdam(_Grouped, torch.optim.Optimizer):
     grad_scale (the averaged gradient under the data-parallel wrapper), in two launches per flat buffer and without a host wait;
     `last_grad_norm` is then the norm before clipping as a device scalar (None before the first clipped step).
     Without groups, weight decay and clipping the calls into the library are those of the plain optimizer, argument for argument."""
+    _name = "FusedAdam"
+    _moments = (("_m", "exp_avg"), ("_v", "exp_avg_sq"))
+    _mismatch = (": the snapshot holds optimizer state for {k} flat buffer(s) ({e} moment entries), this optimizer has {n} ({names}); "
+                 "was it saved with a different langweight?")
+    _elements = ": moments of owner {i} ({t}) have {k} elements, its parameters {n}"
 
     def __init__(self, owners, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled_weight_decay=False, max_grad_norm=None,
                  param_groups=None):
-        if weight_decay < 0 or lr < 0:
-            raise ValueError(f"FusedAdam: lr={lr} and weight_decay={weight_decay} must be >= 0")
-        self.owners = list(owners)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled_weight_decay=bool(decoupled_weight_decay),
                         max_grad_norm=max_grad_norm)
-        if param_groups is None:
-            params = [p for o in self.owners for p in o.parameters()]
-        else:
-            params = _make_groups(type(self).__name__, self.owners, param_groups, defaults,
-                                  ("betas", "eps", "decoupled_weight_decay", "max_grad_norm"))
-        super().__init__(params, defaults)
-        self._init_common(self.owners)         # torch.optim.Adam keeps `step` per parameter: an owner that receives its first
-        self._m = [None] * len(self.owners)    # gradient later (the language head) starts its bias correction then
-        self._v = [None] * len(self.owners)
-
-    def __getstate__(self):
-        # Optimizer.__getstate__ keeps defaults/state/param_groups only; deepcopy(R3M) and pickling must keep the owners
-        # protocol and the moments too (the reference's torch.optim.Adam deep-copies with its state).
-        st = super().__getstate__()
-        st.update(self._common_state(), _m=self._m, _v=self._v)
-        return st
+        super().__init__(owners, defaults, param_groups, ("betas", "eps", "decoupled_weight_decay"))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -325,7 +335,7 @@ class FusedAdam(_Grouped, torch.optim.Optimizer):
         g0 = self.param_groups[0]
         (b1, b2), eps, decoupled = g0["betas"], g0["eps"], bool(g0.get("decoupled_weight_decay", False))
         L = _lib.lib()
-        plans, coef = self._begin_step("FusedAdam")
+        plans, coef = self._begin_step()
         for i, o, plan in plans:
             p = o.flat_params()
             g = o.flat_grads()
@@ -369,38 +379,12 @@ class FusedAdam(_Grouped, torch.optim.Optimizer):
         """Step count of the first owner (the encoder): what the snapshot's `step` key has always meant."""
         return self._steps[0]
 
-    # state: enough to resume (the reference never saved optimizer state, train_representation.py:123-130)
     def state_dict(self):
-        return {"step": self._steps[0], "steps": list(self._steps), "tensor_steps": [self.tensor_steps(i) for i in range(len(self.owners))],
-                "exp_avg": [None if m is None else m.cpu() for m in self._m],
-                "exp_avg_sq": [None if v is None else v.cpu() for v in self._v], "grad_scale": float(self.grad_scale), "param_groups": [
-                    {k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+        return {"step": self._steps[0], **super().state_dict()}
 
-    def load_state_dict(self, sd):
+    def _saved_steps(self, sd):
         steps = sd.get("steps")           # round-1 snapshots carry one shared `step`
-        steps = [int(s) for s in steps] if steps is not None else [int(sd["step"])] * len(self.owners)
-        n = len(self.owners)
-        if len(steps) != n or len(sd["exp_avg"]) != n or len(sd["exp_avg_sq"]) != n:
-            # e.g. saved with langweight=0 (encoder only) and resumed with a language head, or the reverse: silently
-            # mis-assigning moments between owners would be worse than refusing
-            raise ValueError(f"FusedAdam.load_state_dict: the snapshot holds optimizer state for {len(steps)} flat buffer(s) "
-                             f"({len(sd['exp_avg'])} moment entries), this optimizer has {n} "
-                             f"({', '.join(type(o).__name__ for o in self.owners)}); was it saved with a different langweight?")
-        for i, o in enumerate(self.owners):
-            m = sd["exp_avg"][i]
-            if m is not None and m.numel() != o.flat_params().numel():
-                raise ValueError(f"FusedAdam.load_state_dict: moments of owner {i} ({type(o).__name__}) have {m.numel()} elements, "
-                                 f"its parameters {o.flat_params().numel()}")
-        self._steps = steps
-        self._load_tensor_steps(sd)
-        for i, o in enumerate(self.owners):
-            if sd["exp_avg"][i] is not None:
-                dev = o.flat_params().device
-                self._m[i] = sd["exp_avg"][i].to(dev)
-                self._v[i] = sd["exp_avg_sq"][i].to(dev)
-        self._load_groups("FusedAdam", sd)
-        if "grad_scale" in sd:              # absent in older snapshots: the optimizer keeps the one it has
-            self.grad_scale = float(sd["grad_scale"])
+        return steps if steps is not None else [sd["step"]] * len(self.owners)
 
 
 class FusedAdamW(FusedAdam):
@@ -411,28 +395,23 @@ class FusedAdamW(FusedAdam):
                          max_grad_norm=max_grad_norm, param_groups=param_groups)
 
 
-class FusedSGD(_Grouped, torch.optim.Optimizer):
+class FusedSGD(_FlatOptimizer):
     """torch.optim.SGD semantics (momentum, dampening, weight_decay, nesterov) as one HIP kernel per flat buffer. The reference
     only ever builds Adam (models_r3m.py:76); this is the plain alternative on the same owners protocol. param_groups (lr and
     weight_decay per group; momentum, dampening and nesterov are optimizer-wide) and max_grad_norm as in FusedAdam."""
+    _name = "FusedSGD"
     _plain_weight_decay = True
+    _moments = (("_buf", "momentum_buffer"),)
+    _mismatch = ": the snapshot holds optimizer state for {k} flat buffer(s), this optimizer has {n} ({names})"
+    _elements = ": the momentum buffer of owner {i} ({t}) has {k} elements, its parameters {n}"
 
     def __init__(self, owners, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, max_grad_norm=None,
                  param_groups=None):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        if weight_decay < 0 or lr < 0:
-            raise ValueError(f"FusedSGD: lr={lr} and weight_decay={weight_decay} must be >= 0")
-        self.owners = list(owners)
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
                         max_grad_norm=max_grad_norm)
-        if param_groups is None:
-            params = [p for o in self.owners for p in o.parameters()]
-        else:
-            params = _make_groups("FusedSGD", self.owners, param_groups, defaults, ("momentum", "dampening", "nesterov", "max_grad_norm"))
-        super().__init__(params, defaults)
-        self._init_common(self.owners)
-        self._buf = [None] * len(self.owners)
+        super().__init__(owners, defaults, param_groups, ("momentum", "dampening", "nesterov"))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -440,7 +419,7 @@ class FusedSGD(_Grouped, torch.optim.Optimizer):
             raise NotImplementedError("FusedSGD.step(closure) is not supported")
         g0 = self.param_groups[0]
         L = _lib.lib()
-        plans, coef = self._begin_step("FusedSGD")
+        plans, coef = self._begin_step()
         for i, o, plan in plans:
             p = o.flat_params()
             g = o.flat_grads()
@@ -462,37 +441,6 @@ class FusedSGD(_Grouped, torch.optim.Optimizer):
                                                      len(plan.offs), float(plan.lrs[0]), float(g0["momentum"]), float(g0["dampening"]),
                                                      float(plan.wds[0]), int(bool(g0["nesterov"])), float(self.grad_scale),
                                                      _lib.stream_ptr(p.device)), "sgd_step_ranges")
-
-    def __getstate__(self):
-        st = super().__getstate__()
-        st.update(self._common_state(), _buf=self._buf)
-        return st
-
-    # state: enough to resume, in the manner of FusedAdam's (torch's own state_dict would drop the momentum buffers, the step counts and
-    # grad_scale, which all live outside Optimizer.state)
-    def state_dict(self):
-        return {"steps": list(self._steps), "tensor_steps": [self.tensor_steps(i) for i in range(len(self.owners))],
-                "momentum_buffer": [None if b is None else b.cpu() for b in self._buf], "grad_scale": float(self.grad_scale),
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
-
-    def load_state_dict(self, sd):
-        n = len(self.owners)
-        if len(sd["steps"]) != n or len(sd["momentum_buffer"]) != n:
-            raise ValueError(f"FusedSGD.load_state_dict: the snapshot holds optimizer state for {len(sd['steps'])} flat buffer(s), this "
-                             f"optimizer has {n} ({', '.join(type(o).__name__ for o in self.owners)})")
-        for i, o in enumerate(self.owners):
-            b = sd["momentum_buffer"][i]
-            if b is not None and b.numel() != o.flat_params().numel():
-                raise ValueError(f"FusedSGD.load_state_dict: the momentum buffer of owner {i} ({type(o).__name__}) has {b.numel()} elements, "
-                                 f"its parameters {o.flat_params().numel()}")
-        self._steps = [int(s) for s in sd["steps"]]
-        self._load_tensor_steps(sd)
-        for i, o in enumerate(self.owners):
-            b = sd["momentum_buffer"][i]
-            self._buf[i] = None if b is None else b.to(o.flat_params().device)
-        self._load_groups("FusedSGD", sd)
-        if "grad_scale" in sd:
-            self.grad_scale = float(sd["grad_scale"])
 
 
 # ---- group builders -------------------------------------------------------------------------------------------------------------

@@ -2,10 +2,11 @@
 r3m_grad_sqnorm_ranges / r3m_clip_coef (csrc/adam.hip) at the C ABI, then through FusedAdam / FusedAdamW / FusedSGD, the encoder and the
 data-parallel wrapper.
 
-1. Bit identity. With every weight decay 0, one learning rate and a NULL coefficient a block of the grouped kernels runs adam_span /
-   sgd_span themselves, so the result must be torch.equal to r3m_adam_step_ranges / r3m_sgd_step_ranges (the CASES of
-   tests/test_gpu_optim_ranges.py, restated). A coefficient buffer holding 1.0f must give the same bits too: here grad_scale = 0.5, so
-   g * grad_scale is exact and the extra multiplication by 1 changes nothing (include/r3m_hip.h says when that holds).
+1. Bit identity. With every weight decay 0, one learning rate and a NULL coefficient a block of the step kernels runs the plain element
+   loop (adam_span_t<false, 0> / sgd_span_t<false>), which is all that r3m_adam_step_ranges / r3m_sgd_step_ranges ask of the same
+   kernels, so the result must be torch.equal to theirs (the CASES of tests/optim_cases.py): a wrongly replicated learning rate shows.
+   A coefficient buffer holding 1.0f must give the same bits too: here grad_scale = 0.5, so g * grad_scale is exact and the extra
+   multiplication by 1 changes nothing (include/r3m_hip.h says when that holds).
 
 2. One grouped Adam step against float64. The bounds extend the derivation of tests/test_gpu_optim_steps.py (its docstring; u = 2^-24,
    the float64 reference uses the very fp32 scalars the launcher passes, a fused multiply-add only removes roundings). What changes is the
@@ -42,7 +43,6 @@ data-parallel wrapper.
 6. Under the data-parallel wrapper (a forced one-rank RCCL group, as tests/test_gpu_ddp.py runs one) with grad_scale = 0.5: the clipped
    step equals the plain step on gradients multiplied by 0.5 beforehand, and last_grad_norm is half the norm of the raw gradients.
 """
-import ctypes as C
 import functools
 import math
 import os
@@ -51,23 +51,14 @@ import numpy as np
 import pytest
 import torch
 
+from optim_cases import CASES, HYPER, N, SGD, SIZES, _dd, _ll, _state
 from util import DEV, _st, rnd
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 U64 = 2.0 ** -53
-GRID_CAP = 4096 * 256                                   # f32x4 groups one trip of the capped grid covers (csrc/adam.hip opt_grid)
-SIZES = [4, 1028, 4 * GRID_CAP + 12]
 B1, B2, EPS = 0.9, 0.999, 1e-8
-
-
-def _ll(v):
-    return (C.c_longlong * len(v))(*v)
-
-
-def _dd(v):
-    return (C.c_double * len(v))(*v)
 
 
 def f32(x):
@@ -75,28 +66,6 @@ def f32(x):
 
 
 # ---- 1. bit identity with the ranged steps ------------------------------------------------------------------------------------
-N = 4 * 257 * 9 + 64
-CASES = {
-    "count4": [(8, 4, 1)],
-    "count4x257": [(16, 4 * 257, 3)],
-    "adjacent": [(0, 64, 2), (64, 1024, 2), (1088, 4, 5)],
-    "ends_at_buffer_end": [(4, 12, 1), (N - 4 * 300, 4 * 300, 7)],
-    "distinct_steps": [(0, 256, 1), (512, 2048, 2), (4096, 4 * 257, 1000), (N - 8, 8, 4)],
-    "65_ranges": [(32 * i, 4 * (1 + i % 7), 1 + i % 3) for i in range(65)],
-    "empty_range_between": [(0, 8, 1), (8, 0, 1), (16, 8, 2)],
-}
-HYPER = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, gs=0.5)
-
-
-def _state(seed, n=N):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(n, generator=g)
-    grad = torch.randn(n, generator=g) * 0.01
-    m = torch.randn(n, generator=g) * 0.01
-    v = torch.rand(n, generator=g) * 1e-4
-    return [t.to(DEV) for t in (p, grad, m, v)]
-
-
 def _inside(ranges):
     inside = torch.zeros(N, dtype=torch.bool, device=DEV)
     for off, cnt, _ in ranges:
@@ -129,10 +98,6 @@ def test_adam_groups_without_decay_and_coefficient_equal_adam_ranges(hip, case):
                 assert torch.equal(got, ref), what
                 assert torch.equal(got[~inside], before[~inside]), what
                 assert not torch.equal(got[inside], before[inside]), what
-
-
-SGD = [dict(momentum=0.0, damp=0.0, wd=0.0, nesterov=0), dict(momentum=0.9, damp=0.0, wd=0.0, nesterov=0),
-       dict(momentum=0.9, damp=0.1, wd=1e-2, nesterov=0), dict(momentum=0.9, damp=0.0, wd=1e-2, nesterov=1)]
 
 
 @pytest.mark.parametrize("cfg", SGD, ids=["plain", "momentum", "damp+wd", "nesterov"])
@@ -194,7 +159,7 @@ def state64(n):
 
 
 def adam_group_reference(p64, g64, m64, v64, lr, wd, step, scale, coef, decoupled):
-    """float64 results and bounds of ONE range (module docstring), with the launcher's fp32 scalars (csrc/adam.hip launch_adam_groups)"""
+    """float64 results and bounds of ONE range (module docstring), with the launcher's fp32 scalars (csrc/adam.hip launch_adam)"""
     a, beta2, c, eps = f32(1.0 - B1), f32(B2), f32(1.0 - B2), f32(EPS)
     neg_step = f32(-(lr / (1.0 - math.pow(B1, float(step)))))
     bc2s = f32(math.sqrt(1.0 - math.pow(B2, float(step))))

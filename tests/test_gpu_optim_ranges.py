@@ -1,45 +1,14 @@
 """The ranged optimizer steps (r3m_adam_step_ranges / r3m_sgd_step_ranges): inside every range bit for bit what r3m_adam_step /
 r3m_sgd_step on that slice with that range's step count gives, outside every range nothing is touched. Both forms run the same
-element loop, so the comparison is exact (torch.equal on p and the moments)."""
-import ctypes as C
-
+element loop of the same kernel, so the comparison is exact (torch.equal on p and the moments): it guards what the entry points hand
+that kernel, a dropped step count or offset for instance."""
 import pytest
 import torch
 
+from optim_cases import CASES, HYPER, N, SGD, _ll, _state
+from util import DEV, _st
+
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-N = 4 * 257 * 9 + 64          # a few blocks of 256 float4 groups, not a multiple of the block
-
-
-def _st():
-    from r3m_amd import _lib
-    return _lib.stream_ptr(torch.device(DEV))
-
-
-def _ll(v):
-    return (C.c_longlong * len(v))(*v)
-
-
-def _state(seed, n=N):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(n, generator=g)
-    grad = torch.randn(n, generator=g) * 0.01
-    m = torch.randn(n, generator=g) * 0.01
-    v = torch.rand(n, generator=g) * 1e-4
-    return [t.to(DEV) for t in (p, grad, m, v)]
-
-
-# (ranges [(offset, count, step)]) — multiples of 4, sorted, disjoint
-CASES = {
-    "count4": [(8, 4, 1)],
-    "count4x257": [(16, 4 * 257, 3)],
-    "adjacent": [(0, 64, 2), (64, 1024, 2), (1088, 4, 5)],
-    "ends_at_buffer_end": [(4, 12, 1), (N - 4 * 300, 4 * 300, 7)],
-    "distinct_steps": [(0, 256, 1), (512, 2048, 2), (4096, 4 * 257, 1000), (N - 8, 8, 4)],
-    "65_ranges": [(32 * i, 4 * (1 + i % 7), 1 + i % 3) for i in range(65)],
-    "empty_range_between": [(0, 8, 1), (8, 0, 1), (16, 8, 2)],
-}
-HYPER = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, gs=0.5)
 
 
 def _adam(hip, p, g, m, v, n, step, off=0):
@@ -82,10 +51,6 @@ def test_adam_ranges_inside_equal_slices_outside_untouched(hip, case):
         assert torch.equal(got, ref)
         assert torch.equal(got[~inside], before[~inside])
         assert not torch.equal(got[inside], before[inside])
-
-
-SGD = [dict(momentum=0.0, damp=0.0, wd=0.0, nesterov=0), dict(momentum=0.9, damp=0.0, wd=0.0, nesterov=0),
-       dict(momentum=0.9, damp=0.1, wd=1e-2, nesterov=0), dict(momentum=0.9, damp=0.0, wd=1e-2, nesterov=1)]
 
 
 @pytest.mark.parametrize("cfg", SGD, ids=["plain", "momentum", "damp+wd", "nesterov"])

@@ -1,12 +1,12 @@
 """-m gpu: ONE step of r3m_adam_step / r3m_sgd_step (csrc/adam.hip) from a random non-zero fp32 state against float64 on the CPU, at the
 sizes where the launch changes shape and with the scalars the other optimizer tests never pass:
 
-  * adam_kernel / sgd_kernel: n = 4 (one f32x4 group), 1028 (one block plus one group), 4 x (4096 x 256) + 12 = 4 194 316 (opt_grid caps
+  * the whole-buffer calls: n = 4 (one f32x4 group), 1028 (one block plus one group), 4 x (4096 x 256) + 12 = 4 194 316 (opt_grid caps
     the grid at 4096 blocks: the grid-stride loop takes a second, ragged trip -- three groups). No other operator test passes 4 194 304;
   * grad_scale = 0.125 and 3.0 (never anything but 1.0 elsewhere), at the C ABI and through FusedAdam / FusedSGD;
   * step = 1, 2, 1000, 10^6 (bias corrections from 0.1 / 0.001 to 1).
 
-A single step, so no error accumulates: the bounds below are derived from the count of fp32 roundings in adam_span / sgd_span, in units
+A single step, so no error accumulates: the bounds below are derived from the count of fp32 roundings in adam_span_t / sgd_span_t, in units
 of u = 2^-24 (the relative error of one correctly rounded fp32 operation; the library is built without fast-math, so `/` and sqrtf are
 correctly rounded) of the quantity's own scale. The float64 reference uses the very fp32 scalars the launcher passes (the `(float)` casts
 and adam_bias_corrections are restated here). A fused multiply-add only removes roundings. None is looser than 16 u.
@@ -36,20 +36,16 @@ import numpy as np
 import pytest
 import torch
 
+from optim_cases import SGD_CFGS, SGD_IDS, SIZES
 from util import DEV, _st, rnd
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
-GRID_CAP = 4096 * 256                                   # f32x4 groups one trip of the capped grid covers (csrc/adam.hip opt_grid)
-SIZES = [4, 1028, 4 * GRID_CAP + 12]
 STEPS = [1, 2, 1000, 10 ** 6]
 SCALES = [1.0, 0.125, 3.0]
 LR, B1, B2, EPS = 1e-4, 0.9, 0.999, 1e-8
 SGD_LR = 1e-2
-SGD_CFGS = [dict(momentum=0.0), dict(momentum=0.9), dict(momentum=0.9, dampening=0.1, weight_decay=1e-2),
-            dict(momentum=0.9, nesterov=True, weight_decay=1e-3)]            # the four of tests/test_gpu_ops.py::test_sgd_matches_torch
-SGD_IDS = ["plain", "momentum", "damp_wd", "nesterov"]
 
 
 def f32(x):
@@ -96,7 +92,7 @@ def check(what, got, ref, bound):
 @pytest.mark.parametrize("n", SIZES)
 def test_adam_single_step_against_float64(hip, n, step, scale):
     """r3m_adam_step, one step: m', v', p' within the derived bounds; elements with g = m = v = 0 keep p bit for bit and m' = v' = 0.
-    Paths first reached here: adam_kernel's grid-stride loop (n = 4 194 316: 1 048 579 groups over 4096 x 256 threads, a second trip of
+    Paths first reached here: r3m_adam_step's grid-stride loop (n = 4 194 316: 1 048 579 groups over 4096 x 256 threads, a second trip of
     three groups) and grad_scale != 1."""
     p, g, m, v, _, dead = state(n)
     p64, g64, m64, v64, _ = state64(n)
@@ -137,7 +133,7 @@ def test_adam_single_step_against_float64(hip, n, step, scale):
 def test_sgd_single_step_against_float64(hip, n, step, scale, cfg):
     """r3m_sgd_step, one step in the four configurations of test_sgd_matches_torch: buf' and p' within the derived bounds. Step 1 gets a
     NaN-filled momentum buffer, which must be initialised and not read. Without weight decay, elements with g = buf = 0 keep p bit for
-    bit. Paths first reached here: sgd_kernel's grid-stride loop (n = 4 194 316) and grad_scale != 1 (dropping it from sgd_span fails
+    bit. Paths first reached here: r3m_sgd_step's grid-stride loop (n = 4 194 316) and grad_scale != 1 (dropping it from sgd_span_t fails
     every case with scale 0.125 or 3)."""
     p, g, _, _, buf, dead = state(n)
     p64, g64, _, _, buf64 = state64(n)
