@@ -199,6 +199,34 @@ int r3m_resnet_feature_info(r3m_resnet_t h, int layer, int* C, int* H, int* W);
  * mode; in inference mode (training = 2) the copy is taken before a later block overwrites the map in place. */
 int r3m_resnet_forward_features(r3m_resnet_t h, const float* x, const float* params, float* buffers, void* arena, float* h_out,
                                 float* const feats[4], int training, r3m_stream_t stream);
+/* PREPARED INFERENCE — a frozen encoder called on one image or a handful of frames at a time (/root/reference/r3m/example.py:19-33).
+ * r3m_resnet_forward(training = 2) recomputes the eval-mode BatchNorm coefficients of every layer (one launch per convolution) and, on a
+ * bf16 plan, re-converts all weights on every call, although both change only when parameters or running statistics do.
+ *
+ * r3m_resnet_inference_prepare writes the coefficients of every BatchNorm of the plan into the arena's coefficient blocks in ONE launch
+ * (the layer table travels in the kernel arguments: no allocation, no host-to-device copy; bit for bit r3m_bn_eval_coeffs per layer)
+ * and, for a bf16 plan, the bf16 weight image. It must be called again whenever params (bf16 plans), the BatchNorm parameters or
+ * `buffers` change, and after ANY other forward of this plan on this arena (r3m_resnet_forward*, every training mode: they rewrite
+ * the coefficient blocks), which r3m_resnet_forward_prepared detects and refuses. NOT detected: another plan that ran on the same
+ * arena (plans of different frame counts or sizes lay it out differently) — prepare again after switching plans. */
+int r3m_resnet_inference_prepare(r3m_resnet_t h, const float* params, const float* buffers, void* arena, r3m_stream_t stream);
+/* Diagnostic (tests), needs no GPU: byte offset inside the arena of the coefficient block of convolution i (r3m_resnet_conv_info
+ * order): [6][Co] floats, rows mean, invstd, scale, shift (what r3m_bn_eval_coeffs writes as coef[4][Co]) and two rows a backward
+ * uses. -1 for an index out of range. */
+long long r3m_debug_resnet_coef_offset(r3m_resnet_t h, int i);
+/* Bytes of the caller-owned workspace of r3m_resnet_forward_prepared: the split-K tickets of every launch that the routing rule of
+ * r3m_conv2d_fwd_affine_small takes, then one slab area sized for the largest of them. 0 for plans without such launches (bf16 plans,
+ * large frame counts). Not part of the arena: r3m_resnet_arena_bytes and every arena offset are what they were. */
+long long r3m_resnet_inference_workspace_bytes(r3m_resnet_t h);
+/* The fused inference sequence of r3m_resnet_forward_features(training = 2) on a prepared arena: no coefficient launches, no weight
+ * conversion; the fp32 weights are read live from params. flags bit 0 set: every convolution runs the kernel it runs in
+ * r3m_resnet_forward (results bit-identical to it, embedding and feature maps). Bit 0 clear, fp32 plans: the launches the routing rule
+ * takes run the small-M split-K kernel instead (one hipMemsetAsync over the tickets per call; workspace must hold
+ * r3m_resnet_inference_workspace_bytes; results deterministic, within the fp32 ceiling of the other kernels but not their bits: K is
+ * summed in another order). bf16 plans run exactly today's kernels either way. workspace may be NULL when the plan needs none or bit 0
+ * is set. r3m_resnet_backward after it returns the "inference mode" error. */
+int r3m_resnet_forward_prepared(r3m_resnet_t h, const float* x, const float* params, void* arena, void* workspace, float* h_out,
+                                float* const feats[4], int flags, r3m_stream_t stream);
 /* r3m_resnet_backward_ex + the gradients w.r.t. those outputs: dfeats[k-1] != NULL (HOST array of four device pointers, fp32 NCHW) is
  * added to the running output gradient where autograd adds it, immediately before the backward of that stage's last block — what
  * loss.backward() does for a loss that reads convnet.layerk's output. dh == NULL: no gradient reaches the embedding (zeros flow down
@@ -345,6 +373,25 @@ int r3m_conv2d_dgrad_bnred_dt(const void* dy, const float* w_ohwi, void* dx, voi
 int r3m_conv2d_dgrad_join_dt(const void* dy, const float* w_ohwi, void* dx, void* workspace, size_t workspace_bytes, int N, int Hi,
                              int Wi, int Ci, int Co, int k, int stride, int pad, int accumulate, const void* residual_grad,
                              const unsigned* residual_bits, int dtype, r3m_stream_t stream);
+/* The small-M inference forward of one convolution (csrc/conv_small.hip): out = [relu](conv(x, w) * scale[co] + shift[co] [+ out]) like
+ * r3m_conv2d_fwd_affine_dt, fp32 only, for launches of few GEMM rows (N * Ho * Wo): 16-, 32- or 64-row x 64-column tiles on the exact
+ * fp32 MFMA, K (taps x Ci / 32 chunks) cut into S slices, one block per (tile, slice), about 1/2 - 1 x the CU count in all. Each slice
+ * block writes an fp32 slab to the workspace, releases once and draws a ticket; the block that draws the last ticket of its tile sums
+ * the S slabs in slice order and stores. No block waits for another and nothing is added with floating-point atomics: the same
+ * operands give the same bits on every launch. S = 1 uses neither ticket nor slab.
+ * Takes k in {1, 3} (pad k / 2), stride in {1, 2}, Ci a multiple of 32, Co a multiple of 64, at most 65536 rows, flags 128, 128|16 or
+ * 128|2|16; anything else returns non-zero with a message. split = 0: S by the rule; split > 0 (tests): S forced, at most the tenth
+ * value of r3m_debug_conv_small_plan. workspace: r3m_conv2d_small_workspace_bytes for the same split; the entry zeroes the tickets it
+ * uses with one hipMemsetAsync on `stream`. */
+size_t r3m_conv2d_small_workspace_bytes(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int split);
+int r3m_conv2d_fwd_affine_small(const float* x, const float* w_ohwi, float* out, const float* scale, const float* shift, int N, int Hi,
+                                int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int split, void* workspace,
+                                size_t workspace_bytes, r3m_stream_t stream);
+/* Diagnostic, runs without a GPU and launches nothing: what that entry runs with split = 0. out[0..9] = {the routing rule of
+ * r3m_resnet_forward_prepared takes this launch (a pure function of the geometry), tile rows, tile columns, S, grid (blocks), K chunks
+ * per slice, row tiles, column tiles, K chunks in all, largest split accepted}; all zero for a shape the kernel does not take.
+ * Returns 10, -1 on error. */
+int r3m_debug_conv_small_plan(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int* out, int cap);
 /* The inference forward of one convolution, as r3m_resnet_forward(training = 2) launches it (tests): out = [relu](conv(x, w) * scale[co]
  * + shift[co] [+ out]) stored by the convolution kernel itself, rounded once for bf16. flags: 128 (eval BatchNorm: the downsample
  * branch), 128 | 16 (+ ReLU: inner convolutions), 128 | 2 | 16 (+ the residual, which `out` holds on entry: a block's last

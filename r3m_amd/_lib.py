@@ -103,6 +103,13 @@ SIGNATURES = {
     "r3m_conv2d_dgrad_bnred_dt": (c_i, [c_f, c_f, c_f, c_f, c_sz] + [c_i] * 8 + [c_f] * 8 + [c_i, c_f]),
     "r3m_conv2d_dgrad_join_dt": (c_i, [c_f, c_f, c_f, c_f, c_sz] + [c_i] * 9 + [c_f, c_f, c_i, c_f]),
     "r3m_conv2d_fwd_affine_dt": (c_i, [c_f] * 5 + [c_i] * 10 + [c_f]),
+    "r3m_conv2d_small_workspace_bytes": (c_sz, [c_i] * 9),
+    "r3m_conv2d_fwd_affine_small": (c_i, [c_f] * 5 + [c_i] * 10 + [c_f, c_sz, c_f]),
+    "r3m_debug_conv_small_plan": (c_i, [c_i] * 9 + [C.POINTER(c_i), c_i]),
+    "r3m_resnet_inference_prepare": (c_i, [C.c_void_p, c_f, c_f, c_f, c_f]),
+    "r3m_resnet_inference_workspace_bytes": (c_ll, [C.c_void_p]),
+    "r3m_debug_resnet_coef_offset": (c_ll, [C.c_void_p, c_i]),
+    "r3m_resnet_forward_prepared": (c_i, [C.c_void_p, c_f, c_f, c_f, c_f, c_f, C.POINTER(C.c_void_p), c_i, c_f]),
     "r3m_conv2d_wgrad_workspace_bytes_dt": (c_sz, [c_i] * 9),
     "r3m_conv2d_wgrad_dt": (c_i, [c_f, c_f, c_f, c_f, c_sz] + [c_i] * 10 + [c_f]),
     "r3m_stem_conv_fwd_dt": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_f]),
@@ -184,7 +191,7 @@ def lib():
         try:
             fn = getattr(h, name)  # AttributeError here means header/binding/library drifted apart
         except AttributeError:
-            if ab_build and name.startswith("r3m_debug_"):
+            if ab_build:                                   # ... or entry points added since (calling one raises AttributeError)
                 continue
             raise
         fn.restype = res

@@ -141,18 +141,43 @@ int bn_train_coeffs(const float* stats, int stats_rows, long long count, const f
   return launch_bn_finalize_rows(acc, stats_rows, count, gamma, beta, running_mean, running_var, momentum, eps, o, C, s);
 }
 
-__global__ __launch_bounds__(256) void bn_eval_coeffs_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                              const float* __restrict__ rm, const float* __restrict__ rv,
-                                                              float eps, float* __restrict__ mean_o, float* __restrict__ invstd_o,
-                                                              float* __restrict__ scale_o, float* __restrict__ shift_o, int C) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
+// one channel's eval-mode coefficients from the running statistics: the arithmetic of both kernels below
+__device__ __forceinline__ void bn_eval_coeffs_one(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                                                   float* mean_o, float* invstd_o, float* scale_o, float* shift_o, int c) {
   const float invstd = 1.0f / sqrtf(rv[c] + eps);
   const float sc = gamma[c] * invstd;
   mean_o[c] = rm[c];
   invstd_o[c] = invstd;
   scale_o[c] = sc;
   shift_o[c] = fmaf(-rm[c], sc, beta[c]);
+}
+__global__ __launch_bounds__(256) void bn_eval_coeffs_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              const float* __restrict__ rm, const float* __restrict__ rv,
+                                                              float eps, float* __restrict__ mean_o, float* __restrict__ invstd_o,
+                                                              float* __restrict__ scale_o, float* __restrict__ shift_o, int C) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  bn_eval_coeffs_one(gamma, beta, rm, rv, eps, mean_o, invstd_o, scale_o, shift_o, c);
+}
+
+// The same coefficients for EVERY BatchNorm of a plan in one launch (plan_inference_prepare): the layer table travels in the kernel
+// arguments (at most 56 entries), so the call makes no allocation and no host-to-device copy. Block b serves channels
+// [256 (b - blk0), ...) of the entry whose block range holds b.
+__global__ __launch_bounds__(256) void bn_eval_coeffs_table_kernel(const float* params, const float* bufs, float* arena, const BnEvalTable t,
+                                                                    float eps) {
+  int i = 0;
+  while (i + 1 < t.n && (int)blockIdx.x >= t.e[i + 1].blk0) ++i;
+  const BnEvalEntry e = t.e[i];
+  const int c = ((int)blockIdx.x - e.blk0) * 256 + threadIdx.x;
+  if (c >= e.C) return;
+  const BnCoefOut o = bn_coef_out(arena + e.coef_off, e.C);
+  bn_eval_coeffs_one(params + e.gamma_off, params + e.beta_off, bufs + e.rm_off, bufs + e.rv_off, eps, o.mean, o.invstd, o.scale, o.shift, c);
+}
+
+int launch_bn_eval_coeffs_table(const float* params, const float* bufs, float* arena, const BnEvalTable& t, float eps, hipStream_t s) {
+  if (t.n <= 0) return 0;
+  hipLaunchKernelGGL(bn_eval_coeffs_table_kernel, dim3(t.blocks), dim3(256), 0, s, params, bufs, arena, t, eps);
+  return check_launch("bn_eval_coeffs_table");
 }
 
 int launch_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,

@@ -15,7 +15,7 @@ JOBS="${MAX_JOBS:-$(nproc 2>/dev/null || echo 8)}"
 [ "$JOBS" -ge 1 ] 2>/dev/null || JOBS=8
 [ "$JOBS" -gt 16 ] && JOBS=16
 launched=""
-SRCS="conv conv_pw wgrad wgrad_win conv_bf16 wgrad_bf16 conv_row16 conv_pw16 stem stem_bf16 stem_dgrad stem_gen bn bn_pool feat loss adam lang text augment engine capi"
+SRCS="conv conv_pw conv_small wgrad wgrad_win conv_bf16 wgrad_bf16 conv_row16 conv_pw16 stem stem_bf16 stem_dgrad stem_gen bn bn_pool feat loss adam lang text augment engine capi"
 for f in $SRCS; do
   [ -f "$HERE/$f.hip" ] || continue
   stale=0

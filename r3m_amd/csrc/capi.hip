@@ -382,6 +382,54 @@ int r3m_conv2d_fwd_affine_dt(const void* x, const void* w, void* out, const floa
               "(128, 128|16 or 128|2|16 on a fusing route): the engine runs conv + bn_act_fwd here", flags);
   return conv_forward_launch_affine(FP(x), FP(w), FPM(out), scale, shift, g, flags, dtype, S(stream));
 }
+size_t r3m_conv2d_small_workspace_bytes(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int split) {
+  const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
+  const int fl = EPI_AFFINE | EPI_RELU;
+  if (!small_conv_plan(g, fl, split).grid) return 0;
+  return small_conv_ctr_bytes(g, fl, split) + small_conv_slab_bytes(g, fl, split);
+}
+int r3m_conv2d_fwd_affine_small(const float* x, const float* w, float* out, const float* scale, const float* shift, int N, int Hi, int Wi,
+                                int Ci, int Co, int k, int stride, int pad, int flags, int split, void* workspace, size_t workspace_bytes,
+                                r3m_stream_t stream) {
+  R3M_REQUIRE(x && w && out && scale && shift, "conv2d_fwd_affine_small: null argument");
+  const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
+  const SmallConvPlan r = small_conv_plan(g, flags, split);
+  if (!r.grid || split < 0 || split > small_conv_max_split(g))      // a shape, flag set or split the kernel does not take: the launcher says why
+    return launch_conv_small(x, w, out, scale, shift, g, flags, split, nullptr, nullptr, S(stream));
+  const size_t ctr = small_conv_ctr_bytes(g, flags, split), need = ctr + small_conv_slab_bytes(g, flags, split);
+  R3M_REQUIRE(workspace && workspace_bytes >= need, "conv2d_fwd_affine_small: the workspace has %zu bytes, this launch needs %zu "
+              "(r3m_conv2d_small_workspace_bytes)", workspace ? workspace_bytes : (size_t)0, need);
+  if (r.S > 1 && hipMemsetAsync(workspace, 0, ctr, S(stream)) != hipSuccess) {
+    set_last_error("conv2d_fwd_affine_small: cannot reset the tickets");
+    return 1;
+  }
+  return launch_conv_small(x, w, out, scale, shift, g, flags, split, static_cast<unsigned*>(workspace),
+                           reinterpret_cast<float*>(static_cast<char*>(workspace) + ctr), S(stream));
+}
+int r3m_debug_conv_small_plan(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int* out, int cap) {
+  if (!out || cap < 10) { set_last_error("debug_conv_small_plan: the output buffer needs 10 ints"); return -1; }
+  const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
+  const SmallConvPlan r = small_conv_plan(g, flags, 0);
+  const int v[10] = {r.take, r.bm, r.bn, r.S, r.grid, r.cps, r.tiles_m, r.tiles_n, r.nch, r.grid ? small_conv_max_split(g) : 0};
+  for (int i = 0; i < 10; ++i) out[i] = v[i];
+  return 10;
+}
+int r3m_resnet_inference_prepare(r3m_resnet_t h, const float* params, const float* buffers, void* arena, r3m_stream_t stream) {
+  R3M_REQUIRE(h && params && buffers && arena, "resnet_inference_prepare: null argument");
+  return plan_inference_prepare(*PLAN(h), params, buffers, static_cast<float*>(arena), S(stream));
+}
+long long r3m_debug_resnet_coef_offset(r3m_resnet_t h, int i) {
+  int g[10];
+  if (!h || plan_conv_info(PLAN(h), i, g)) return -1;
+  return plan_coef_offset(PLAN(h), i) * 4;
+}
+long long r3m_resnet_inference_workspace_bytes(r3m_resnet_t h) { return h ? plan_inference_workspace_bytes(PLAN(h)) : -1; }
+int r3m_resnet_forward_prepared(r3m_resnet_t h, const float* x, const float* params, void* arena, void* workspace, float* h_out,
+                                float* const feats[4], int flags, r3m_stream_t stream) {
+  R3M_REQUIRE(h && x && params && arena && h_out, "resnet_forward_prepared: null argument");
+  R3M_REQUIRE((flags & ~1) == 0, "resnet_forward_prepared: flags=%d (bit 0: no split-K kernel)", flags);
+  return plan_forward_prepared(*PLAN(h), x, params, static_cast<float*>(arena), workspace, h_out, feats, flags, S(stream));
+}
 int r3m_conv2d_dgrad(const float* dy, const float* w, float* dx, void* ws, size_t ws_bytes, int N, int Hi, int Wi, int Ci, int Co,
                      int k, int stride, int pad, r3m_stream_t stream) {
   return r3m_conv2d_dgrad_dt(dy, w, dx, ws, ws_bytes, N, Hi, Wi, Ci, Co, k, stride, pad, DT_F32, stream);

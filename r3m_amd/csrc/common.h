@@ -239,7 +239,7 @@ struct BnCoefOut { float* mean; float* invstd; float* scale; float* shift; };   
 struct BnBwdOut { float* dgamma; float* dbeta; float* c1; float* c2; int accumulate; };   // what a backward's combine writes (accumulate: sums +=)
 // A layer's coefficient block [6][C] = {mean, invstd, scale, shift, c1, c2}: these three know the row order, nobody else does
 static inline BnCoef bn_coef_block(const float* k, int C) { return {k + 2LL * C, k + 3LL * C, k, k + C, k + 4LL * C, k + 5LL * C}; }
-static inline BnCoefOut bn_coef_out(float* k, int C) { return {k, k + C, k + 2LL * C, k + 3LL * C}; }
+__host__ __device__ static inline BnCoefOut bn_coef_out(float* k, int C) { return {k, k + C, k + 2LL * C, k + 3LL * C}; }
 static inline BnBwdOut bn_bwd_out(float* dgamma, float* dbeta, float* k, int C, int accumulate) {
   return {dgamma, dbeta, k + 4LL * C, k + 5LL * C, accumulate};
 }
@@ -254,6 +254,11 @@ int bn_bwd_partial_rows(long long rows, int C, int dt);
 int bn_debug_geometry(long long rows, int C, int dt, int* out, int cap);   // r3m_debug_bn_geometry: what the launchers pick, nothing launched
 int launch_bn_eval_coeffs(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
                           const BnCoefOut& o, int C, hipStream_t s);
+// every BatchNorm of a plan at once: offsets into the flat parameter / running-statistics buffers and the arena (floats); a by-value
+// kernel argument
+struct BnEvalEntry { long long gamma_off, beta_off, rm_off, rv_off, coef_off; int C, blk0; };
+struct BnEvalTable { BnEvalEntry e[56]; int n, blocks; };
+int launch_bn_eval_coeffs_table(const float* params, const float* bufs, float* arena, const BnEvalTable& t, float eps, hipStream_t s);
 // Z = [relu](bn(Y) [+ R]); K2 != null: R is a second raw conv output with its own BatchNorm, Z = [relu](bn(Y) + bn2(R))
 int launch_bn_act_fwd(const void* Y, const BnCoef& K, const void* R, const BnCoef* K2, void* Z, long long rows, int C, int relu,
                       unsigned* maskbits, int dt, hipStream_t s);

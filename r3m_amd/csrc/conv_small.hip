@@ -1,0 +1,235 @@
+// r3m_amd — forward convolution for SMALL row counts (one image or a handful of frames per call): a split-K gather-GEMM on the exact-fp32
+// MFMA (v_mfma_f32_16x16x4_f32) with 16-, 32- or 64-row tiles and an in-launch, deterministic, wait-free reduction.
+//
+// Operands as the other forward kernels: NHWC fp32 input, OHWI fp32 weights (both K-contiguous), k in {1, 3}, stride in {1, 2}; the
+// three inference stores EPI_AFFINE [| EPI_RELU] [| EPI_ACCUM | EPI_RELU]. Why another kernel: the 128 x 128 / 256 x 64 tiles of conv.hip /
+// conv_pw.hip were sized for thousands of row tiles. At one frame a layer4 launch is 49 rows: a handful of blocks on a 256-CU part,
+// each walking the whole K with most of its rows empty. Here
+//   * a block is 4 waves over BM x 64 outputs, BM = 16 * MT (MT = 1, 2, 4): wave w owns columns 16 w .. 16 w + 15 and all BM rows;
+//   * K (taps x Ci / 32 chunks of 32) is cut into S slices, one block per (row tile, column tile, slice), S chosen so that the grid is
+//     about 1/2 - 1 x the CU count (small_conv_plan below; a slice boundary may fall inside a tap);
+//   * nothing goes through LDS: a weight element is used by one wave only and the few input rows are L2-resident, so each lane loads
+//     its fragments straight to registers (16 B per load, two loads per operand and chunk) one chunk ahead of the MFMAs. Lane l holds
+//     k = 16 h + 4 (l >> 4) + j of chunk half h in element j for BOTH operands, so step (h, j) of the MFMA chain multiplies like k;
+//   * S > 1: every block writes its accumulators as one fp32 slab (16 B per lane and row group, fragment order), the block performs ONE
+//     agent-scope release and draws a ticket from its tile's counter; the block that draws S - 1 performs ONE agent-scope acquire, sums
+//     the S slabs IN SLICE ORDER (its own included, read back like the others), applies scale / shift, the residual and the ReLU and
+//     stores. No block waits for another one: no spinning, no grid barrier, no floating-point atomics — the same operands give the same
+//     bits on every launch whichever block arrives last. S = 1 stores from the accumulators and touches neither counter nor slab.
+// The counters are zeroed by a hipMemsetAsync ahead of the launch (the C entry does it per launch, the engine once per forward).
+#include "engine.h"
+#include <algorithm>
+#include <cstring>
+
+namespace r3m {
+
+struct SmallConvParams {
+  const float* x;
+  const float* w;
+  float* out;
+  const float* scale;
+  const float* shift;
+  float* slabs;          // [tiles][S][MT][256] f32x4 (S > 1)
+  unsigned* ctr;         // [tiles] tickets, zero before the launch (S > 1)
+  int Hi, Wi, Ci, Co, Ho, Wo, M;
+  int k, stride, pad, flags;
+  int tiles_n;           // Co / 64
+  int S, cps, nch, cpt;  // slices, chunks per slice, chunks in all (taps * Ci / 32), chunks per tap (Ci / 32)
+};
+
+template <int MT>
+struct SmallFrag {
+  f32x4 a[MT][2];
+  f32x4 b[2];
+};
+
+template <int MT>
+__global__ __launch_bounds__(256) void conv_small_kernel(const SmallConvParams p) {
+  __shared__ int s_ticket;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int slice = blockIdx.x % p.S, tile = blockIdx.x / p.S;
+  const int tn = tile % p.tiles_n, tm = tile / p.tiles_n;
+  const int col = tn * 64 + wave * 16 + r;               // < Co: Co is a multiple of 64
+  const int T = p.k * p.k;
+
+  // the MT input rows this lane feeds (A operand): their pixel origin, or "no row"
+  int iy0[MT], ix0[MT];
+  long long img[MT];
+  bool rowok[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int row = (tm * MT + m) * 16 + r;
+    rowok[m] = row < p.M;
+    const int rr = rowok[m] ? row : 0;
+    const int n = rr / (p.Ho * p.Wo), rem = rr - n * (p.Ho * p.Wo);
+    const int oy = rem / p.Wo, ox = rem - oy * p.Wo;
+    iy0[m] = oy * p.stride - p.pad;
+    ix0[m] = ox * p.stride - p.pad;
+    img[m] = (long long)n * p.Hi * p.Wi;
+  }
+  const float* wcol = p.w + (long long)col * T * p.Ci + q * 4;
+
+  const int c0 = slice * p.cps, c1 = min(c0 + p.cps, p.nch);
+  int tap = c0 / p.cpt, kc = c0 - tap * p.cpt;            // chunk c = (tap, kc): advanced by next()
+  auto load = [&](SmallFrag<MT>& f) {
+    const int kh = tap / p.k, kw = tap - kh * p.k;
+    const int koff = kc * 32 + q * 4;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int iy = iy0[m] + kh, ix = ix0[m] + kw;
+      const bool ok = rowok[m] && iy >= 0 && iy < p.Hi && ix >= 0 && ix < p.Wi;
+      // a padding tap or a row past M loads from the tensor's first pixel and is zeroed afterwards: no branch around the loads
+      const float* src = p.x + (ok ? (img[m] + (long long)iy * p.Wi + ix) * p.Ci : 0LL) + koff;
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(src), v1 = *reinterpret_cast<const f32x4*>(src + 16);
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      f.a[m][0] = ok ? v0 : z;
+      f.a[m][1] = ok ? v1 : z;
+    }
+    const float* wsrc = wcol + (long long)tap * p.Ci + kc * 32;
+    f.b[0] = *reinterpret_cast<const f32x4*>(wsrc);
+    f.b[1] = *reinterpret_cast<const f32x4*>(wsrc + 16);
+  };
+  auto next = [&]() { if (++kc == p.cpt) { kc = 0; ++tap; } };
+
+  f32x4 acc[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (c0 < c1) {
+    SmallFrag<MT> cur, nxt;
+    load(cur);
+    for (int c = c0; c < c1; ++c) {
+      next();
+      const bool more = c + 1 < c1;                        // block-uniform
+      if (more) load(nxt);
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.a[m][h][j], cur.b[h][j], acc[m], 0, 0, 0);
+      if (more) cur = nxt;
+    }
+  }
+
+  if (p.S > 1) {
+    f32x4* slab = reinterpret_cast<f32x4*>(p.slabs);
+    const long long base = ((long long)tile * p.S) * (MT * 256) + tid;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) slab[base + ((long long)slice * MT + m) * 256] = acc[m];
+    // publish: every wave drains its stores, the block meets, ONE lane releases at agent scope, waits once more, then draws the ticket
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      s_ticket = (int)__hip_atomic_fetch_add(p.ctr + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (s_ticket != p.S - 1) return;                       // not the last slice of this tile to arrive: done, nobody waits
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+#pragma unroll
+    for (int m = 0; m < MT; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int s = 0; s < p.S; ++s)                          // slice order, whoever arrived last
+#pragma unroll
+      for (int m = 0; m < MT; ++m) acc[m] += slab[base + ((long long)s * MT + m) * 256];
+  }
+
+  // store: lane holds column `col` of rows 4 q + i of each 16-row group
+  const float sc = p.scale[col], sh = p.shift[col];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = (tm * MT + m) * 16 + q * 4 + i;
+      if (row >= p.M) continue;
+      float* o = p.out + (long long)row * p.Co + col;
+      float v = fmaf(acc[m][i], sc, sh);
+      if (p.flags & EPI_ACCUM) v += *o;
+      if (p.flags & EPI_RELU) v = fmaxf(v, 0.f);
+      *o = v;
+    }
+}
+
+// ---- host: the plan (pure), the sizes, the launcher ----
+static const char* small_conv_refuses(const ConvGeom& c, int flags) {
+  if (c.N < 1 || c.Hi < 1 || c.Wi < 1) return "empty input";
+  if (c.k != 1 && c.k != 3) return "k must be 1 or 3";
+  if (c.stride != 1 && c.stride != 2) return "stride must be 1 or 2";
+  if (c.pad != (c.k == 3 ? 1 : 0)) return "pad must be 1 (k = 3) or 0 (k = 1)";
+  if (c.Ci < 32 || (c.Ci & 31)) return "Ci must be a multiple of 32";
+  if (c.Co < 64 || (c.Co & 63)) return "Co must be a multiple of 64";
+  if (c.Ho() < 1 || c.Wo() < 1) return "empty output";
+  if ((long long)c.N * c.Ho() * c.Wo() > SMALL_CONV_ROWS_MAX) return "more rows than the kernel is built for";
+  if (flags != EPI_AFFINE && flags != (EPI_AFFINE | EPI_RELU) && flags != (EPI_AFFINE | EPI_ACCUM | EPI_RELU))
+    return "epilogue flags must be 128, 128|16 or 128|2|16";
+  return nullptr;
+}
+
+int small_conv_max_split(const ConvGeom& c) { return std::min(SMALL_CONV_SPLIT_MAX, c.k * c.k * (c.Ci / 32)); }
+
+SmallConvPlan small_conv_plan(const ConvGeom& c, int flags, int split) {
+  SmallConvPlan r;
+  memset(&r, 0, sizeof r);
+  if (small_conv_refuses(c, flags)) return r;
+  const int M = c.M();
+  r.bm = M <= 16 ? 16 : M <= 32 ? 32 : 64;
+  r.bn = 64;
+  r.tiles_m = ceil_div(M, r.bm);
+  r.tiles_n = c.Co / 64;
+  r.nch = c.k * c.k * (c.Ci / 32);
+  const int tiles = r.tiles_m * r.tiles_n;
+  int S = split;
+  if (S <= 0) {
+    // decomposition first: blocks = tiles * S about 1/2 - 1 x the 256 CUs, a slice no shorter than 4 chunks (128 k)
+    S = std::max(1, std::min(std::min(256 / tiles, r.nch / 4), SMALL_CONV_SPLIT_MAX));
+    r.cps = ceil_div(r.nch, S);
+    S = ceil_div(r.nch, r.cps);                       // no empty slice
+  } else {
+    r.cps = ceil_div(r.nch, S);                       // forced (tests): trailing slices may be empty, they contribute zero slabs
+  }
+  r.S = S;
+  r.grid = tiles * S;
+  // the routing rule, from the per-launch A/B in profiles/small_batch_latency.txt: while the tiles fit the CUs in one round this
+  // kernel's time is one block's latency over a K slice, and the kernels of conv.hip / conv_pw.hip pay for the whole K in a few
+  // 128-row tiles (ratios 1.1 - 10); from about 400 blocks on they win (0.45 - 0.93)
+  r.take = tiles <= SMALL_CONV_TAKE_TILES && r.nch >= SMALL_CONV_TAKE_CHUNKS ? 1 : 0;
+  return r;
+}
+
+static size_t small_ctr_bytes(const SmallConvPlan& r) { return ((size_t)r.tiles_m * r.tiles_n * 4 + 255) / 256 * 256; }
+size_t small_conv_ctr_bytes(const ConvGeom& c, int flags, int split) { return small_ctr_bytes(small_conv_plan(c, flags, split)); }
+size_t small_conv_slab_bytes(const ConvGeom& c, int flags, int split) {
+  const SmallConvPlan r = small_conv_plan(c, flags, split);
+  return (size_t)r.S * r.tiles_m * r.bm * c.Co * 4;
+}
+
+int launch_conv_small(const float* x, const float* w, float* out, const float* scale, const float* shift, const ConvGeom& c, int flags,
+                      int split, unsigned* ctr, float* slabs, hipStream_t s) {
+  if (const char* why = small_conv_refuses(c, flags)) {
+    set_last_error("conv2d_fwd_affine_small: %s (N=%d %dx%d Ci=%d Co=%d k=%d stride=%d pad=%d flags=%d)", why, c.N, c.Hi, c.Wi, c.Ci, c.Co,
+                   c.k, c.stride, c.pad, flags);
+    return 1;
+  }
+  R3M_REQUIRE(split >= 0 && split <= small_conv_max_split(c), "conv2d_fwd_affine_small: split=%d outside 0..%d", split, small_conv_max_split(c));
+  const SmallConvPlan r = small_conv_plan(c, flags, split);
+  R3M_REQUIRE(r.S == 1 || (ctr && slabs), "conv2d_fwd_affine_small: %d slices need a workspace", r.S);
+  SmallConvParams p;
+  p.x = x; p.w = w; p.out = out; p.scale = scale; p.shift = shift; p.slabs = slabs; p.ctr = ctr;
+  p.Hi = c.Hi; p.Wi = c.Wi; p.Ci = c.Ci; p.Co = c.Co; p.Ho = c.Ho(); p.Wo = c.Wo(); p.M = c.M();
+  p.k = c.k; p.stride = c.stride; p.pad = c.pad; p.flags = flags;
+  p.tiles_n = r.tiles_n; p.S = r.S; p.cps = r.cps; p.nch = r.nch; p.cpt = c.Ci / 32;
+  switch (r.bm) {
+    case 16: hipLaunchKernelGGL(conv_small_kernel<1>, dim3(r.grid), dim3(256), 0, s, p); break;
+    case 32: hipLaunchKernelGGL(conv_small_kernel<2>, dim3(r.grid), dim3(256), 0, s, p); break;
+    default: hipLaunchKernelGGL(conv_small_kernel<4>, dim3(r.grid), dim3(256), 0, s, p); break;
+  }
+  return check_launch("conv_small");
+}
+
+}  // namespace r3m

@@ -61,6 +61,23 @@ int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial
 size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt);     // split-K scratch of that launch: plan.split slabs
 WgradPlan conv_wgrad_plan(const ConvGeom& c, int dt);       // what conv_wgrad_launch would run (r3m_debug_wgrad_route)
 
+// ---- the small-M split-K forward (conv_small.hip): inference stores only, fp32 ----
+constexpr int SMALL_CONV_ROWS_MAX = 1 << 16;   // rows the entry accepts at all
+constexpr int SMALL_CONV_SPLIT_MAX = 32;       // most K slices (the last arriver reads that many slabs of its tile serially)
+constexpr int SMALL_CONV_TAKE_TILES = 256;     // the routing rule: the launch's tiles fit the 256 CUs in one round (S keeps the grid there) ...
+constexpr int SMALL_CONV_TAKE_CHUNKS = 4;      // ... and K is at least this many chunks of 32 (below, a 1 x 1 over 64 channels, both kernels tie)
+// What one launch runs: a pure function of the geometry, the flags and the forced split (0 = the rule's). take: the routing rule sends
+// this launch here (all zero: the kernel does not take the shape at all). grid = tiles_m * tiles_n * S blocks; slice s covers chunks
+// [s * cps, min((s + 1) * cps, nch)) of the taps * Ci / 32 chunks of 32 k.
+struct SmallConvPlan { int take, bm, bn, tiles_m, tiles_n, S, cps, nch, grid; };
+SmallConvPlan small_conv_plan(const ConvGeom& c, int flags, int split);
+int small_conv_max_split(const ConvGeom& c);
+size_t small_conv_ctr_bytes(const ConvGeom& c, int flags, int split);    // one ticket per tile, padded to 256 bytes
+size_t small_conv_slab_bytes(const ConvGeom& c, int flags, int split);   // S slabs of tiles_m * bm rows x Co
+// ctr: the launch's zeroed tickets, slabs: its slab area (both may be null when the plan has one slice)
+int launch_conv_small(const float* x, const float* w, float* out, const float* scale, const float* shift, const ConvGeom& c, int flags,
+                      int split, unsigned* ctr, float* slabs, hipStream_t s);
+
 // ---- the plan ----
 struct Plan;
 struct FrameSource;   // augment_dev.h: raw clips + crop boxes
@@ -72,6 +89,12 @@ void plan_destroy(Plan* P);
 // exported right behind the stage's last block on s; frames through x_nchw only
 int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena, float* h_out,
                  int training, hipStream_t s, float* const* feats = nullptr);
+// prepared inference (engine.hip): coefficients (bf16: weight image) once, then forwards without the per-layer coefficient launches;
+// flags bit 0: no launch goes to conv_small.hip
+int plan_inference_prepare(Plan& P, const float* params, const float* bufs, float* arena, hipStream_t s);
+long long plan_inference_workspace_bytes(Plan* P);
+int plan_forward_prepared(Plan& P, const float* x_nchw, const float* params, float* arena, void* workspace, float* h_out, float* const* feats,
+                          int flags, hipStream_t s);
 // dh == nullptr: the embedding received no gradient. dfeats (optional): dfeats[k-1] != null is the gradient w.r.t. that output of
 // the forward, fp32 NCHW; every staged call carries the same array, the stage that owns an entry (stage 4 - k) reads it
 int plan_backward(Plan& P, const float* dh, const float* params, float* grads, float* arena, int stage_begin, int stage_end,
@@ -81,6 +104,7 @@ int plan_out_dim(Plan* P);
 int plan_input_hw(Plan* P, int* H, int* W);
 int plan_num_convs(Plan* P);
 int plan_conv_info(Plan* P, int i, int* geo10);
+long long plan_coef_offset(Plan* P, int i);   // arena offset (floats) of convolution i's coefficient block [6][Co]
 int plan_dtype(Plan* P);
 long long plan_num_params(Plan* P);
 long long plan_num_buffers(Plan* P);

@@ -12,7 +12,7 @@
 //
 // File order: the layer table and Plan (layout, options, RunState) -> plan_create -> the convolution launch helpers of engine.h ->
 // Ctx (one call's view of plan + buffers) and the tile-counter guard -> forward (stem_forward, block_forward, block_forward_fused,
-// plan_forward) -> backward (BatchNorm / dgrad / wgrad helpers, SideStream, block_backward, stem_backward, plan_backward) -> accessors.
+// plan_forward, forward_sequence; prepared inference: plan_inference_prepare, plan_forward_prepared) -> backward (BatchNorm / dgrad / wgrad helpers, SideStream, block_backward, stem_backward, plan_backward) -> accessors.
 // The BatchNorm helpers only pick pointers, gradient destinations and work bits: the launch sequences themselves (bn_train_coeffs, bn_bwd,
 // bn_bwd_pair, bn_bwd_pool) are in bn.hip / bn_pool.hip, shared with the C ABI.
 #include "engine.h"
@@ -109,6 +109,8 @@ struct RunState {
   WtEntry* d_wt_tab = nullptr;      // device copies of wt_tab / wt_tile0, made at the first backward (plan creation needs no GPU)
   int* d_wt_tile0 = nullptr;
   SideStream side;
+  const float* prepared = nullptr;   // the arena whose coefficient blocks (bf16: weight image too) plan_inference_prepare filled and no
+                                     // other forward of this plan has touched since; null: plan_forward_prepared refuses
 };
 
 // Layout (set by plan_create; forward and backward see it const), two options, and the run state.
@@ -139,6 +141,10 @@ struct Plan {
   long long wt_elems = 0;
   // options (plan_set_*)
   int fuse_bnred = 1;       // BatchNorm-backward partials from the producing dgrad's epilogue (EPI_BNRED); 0: stand-alone reduce pass
+  // the small-M kernel (conv_small.hip) in a prepared forward: per convolution its ticket block inside the caller's workspace (-1: the
+  // routing rule leaves the launch where it is), all ticket blocks first (one memset per call), one slab area behind them for all
+  std::vector<long long> small_ctr_off;
+  long long small_ctr_bytes = 0, small_slab_bytes = 0;
   std::vector<unsigned char> trainable;   // plan_set_trainable: one byte per tensor, empty = all trainable (read by the next stage 0)
   int bn_pair = R3M_BN_PAIR_DEFAULT;   // the two tail BatchNorms of a downsample block share their backward passes (bn_backward_pair); 0: separate passes
   RunState run;
@@ -401,6 +407,16 @@ Plan* plan_create(int size, int F, int dtype, int H, int W) {
     if (emax > 0) P.E_off = take(emax);
   }
   P.arena_floats = off;
+  P.small_ctr_off.assign(P.convs.size(), -1);
+  if (dtype == DT_F32)
+    for (size_t i = 1; i < P.convs.size(); ++i) {
+      const ConvGeom g = P.convs[i].geom(F);
+      const int fl = EPI_AFFINE | EPI_RELU;   // the plan does not depend on which of the three stores the launch makes
+      if (!small_conv_plan(g, fl, 0).take) continue;
+      P.small_ctr_off[i] = P.small_ctr_bytes;
+      P.small_ctr_bytes += (long long)small_conv_ctr_bytes(g, fl, 0);
+      P.small_slab_bytes = std::max(P.small_slab_bytes, (long long)small_conv_slab_bytes(g, fl, 0));
+    }
   return Pp;
 }
 
@@ -547,6 +563,8 @@ struct Ctx {
   int training;
   int accumulate;
   int dt;
+  bool prepared = false;            // plan_forward_prepared: the eval coefficients (and the bf16 weight image) are in the arena already
+  char* small_ws = nullptr;         // plan_forward_prepared: the caller's workspace when the small-M kernel may run, else null
   // where BatchNorm backward puts d gamma / d beta of layer L: the flat gradient buffer, or plan scratch when no parameter gradient
   // is wanted (the sums themselves are still formed: train-mode dz needs c1 / c2 from the same pass)
   // (a frozen gamma / beta counts as unwanted: its range of the gradient buffer is never written)
@@ -600,6 +618,7 @@ static const float* fwd_weights(Ctx& c, const ConvSpec& L) {
 // training: the statistics partials a forward launch left (L.stats_rows rows) -> batch coefficients (+ running-statistics update);
 // eval / inference: running statistics -> coefficients
 static int bn_forward_coeffs(Ctx& c, const ConvSpec& L) {
+  if (c.prepared) return 0;
   const float* gamma = c.params + L.gamma_off;
   const float* beta = c.params + L.beta_off;
   const BnCoefOut o = bn_coef_out(c.arena + L.coef_off, L.Co);
@@ -675,6 +694,9 @@ static bool block_fusable(Ctx& c, const BlockSpec& B) {
 }
 static int conv_bn_fused(Ctx& c, const ConvSpec& L, const float* X, float* out, int flags) {
   TRY(bn_forward_coeffs(c, L));
+  if (const long long co = c.P.small_ctr_off[&L - c.P.convs.data()]; c.small_ws && co >= 0)
+    return launch_conv_small(X, c.params + L.w_off, out, c.coef(L).scale, c.coef(L).shift, L.geom(c.P.F), flags, 0,
+                             reinterpret_cast<unsigned*>(c.small_ws + co), reinterpret_cast<float*>(c.small_ws + c.P.small_ctr_bytes), c.s);
   TileCounters tc(c, TileCounters::FORWARD, L);
   return conv_forward_launch_affine(X, fwd_weights(c, L), out, c.coef(L).scale, c.coef(L).shift, L.geom(c.P.F), flags, c.dt, c.s);
 }
@@ -700,6 +722,8 @@ static int block_forward_fused(Ctx& c, const BlockSpec& B, float* Xin, float** o
 // the last block of its stage: its output is torchvision's layer`stage + 1` output
 static bool ends_stage(const Plan& P, size_t bi) { return bi + 1 == P.blocks.size() || P.blocks[bi + 1].stage != P.blocks[bi].stage; }
 
+static int forward_sequence(Ctx& c, const float* x_nchw, const FrameSource* crop, float* h_out, bool infer, bool fused, float* const* feats);
+
 int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const float* params, float* bufs, float* arena, float* h_out,
                  int training, hipStream_t s, float* const* feats) {
   // training: 1 = batch statistics (+ running-statistics update), 0 = running statistics with everything a backward needs kept,
@@ -710,14 +734,22 @@ int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const fl
   R3M_REQUIRE(!crop || (P.H == 224 && P.W == 224), "resnet_forward_crop: the crops are 224 x 224 but this plan takes %d x %d frames "
               "(create it for 224 x 224)", P.H, P.W);
   R3M_REQUIRE(!(crop && feats), "resnet_forward_crop: feature maps are not available on the crop-fed forward");
-  c.R.last_training = training;
+  c.R.prepared = nullptr;            // this forward rewrites the coefficient blocks (a bf16 plan: the weight image too)
+  if (c.dt == DT_BF16) TRY(launch_convert_bf16(params, arena + P.w16_off, P.n_params, s));   // bf16 image of every weight (45 MB for ResNet-50)
+  return forward_sequence(c, x_nchw, crop, h_out, infer, infer && g_fused_inference, feats);
+}
+
+// stem -> blocks -> pool on c's stream; fused: the inference sequence (block_forward_fused where every launch of the block has the stores)
+static int forward_sequence(Ctx& c, const float* x_nchw, const FrameSource* crop, float* h_out, bool infer, bool fused, float* const* feats) {
+  const Plan& P = c.P;
+  float* arena = c.arena;
+  hipStream_t s = c.s;
+  c.R.last_training = c.training;
   c.R.last_crop = crop ? 1 : 0;
   c.R.next_stage = infer ? -3 : 0;   // a new forward invalidates whatever an unfinished backward left behind (-3: nothing to differentiate)
   c.R.dout_fused_rows = 0;
   TRY(TileCounters::reset(c, TileCounters::FORWARD));
-  if (c.dt == DT_BF16) TRY(launch_convert_bf16(params, arena + P.w16_off, P.n_params, s));   // bf16 image of every weight (45 MB for ResNet-50)
   TRY(stem_forward(c, x_nchw, crop));
-  const bool fused = infer && g_fused_inference;
   float* cur = arena + P.blocks[0].in_off;
   for (size_t bi = 0; bi < P.blocks.size(); ++bi) {
     const BlockSpec& B = P.blocks[bi];
@@ -733,6 +765,40 @@ int plan_forward(Plan& P, const float* x_nchw, const FrameSource* crop, const fl
   }
   const BlockSpec& last = P.blocks.back();
   return launch_avgpool_fwd(cur, h_out, P.F, last.Ho * last.Wo, last.Co, c.dt, s);
+}
+
+// ---- prepared inference: the eval coefficients of every BatchNorm (bf16 plans: the weight image too) are written ONCE, by
+// plan_inference_prepare; plan_forward_prepared then runs the fused inference sequence without the per-layer coefficient launches and
+// without the weight conversion, and (fp32) sends the launches the routing rule of conv_small.hip takes to that kernel ----
+int plan_inference_prepare(Plan& P, const float* params, const float* bufs, float* arena, hipStream_t s) {
+  BnEvalTable t;
+  R3M_REQUIRE(P.convs.size() <= sizeof(t.e) / sizeof(t.e[0]), "resnet_inference_prepare: %d BatchNorms do not fit the table", (int)P.convs.size());
+  t.n = 0; t.blocks = 0;
+  for (const ConvSpec& L : P.convs) {
+    t.e[t.n++] = BnEvalEntry{L.gamma_off, L.beta_off, L.rm_off, L.rv_off, L.coef_off, L.Co, t.blocks};
+    t.blocks += ceil_div(L.Co, 256);
+  }
+  P.run.prepared = nullptr;
+  TRY(launch_bn_eval_coeffs_table(params, bufs, arena, t, 1e-5f, s));
+  if (P.dtype == DT_BF16) TRY(launch_convert_bf16(params, arena + P.w16_off, P.n_params, s));
+  P.run.prepared = arena;
+  return 0;
+}
+long long plan_inference_workspace_bytes(Plan* P) { return P->small_ctr_bytes + P->small_slab_bytes; }
+int plan_forward_prepared(Plan& P, const float* x_nchw, const float* params, float* arena, void* workspace, float* h_out, float* const* feats,
+                          int flags, hipStream_t s) {
+  R3M_REQUIRE(P.run.prepared && P.run.prepared == arena, "resnet_forward_prepared: this arena is not prepared for the plan (call "
+              "r3m_resnet_inference_prepare first; any other forward of the plan invalidates the preparation)");
+  const bool small = !(flags & 1) && P.small_ctr_bytes > 0;
+  R3M_REQUIRE(!small || workspace, "resnet_forward_prepared: the plan needs a workspace of r3m_resnet_inference_workspace_bytes");
+  Ctx c{P, P.run, params, nullptr, nullptr, arena, s, 0, 0, P.dtype};
+  c.prepared = true;
+  c.small_ws = small ? static_cast<char*>(workspace) : nullptr;
+  if (small && hipMemsetAsync(workspace, 0, (size_t)P.small_ctr_bytes, s) != hipSuccess) {
+    set_last_error("resnet_forward_prepared: cannot reset the split-K tickets");
+    return 1;
+  }
+  return forward_sequence(c, x_nchw, nullptr, h_out, true, true, feats);
 }
 
 // ---- backward -----------------------------------------------------------------------------------------------
@@ -1114,6 +1180,7 @@ int plan_feature_info(Plan* P, int layer, int* C, int* H, int* W) {
   set_last_error("feature_info: the plan has no layer%d", layer);
   return 1;
 }
+long long plan_coef_offset(Plan* P, int i) { return P->convs[i].coef_off; }
 int plan_dtype(Plan* P) { return P->dtype; }
 long long plan_num_params(Plan* P) { return P->n_params; }
 long long plan_num_buffers(Plan* P) { return P->n_buffers; }

@@ -185,6 +185,7 @@ class HipResNet(nn.Module):
         self._scratch = None          # _LiveSlot for forwards without a backward while every ring slot is live (_pick_slot)
         self._plan_masks = {}     # native handle -> the trainable mask it was last given (absent: all trainable, the plan's default)
         self._stage_hook = None   # callable(stage, offset, count) after each backward stage (data-parallel wrapper)
+        self._epoch = 0           # moves whenever the project itself writes the flat buffers (params_written); InferenceSession compares it
         self.reset_parameters()
 
     @property
@@ -289,11 +290,29 @@ class HipResNet(nn.Module):
         self._flat_p, self._flat_b, self._flat_nbt = flat_p, flat_b, flat_nbt
         self._grads.drop()          # (every .grad was cleared above)
         self._drop_arenas()
+        self.params_written()
 
     def _apply(self, fn, *a, **k):
         super()._apply(fn, *a, **k)
         self._reflatten()
         return self
+
+    def params_written(self):
+        """Every writer of the flat parameter / running-statistics buffers that the project owns calls this: the fused optimizers' steps,
+        a train-mode forward, load_state_dict, _apply / re-flatten. What an InferenceSession derived from the buffers (eval-mode BatchNorm
+        coefficients, the bf16 weight image) is rebuilt when the epoch has moved. Foreign writers (a raw in-place write through a
+        parameter's .data, a hand-written optimizer) call it too, or InferenceSession.refresh()."""
+        self._epoch += 1
+
+    def _load_from_state_dict(self, *a, **k):
+        # runs once per load_state_dict that reaches this module, called on it or on any parent (R3M, SingleDevice)
+        super()._load_from_state_dict(*a, **k)
+        self.params_written()
+
+    def inference_session(self):
+        """A low-latency frozen-encoder caller for one image or a handful of frames per call: see inference.InferenceSession."""
+        from .inference import InferenceSession
+        return InferenceSession(self)
 
     def flat_params(self):
         self._ensure()
@@ -461,6 +480,7 @@ class HipResNet(nn.Module):
                            "resnet_forward_features")
         if training:
             self._flat_nbt += 1
+            self.params_written()       # the running statistics moved
         slot.generation += 1
         slot.F, slot.hw = F, hw
         return out, maps, si, slot.generation

@@ -100,6 +100,12 @@ class R3M(nn.Module):
             obs = resize_center_crop(obs.reshape(-1, *obs.shape[-3:]))
         return self.convnet.forward_features(obs, layers)
 
+    def inference_session(self, obs_shape=[3, 224, 224]):
+        """A low-latency frozen-encoder caller (HipResNet.inference_session) behind the same Resize(256) + CenterCrop(224) branch as
+        forward: sess(obs) -> [F, outdim] for one image or a handful of frames per call, no autograd."""
+        from .inference import InferenceSession
+        return InferenceSession(self.convnet, resize=list(obs_shape) != [3, 224, 224])
+
     def sim(self, tensor1, tensor2):
         if self.l2dist:
             return -torch.linalg.norm(tensor1 - tensor2, dim=-1)

@@ -243,6 +243,8 @@ class _FlatOptimizer(torch.optim.Optimizer):
             plan = self._plan(i, o)            # what torch.optim steps: the tensors with a gradient since zero_grad()
             if plan is not None:
                 plans.append((i, o, plan))
+                if hasattr(o, "params_written"):
+                    o.params_written()         # the step about to be enqueued rewrites this owner's flat parameters
         max_norm = self.max_grad_norm
         if max_norm is None or not plans:
             return plans, None

@@ -122,6 +122,9 @@ class SingleDevice(nn.Module):
     def finish_gradient_sync(self):
         pass
 
+    def inference_session(self, *a, **k):
+        return self.module.inference_session(*a, **k)
+
 
 class ReplicatedInference(nn.Module):
     """Opt-in multi-GPU INFERENCE for `load_r3m` users: the reference returns `DataParallel(rep)`, which splits an inference batch
@@ -144,6 +147,10 @@ class ReplicatedInference(nn.Module):
             raise RuntimeError("ReplicatedInference: no GPU visible")
         self._replicas = None      # plain list on purpose: replicas are not sub-modules (not in state_dict(), not moved by .to())
         self._stamp = None
+
+    def inference_session(self, *a, **k):
+        """a session on the wrapped module (one device: a call of one image or a handful of frames is not worth splitting)"""
+        return self.module.inference_session(*a, **k)
 
     def _structure_stamp(self):
         """What a replica's STRUCTURE depends on: which tensors the module holds (a load_state_dict with assign, .to(), a re-flatten
