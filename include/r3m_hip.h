@@ -461,6 +461,20 @@ int r3m_avgpool_bwd_dt(const float* dh, void* dx, int N, int HW, int C, int dtyp
 /* nn.Linear (+ReLU) of LanguageReward.pred (r3m/models/models_language.py:43-51): y[M,N] = x[M,K] w[N,K]^T + b */
 int r3m_linear_fwd(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int relu,
                    r3m_stream_t stream);
+/* The same Linear over FEW rows on the split-K kernel of csrc/conv_small.hip: the launch of the 1 x 1 geometry (M, 1, 1, K, N, 1, 1, 0),
+ * with that kernel's tiles, slices, slabs and tickets (r3m_conv2d_fwd_affine_small) and a Linear store in place of the affine one.
+ * flags: 8 (y = x w^T + bias), 8 | 16 (+ ReLU: the reward head), 8 | 256 (the exact GELU 0.5 v (1 + erf(v / sqrt 2)) of v = acc + bias:
+ * the text model's lin1). Takes K a multiple of 32, N a multiple of 64, 1 <= M <= 65536; a convolution flag set (128 ...) or anything
+ * else returns non-zero with a message. split and workspace as r3m_conv2d_fwd_affine_small: split = 0 is the rule's S, the workspace is
+ * r3m_linear_small_workspace_bytes for the same split (0 for a shape the kernel refuses), and the entry zeroes its tickets with one
+ * hipMemsetAsync on `stream`. The same operands give the same bits on every launch. */
+size_t r3m_linear_small_workspace_bytes(int M, int K, int N, int split);
+int r3m_linear_fwd_small(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int flags, int split,
+                         void* workspace, size_t workspace_bytes, r3m_stream_t stream);
+/* Diagnostic, runs without a GPU and launches nothing: the ten integers of r3m_debug_conv_small_plan for that Linear (one planner: it
+ * IS the plan of the 1 x 1 geometry); out[0] is the routing rule r3m_langrew_infer and r3m_text_forward_small follow. All zero for a
+ * shape or a flag set the Linear entry refuses. Returns 10, -1 on error. */
+int r3m_debug_linear_small_plan(int M, int K, int N, int flags, int* out, int cap);
 
 /* RandomResizedCrop resample of the rc / rctraj augmentations (r3m/utils/data_loaders.py:47-50,81-102): crop box
  * boxes[n / frames_per_box] = {top, left, height, width} (host-drawn), bilinear resize to Ho x Wo (align_corners=False),
@@ -513,6 +527,16 @@ int r3m_langrew_call_forward(const float* e0, const float* eg, const float* le, 
 int r3m_langrew_call_backward(const float* dscore, const float* params, float* grads, float* de0, float* deg, float* dle,
                               void* workspace, size_t workspace_bytes, int R, int D, int hidden, int lang_dim, int accumulate,
                               r3m_stream_t stream);
+/* The same evaluation WITHOUT a backward, for one frame or a handful per call: score[R] = G(e0, eg[R,D], le), fp32, same parameter
+ * layout. R0 is the row count of e0 [R0,D] and le [R0,lang_dim]: R0 == R is one row per frame, R0 == 1 broadcasts ONE first frame and
+ * ONE instruction to all R rows (inside the concat kernel); any other R0 is refused. Launches on `stream`: concat, ONE memset over the
+ * tickets of all four hidden Linears, the four Linears (flags 8 | 16) and the final GEMV. A hidden Linear runs on the few-row kernel
+ * (r3m_linear_fwd_small's) where r3m_debug_linear_small_plan says take, else on the launch r3m_langrew_call_forward runs: a pure
+ * function of (R, D, hidden, lang_dim). The workspace keeps only what a forward needs: the input rows, two hidden buffers, the tickets
+ * and ONE slab area sized for the largest launch. */
+size_t r3m_langrew_infer_workspace_bytes(int R, int D, int hidden, int lang_dim);
+int r3m_langrew_infer(const float* e0, const float* eg, const float* le, const float* params, float* score, void* workspace,
+                      size_t workspace_bytes, int R, int R0, int D, int hidden, int lang_dim, r3m_stream_t stream);
 
 /* ---------------- sentence features: the DistilBERT forward of LangEncoder (r3m/models/models_language.py:13-35) ----------------
  * What the reference reaches through transformers' DistilBertModel under no_grad, then last_hidden_state.mean(1). Inference only,
@@ -539,6 +563,13 @@ int r3m_text_tensor_info(const int* dims, int index, char* name, int name_cap, l
 size_t r3m_text_workspace_bytes(const int* dims, int B, int T);
 int r3m_text_forward(const int* ids, const int* mask, const float* params, float* feats, float* hidden, void* workspace,
                      size_t workspace_bytes, int B, int T, const int* dims, int pool, r3m_stream_t stream);
+/* r3m_text_forward for few rows (B * T): the same sequence, the same arguments and refusals, but a Linear that
+ * r3m_debug_linear_small_plan takes at B * T rows runs on the few-row kernel (QKV, the output Linear and lin2 with flags 8, lin1 with
+ * 8 | 256, so no bias + GELU launch follows it); a Linear the plan leaves makes exactly r3m_text_forward's launches. One memset over
+ * all tickets per call. The workspace (r3m_text_small_workspace_bytes) is r3m_text_forward's plus the tickets and one slab area. */
+size_t r3m_text_small_workspace_bytes(const int* dims, int B, int T);
+int r3m_text_forward_small(const int* ids, const int* mask, const float* params, float* feats, float* hidden, void* workspace,
+                           size_t workspace_bytes, int B, int T, const int* dims, int pool, r3m_stream_t stream);
 /* The model's own kernels, one by one (all pointers 16-byte aligned, C a multiple of 4).
  * r3m_text_embed: y[b,t,:] = LayerNorm(word[clamp(ids[b,t], 0, vocab - 1)] + pos[t]); word [vocab][C], pos [>= T][C].
  * r3m_layernorm_fwd: y = LayerNorm(x (+ residual, may be NULL)) over the last dimension of [rows][C], biased variance, two passes (a

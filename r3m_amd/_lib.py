@@ -132,6 +132,9 @@ SIGNATURES = {
     "r3m_avgpool_fwd_dt": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "r3m_avgpool_bwd_dt": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "r3m_linear_fwd": (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_linear_small_workspace_bytes": (c_sz, [c_i] * 4),
+    "r3m_linear_fwd_small": (c_i, [c_f, c_f, c_f, c_f] + [c_i] * 5 + [c_f, c_sz, c_f]),
+    "r3m_debug_linear_small_plan": (c_i, [c_i] * 4 + [C.POINTER(c_i), c_i]),
     "r3m_crop_resize": (c_i, [c_f, c_i, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_resize_crop": (c_i, [c_f, c_i, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_resize_crop_backward": (c_i, [c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
@@ -144,11 +147,15 @@ SIGNATURES = {
     "r3m_langrew_call_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "r3m_langrew_call_forward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_f]),
     "r3m_langrew_call_backward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_langrew_infer_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "r3m_langrew_infer": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_text_num_params": (c_ll, [C.POINTER(c_i)]),
     "r3m_text_num_tensors": (c_i, [C.POINTER(c_i)]),
     "r3m_text_tensor_info": (c_i, [C.POINTER(c_i), c_i, C.c_char_p, c_i, C.POINTER(c_ll), C.POINTER(c_ll), C.POINTER(c_i), C.POINTER(c_i)]),
     "r3m_text_workspace_bytes": (c_sz, [C.POINTER(c_i), c_i, c_i]),
     "r3m_text_forward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, C.POINTER(c_i), c_i, c_f]),
+    "r3m_text_small_workspace_bytes": (c_sz, [C.POINTER(c_i), c_i, c_i]),
+    "r3m_text_forward_small": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, C.POINTER(c_i), c_i, c_f]),
     "r3m_text_embed": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_fl, c_f]),
     "r3m_layernorm_fwd": (c_i, [c_f, c_f, c_f, c_f, c_f, c_ll, c_i, c_fl, c_f]),
     "r3m_bias_gelu": (c_i, [c_f, c_f, c_ll, c_i, c_f]),

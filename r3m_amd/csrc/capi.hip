@@ -392,6 +392,8 @@ int r3m_conv2d_fwd_affine_small(const float* x, const float* w, float* out, cons
                                 int Ci, int Co, int k, int stride, int pad, int flags, int split, void* workspace, size_t workspace_bytes,
                                 r3m_stream_t stream) {
   R3M_REQUIRE(x && w && out && scale && shift, "conv2d_fwd_affine_small: null argument");
+  R3M_REQUIRE(!small_linear_flags(flags), "conv2d_fwd_affine_small: epilogue flags %d are a Linear store (r3m_linear_fwd_small); this entry "
+              "takes 128, 128|16 or 128|2|16", flags);
   const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
   const SmallConvPlan r = small_conv_plan(g, flags, split);
   if (!r.grid || split < 0 || split > small_conv_max_split(g))      // a shape, flag set or split the kernel does not take: the launcher says why
@@ -661,6 +663,50 @@ int r3m_avgpool_bwd(const float* dh, float* dx, int N, int HW, int C, r3m_stream
 int r3m_linear_fwd(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int relu, r3m_stream_t stream) {
   return conv_forward_launch(x, w, y, nullptr, bias, {M, 1, 1, K, N, 1, 1, 0}, (bias ? EPI_BIAS : 0) | (relu ? EPI_RELU : 0), DT_F32, S(stream));
 }
+// few rows: the split-K kernel of conv_small.hip on the 1 x 1 geometry, Linear stores
+static const char* linear_small_refuses(int M, int K, int N, int flags) {
+  if (!small_linear_flags(flags)) return "flags must be 8 (bias), 8|16 (+ ReLU) or 8|256 (+ GELU); the convolution stores belong to r3m_conv2d_fwd_affine_small";
+  if (M < 1) return "M must be at least 1";
+  if (K < 32 || (K & 31)) return "K must be a multiple of 32";
+  if (N < 64 || (N & 63)) return "N must be a multiple of 64";
+  return small_conv_refuses({M, 1, 1, K, N, 1, 1, 0}, flags);
+}
+size_t r3m_linear_small_workspace_bytes(int M, int K, int N, int split) {
+  const ConvGeom g{M, 1, 1, K, N, 1, 1, 0};
+  const int fl = EPI_BIAS;
+  if (linear_small_refuses(M, K, N, fl) || !small_conv_plan(g, fl, split).grid) return 0;
+  return small_conv_ctr_bytes(g, fl, split) + small_conv_slab_bytes(g, fl, split);
+}
+int r3m_linear_fwd_small(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int flags, int split,
+                         void* workspace, size_t workspace_bytes, r3m_stream_t stream) {
+  R3M_REQUIRE(x && w && bias && y, "linear_fwd_small: null argument");
+  if (const char* why = linear_small_refuses(M, K, N, flags)) {
+    set_last_error("linear_fwd_small: %s (M=%d K=%d N=%d flags=%d)", why, M, K, N, flags);
+    return 1;
+  }
+  const ConvGeom g{M, 1, 1, K, N, 1, 1, 0};
+  R3M_REQUIRE(split >= 0 && split <= small_conv_max_split(g), "linear_fwd_small: split=%d outside 0..%d", split, small_conv_max_split(g));
+  const size_t ctr = small_conv_ctr_bytes(g, flags, split), need = ctr + small_conv_slab_bytes(g, flags, split);
+  const SmallConvPlan r = small_conv_plan(g, flags, split);
+  R3M_REQUIRE(r.S == 1 || workspace, "linear_fwd_small: %d slices need a workspace (r3m_linear_small_workspace_bytes)", r.S);
+  R3M_REQUIRE(!workspace || workspace_bytes >= need, "linear_fwd_small: the workspace has %zu bytes, this launch needs %zu "
+              "(r3m_linear_small_workspace_bytes)", workspace_bytes, need);
+  if (r.S > 1 && hipMemsetAsync(workspace, 0, ctr, S(stream)) != hipSuccess) {
+    set_last_error("linear_fwd_small: cannot reset the tickets");
+    return 1;
+  }
+  return launch_conv_small(x, w, y, nullptr, bias, g, flags, split, static_cast<unsigned*>(workspace),
+                           workspace ? reinterpret_cast<float*>(static_cast<char*>(workspace) + ctr) : nullptr, S(stream));
+}
+int r3m_debug_linear_small_plan(int M, int K, int N, int flags, int* out, int cap) {
+  if (!out || cap < 10) { set_last_error("debug_linear_small_plan: the output buffer needs 10 ints"); return -1; }
+  for (int i = 0; i < 10; ++i) out[i] = 0;
+  if (const char* why = linear_small_refuses(M, K, N, flags)) {
+    set_last_error("debug_linear_small_plan: %s (M=%d K=%d N=%d flags=%d)", why, M, K, N, flags);
+    return 10;
+  }
+  return r3m_debug_conv_small_plan(M, 1, 1, K, N, 1, 1, 0, flags, out, cap);
+}
 
 long long r3m_langrew_num_params(int D, int hidden, int lang_dim) { return langrew_num_params(D, hidden, lang_dim); }
 size_t r3m_langrew_workspace_bytes(int B, int D, int hidden, int lang_dim) { return langrew_ws_floats(B, D, hidden, lang_dim) * 4; }
@@ -702,6 +748,17 @@ int r3m_langrew_call_backward(const float* dscore, const float* params, float* g
   R3M_REQUIRE(ws_bytes >= r3m_langrew_call_workspace_bytes(R, D, hidden, lang_dim), "langrew_call_backward: workspace too small");
   return langrew_call_backward(dscore, params, grads, de0, deg, dle, static_cast<float*>(ws), R, D, hidden, lang_dim, accumulate,
                                S(stream));
+}
+size_t r3m_langrew_infer_workspace_bytes(int R, int D, int hidden, int lang_dim) { return langrew_infer_ws_bytes(R, D, hidden, lang_dim); }
+int r3m_langrew_infer(const float* e0, const float* eg, const float* le, const float* params, float* score, void* ws, size_t ws_bytes,
+                      int R, int R0, int D, int hidden, int lang_dim, r3m_stream_t stream) {
+  R3M_REQUIRE(e0 && eg && le && params && score && ws, "langrew_infer: null argument");
+  const size_t need = r3m_langrew_infer_workspace_bytes(R, D, hidden, lang_dim);
+  if (!need) return 1;                                     // refused dims: the message is set
+  R3M_REQUIRE(ws_bytes >= need, "langrew_infer: the workspace has %zu bytes, this call needs %zu (r3m_langrew_infer_workspace_bytes)",
+              ws_bytes, need);
+  R3M_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "langrew_infer: the workspace must be 16-byte aligned");
+  return langrew_infer(e0, eg, le, params, score, ws, R, R0, D, hidden, lang_dim, S(stream));
 }
 
 int r3m_crop_resize(const void* frames, int frames_are_u8, const int* boxes, float* out, long long N, int C, int Hi, int Wi, int Ho,

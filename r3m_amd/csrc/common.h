@@ -62,7 +62,11 @@ enum : int {
   EPI_AFFINE     = 128, // forward only (round 6, the inference path): out = acc * bn_scale[col] + bn_shift[col] — eval-mode BatchNorm
                         // (running statistics) applied where the convolution result is stored; then EPI_ACCUM (+ the residual already
                         // in `out`) and EPI_RELU in that order: relu(bn(conv(x)) + identity) of a block tail in ONE store.
+  EPI_GELU       = 256, // few-row Linear only (conv_small.hip), with EPI_BIAS: out = gelu(acc + bias[col]), the exact form (gelu_erf)
 };
+
+// the exact GELU 0.5 v (1 + erf(v / sqrt 2)): bias_gelu_kernel (text.hip) and the EPI_GELU store (conv_small.hip) share this arithmetic
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 // rows of the EPI_BNRED partial buffer one launch writes ([rows][2][Nc] floats): one per 64 GEMM rows, tile-independent
 static inline int bnred_partial_rows(long long M) { return (int)((M + 63) / 64); }
@@ -344,6 +348,10 @@ int langrew_call_forward(const float* e0, const float* eg, const float* le, cons
                          int D, int H, int LD, hipStream_t s);
 int langrew_call_backward(const float* dscore, const float* params, float* grads, float* de0, float* deg, float* dle, float* ws,
                           int R, int D, int H, int LD, int accumulate, hipStream_t s);
+// one evaluation without a backward on the few-row kernel (R0: rows of e0 / le, R or 1); the workspace in bytes, 0 for refused dims
+size_t langrew_infer_ws_bytes(int R, int D, int H, int LD);
+int langrew_infer(const float* e0, const float* eg, const float* le, const float* params, float* score, void* workspace, int R, int R0,
+                  int D, int H, int LD, hipStream_t s);
 
 // ---- optional per-kernel-class HIP-event timing (bench.py roofline; off by default, zero cost when off) ----
 enum { KC_GEMM_WIDE = 0, KC_GEMM_NARROW = 1, KC_WGRAD_WIDE = 2, KC_WGRAD_NARROW = 3, KC_COUNT = 4 };

@@ -17,6 +17,11 @@
 //     stores. No block waits for another one: no spinning, no grid barrier, no floating-point atomics — the same operands give the same
 //     bits on every launch whichever block arrives last. S = 1 stores from the accumulators and touches neither counter nor slab.
 // The counters are zeroed by a hipMemsetAsync ahead of the launch (the C entry does it per launch, the engine once per forward).
+//
+// A Linear over few rows is the same launch: the 1 x 1 geometry (M, 1, 1, K, N, 1, 1, 0) makes the main loop y[M, N] = x[M, K] w[N, K]^T.
+// Only the store differs, so the store is a template parameter (SmallStore): the convolution instantiations keep the affine store
+// above, the Linear ones store acc + bias[col] with an optional ReLU (EPI_BIAS [| EPI_RELU]: the reward head) or through the exact GELU
+// (EPI_BIAS | EPI_GELU: the text model's lin1). Main loop, slabs, tickets and the slice-order sum are one body for all of them.
 #include "engine.h"
 #include <algorithm>
 #include <cstring>
@@ -27,8 +32,8 @@ struct SmallConvParams {
   const float* x;
   const float* w;
   float* out;
-  const float* scale;
-  const float* shift;
+  const float* scale;    // affine store only
+  const float* shift;    // the affine store's shift; the bias of the Linear stores
   float* slabs;          // [tiles][S][MT][256] f32x4 (S > 1)
   unsigned* ctr;         // [tiles] tickets, zero before the launch (S > 1)
   int Hi, Wi, Ci, Co, Ho, Wo, M;
@@ -43,7 +48,9 @@ struct SmallFrag {
   f32x4 b[2];
 };
 
-template <int MT>
+enum SmallStore : int { ST_AFFINE = 0, ST_BIAS = 1, ST_BIAS_GELU = 2 };
+
+template <int MT, int ST>
 __global__ __launch_bounds__(256) void conv_small_kernel(const SmallConvParams p) {
   __shared__ int s_ticket;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -141,23 +148,40 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallConvParams p
   }
 
   // store: lane holds column `col` of rows 4 q + i of each 16-row group
-  const float sc = p.scale[col], sh = p.shift[col];
+  if constexpr (ST == ST_AFFINE) {
+    const float sc = p.scale[col], sh = p.shift[col];
 #pragma unroll
-  for (int m = 0; m < MT; ++m)
+    for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = (tm * MT + m) * 16 + q * 4 + i;
-      if (row >= p.M) continue;
-      float* o = p.out + (long long)row * p.Co + col;
-      float v = fmaf(acc[m][i], sc, sh);
-      if (p.flags & EPI_ACCUM) v += *o;
-      if (p.flags & EPI_RELU) v = fmaxf(v, 0.f);
-      *o = v;
-    }
+      for (int i = 0; i < 4; ++i) {
+        const int row = (tm * MT + m) * 16 + q * 4 + i;
+        if (row >= p.M) continue;
+        float* o = p.out + (long long)row * p.Co + col;
+        float v = fmaf(acc[m][i], sc, sh);
+        if (p.flags & EPI_ACCUM) v += *o;
+        if (p.flags & EPI_RELU) v = fmaxf(v, 0.f);
+        *o = v;
+      }
+  } else {
+    const float b = p.shift[col];
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = (tm * MT + m) * 16 + q * 4 + i;
+        if (row >= p.M) continue;
+        float v = acc[m][i] + b;
+        if constexpr (ST == ST_BIAS_GELU) v = gelu_erf(v);
+        else if (p.flags & EPI_RELU) v = fmaxf(v, 0.f);
+        p.out[(long long)row * p.Co + col] = v;
+      }
+  }
 }
 
 // ---- host: the plan (pure), the sizes, the launcher ----
-static const char* small_conv_refuses(const ConvGeom& c, int flags) {
+bool small_linear_flags(int flags) { return flags == EPI_BIAS || flags == (EPI_BIAS | EPI_RELU) || flags == (EPI_BIAS | EPI_GELU); }
+
+const char* small_conv_refuses(const ConvGeom& c, int flags) {
   if (c.N < 1 || c.Hi < 1 || c.Wi < 1) return "empty input";
   if (c.k != 1 && c.k != 3) return "k must be 1 or 3";
   if (c.stride != 1 && c.stride != 2) return "stride must be 1 or 2";
@@ -166,8 +190,8 @@ static const char* small_conv_refuses(const ConvGeom& c, int flags) {
   if (c.Co < 64 || (c.Co & 63)) return "Co must be a multiple of 64";
   if (c.Ho() < 1 || c.Wo() < 1) return "empty output";
   if ((long long)c.N * c.Ho() * c.Wo() > SMALL_CONV_ROWS_MAX) return "more rows than the kernel is built for";
-  if (flags != EPI_AFFINE && flags != (EPI_AFFINE | EPI_RELU) && flags != (EPI_AFFINE | EPI_ACCUM | EPI_RELU))
-    return "epilogue flags must be 128, 128|16 or 128|2|16";
+  if (flags != EPI_AFFINE && flags != (EPI_AFFINE | EPI_RELU) && flags != (EPI_AFFINE | EPI_ACCUM | EPI_RELU) && !small_linear_flags(flags))
+    return "epilogue flags must be 128, 128|16 or 128|2|16 (convolution) or 8, 8|16 or 8|256 (Linear)";
   return nullptr;
 }
 
@@ -209,26 +233,34 @@ size_t small_conv_slab_bytes(const ConvGeom& c, int flags, int split) {
   return (size_t)r.S * r.tiles_m * r.bm * c.Co * 4;
 }
 
+template <int ST>
+static void launch_small_tile(const SmallConvParams& p, const SmallConvPlan& r, hipStream_t s) {
+  switch (r.bm) {
+    case 16: hipLaunchKernelGGL((conv_small_kernel<1, ST>), dim3(r.grid), dim3(256), 0, s, p); break;
+    case 32: hipLaunchKernelGGL((conv_small_kernel<2, ST>), dim3(r.grid), dim3(256), 0, s, p); break;
+    default: hipLaunchKernelGGL((conv_small_kernel<4, ST>), dim3(r.grid), dim3(256), 0, s, p); break;
+  }
+}
+
 int launch_conv_small(const float* x, const float* w, float* out, const float* scale, const float* shift, const ConvGeom& c, int flags,
                       int split, unsigned* ctr, float* slabs, hipStream_t s) {
+  const char* what = small_linear_flags(flags) ? "linear_fwd_small" : "conv2d_fwd_affine_small";
   if (const char* why = small_conv_refuses(c, flags)) {
-    set_last_error("conv2d_fwd_affine_small: %s (N=%d %dx%d Ci=%d Co=%d k=%d stride=%d pad=%d flags=%d)", why, c.N, c.Hi, c.Wi, c.Ci, c.Co,
-                   c.k, c.stride, c.pad, flags);
+    set_last_error("%s: %s (N=%d %dx%d Ci=%d Co=%d k=%d stride=%d pad=%d flags=%d)", what, why, c.N, c.Hi, c.Wi, c.Ci, c.Co, c.k, c.stride,
+                   c.pad, flags);
     return 1;
   }
-  R3M_REQUIRE(split >= 0 && split <= small_conv_max_split(c), "conv2d_fwd_affine_small: split=%d outside 0..%d", split, small_conv_max_split(c));
+  R3M_REQUIRE(split >= 0 && split <= small_conv_max_split(c), "%s: split=%d outside 0..%d", what, split, small_conv_max_split(c));
   const SmallConvPlan r = small_conv_plan(c, flags, split);
-  R3M_REQUIRE(r.S == 1 || (ctr && slabs), "conv2d_fwd_affine_small: %d slices need a workspace", r.S);
+  R3M_REQUIRE(r.S == 1 || (ctr && slabs), "%s: %d slices need a workspace", what, r.S);
   SmallConvParams p;
   p.x = x; p.w = w; p.out = out; p.scale = scale; p.shift = shift; p.slabs = slabs; p.ctr = ctr;
   p.Hi = c.Hi; p.Wi = c.Wi; p.Ci = c.Ci; p.Co = c.Co; p.Ho = c.Ho(); p.Wo = c.Wo(); p.M = c.M();
   p.k = c.k; p.stride = c.stride; p.pad = c.pad; p.flags = flags;
   p.tiles_n = r.tiles_n; p.S = r.S; p.cps = r.cps; p.nch = r.nch; p.cpt = c.Ci / 32;
-  switch (r.bm) {
-    case 16: hipLaunchKernelGGL(conv_small_kernel<1>, dim3(r.grid), dim3(256), 0, s, p); break;
-    case 32: hipLaunchKernelGGL(conv_small_kernel<2>, dim3(r.grid), dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL(conv_small_kernel<4>, dim3(r.grid), dim3(256), 0, s, p); break;
-  }
+  if (!small_linear_flags(flags)) launch_small_tile<ST_AFFINE>(p, r, s);
+  else if (flags & EPI_GELU) launch_small_tile<ST_BIAS_GELU>(p, r, s);
+  else launch_small_tile<ST_BIAS>(p, r, s);
   return check_launch("conv_small");
 }
 

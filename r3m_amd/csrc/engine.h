@@ -61,7 +61,10 @@ int conv_wgrad_launch(const float* X, const float* dY, float* dW, float* partial
 size_t conv_wgrad_ws_floats(const ConvGeom& c, int dt);     // split-K scratch of that launch: plan.split slabs
 WgradPlan conv_wgrad_plan(const ConvGeom& c, int dt);       // what conv_wgrad_launch would run (r3m_debug_wgrad_route)
 
-// ---- the small-M split-K forward (conv_small.hip): inference stores only, fp32 ----
+// ---- the small-M split-K forward (conv_small.hip): inference stores only, fp32. A Linear over few rows is the launch of the 1 x 1
+// geometry (M, 1, 1, K, N, 1, 1, 0) with a Linear flag set (EPI_BIAS, EPI_BIAS | EPI_RELU, EPI_BIAS | EPI_GELU): `shift` is its bias,
+// `scale` is not read. One rule, one planner: the same refusals, take, tile, S and grid for both families (the per-launch A/B of the
+// head's and the text model's Linears, profiles/reward_latency.txt, asked for no tighter rule: every launch it takes is faster). ----
 constexpr int SMALL_CONV_ROWS_MAX = 1 << 16;   // rows the entry accepts at all
 constexpr int SMALL_CONV_SPLIT_MAX = 32;       // most K slices (the last arriver reads that many slabs of its tile serially)
 constexpr int SMALL_CONV_TAKE_TILES = 256;     // the routing rule: the launch's tiles fit the 256 CUs in one round (S keeps the grid there) ...
@@ -72,6 +75,8 @@ constexpr int SMALL_CONV_TAKE_CHUNKS = 4;      // ... and K is at least this man
 struct SmallConvPlan { int take, bm, bn, tiles_m, tiles_n, S, cps, nch, grid; };
 SmallConvPlan small_conv_plan(const ConvGeom& c, int flags, int split);
 int small_conv_max_split(const ConvGeom& c);
+bool small_linear_flags(int flags);                                      // one of the three Linear flag sets
+const char* small_conv_refuses(const ConvGeom& c, int flags);            // null, or why the kernel does not take the launch at all
 size_t small_conv_ctr_bytes(const ConvGeom& c, int flags, int split);    // one ticket per tile, padded to 256 bytes
 size_t small_conv_slab_bytes(const ConvGeom& c, int flags, int split);   // S slabs of tiles_m * bm rows x Co
 // ctr: the launch's zeroed tickets, slabs: its slab area (both may be null when the plan has one slice)

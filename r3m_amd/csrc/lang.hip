@@ -10,6 +10,7 @@
 // Parameter layout (flat, = state-dict order pred.{0,2,4,6,8}.{weight,bias}): W1[H][K1] b1[H] W2[H][H] b2 W3 b3 W4 b4 w5[H] b5[1]
 #include "engine.h"
 #include "conv_dev.h"
+#include <algorithm>
 
 namespace r3m {
 
@@ -366,14 +367,16 @@ int langrew_backward(const float* dscore, const int* iperm, const float* params,
 // LanguageReward.forward, models_language.py:53-55), 15 of them per step in trainer.py:72-92. Same MLP core as the batched
 // pass; the input rows are the concatenation [e0 | eg | le] staged by one copy kernel, the input gradient is split back.
 __global__ __launch_bounds__(256) void lang_concat_kernel(const float* __restrict__ e0, const float* __restrict__ eg,
-                                                           const float* __restrict__ le, float* __restrict__ X, int D, int LD) {
+                                                           const float* __restrict__ le, float* __restrict__ X, int D, int LD,
+                                                           int one_first) {
   const long long row = blockIdx.x;
+  const long long r0 = one_first ? 0 : row;              // one_first: e0 and le hold ONE row, broadcast to every row of X
   float* x = X + row * (2LL * D + LD);
   for (int d = threadIdx.x * 4; d < D; d += 1024) {
-    *reinterpret_cast<f32x4*>(x + d) = ld4g(e0 + row * D + d);
+    *reinterpret_cast<f32x4*>(x + d) = ld4g(e0 + r0 * D + d);
     *reinterpret_cast<f32x4*>(x + D + d) = ld4g(eg + row * D + d);
   }
-  for (int d = threadIdx.x * 4; d < LD; d += 1024) *reinterpret_cast<f32x4*>(x + 2 * D + d) = ld4g(le + row * LD + d);
+  for (int d = threadIdx.x * 4; d < LD; d += 1024) *reinterpret_cast<f32x4*>(x + 2 * D + d) = ld4g(le + r0 * LD + d);
 }
 
 __global__ __launch_bounds__(256) void lang_split_kernel(const float* __restrict__ dX, float* __restrict__ de0, float* __restrict__ deg,
@@ -392,9 +395,87 @@ int langrew_call_forward(const float* e0, const float* eg, const float* le, cons
                          int D, int H, int LD, hipStream_t s) {
   const LangDims d = lang_dims_rows(R, 0, D, H, LD);
   if (int e = check_dims(d)) return e;
-  hipLaunchKernelGGL(lang_concat_kernel, dim3(R), dim3(256), 0, s, e0, eg, le, ws + d.X, D, LD);
+  hipLaunchKernelGGL(lang_concat_kernel, dim3(R), dim3(256), 0, s, e0, eg, le, ws + d.X, D, LD, 0);
   if (int e = check_launch("lang_concat")) return e;
   return mlp_forward(d, params, score, ws, DT_F32, s);
+}
+
+// ---- the same evaluation WITHOUT a backward (a reward per control step: one frame or a handful per call). Nothing is kept for a
+// gradient: the input rows, two hidden buffers that the four Linears ping-pong between, and the split-K workspace of the few-row
+// kernel (conv_small.hip): a ticket block per Linear the rule takes, zeroed by ONE memset, and ONE slab area sized for the largest
+// launch (the launches are ordered on the stream). A Linear the rule leaves runs the conv_forward_launch of mlp_forward. The routing
+// is small_conv_plan(...).take of each layer's geometry: a pure function of (R, D, H, LD). Offsets in bytes, multiples of 256.
+struct LangInferWs {
+  size_t X, Ha, Hb, ctr0, ctr_bytes, ctr[4], slabs, total;
+  bool take[4];
+};
+static LangInferWs lang_infer_ws(int R, int D, int H, int LD) {
+  LangInferWs w;
+  const size_t K1 = 2 * (size_t)D + LD;
+  size_t o = 0;
+  auto take = [&](size_t n) { const size_t r = o; o = (o + n + 255) / 256 * 256; return r; };
+  w.X = take((size_t)R * K1 * 4);
+  w.Ha = take((size_t)R * H * 4);
+  w.Hb = take((size_t)R * H * 4);
+  w.ctr0 = o;
+  size_t slab = 0;
+  for (int l = 0; l < 4; ++l) {
+    const ConvGeom g = linear_geom(R, l == 0 ? (int)K1 : H, H);
+    const int fl = EPI_BIAS | EPI_RELU;
+    w.take[l] = small_conv_plan(g, fl, 0).take != 0;
+    w.ctr[l] = o;
+    if (!w.take[l]) continue;
+    take(small_conv_ctr_bytes(g, fl, 0));
+    slab = std::max(slab, small_conv_slab_bytes(g, fl, 0));
+  }
+  w.ctr_bytes = o - w.ctr0;
+  w.slabs = take(slab);
+  w.total = o;
+  return w;
+}
+
+static int langrew_infer_check(int R, int D, int H, int LD) {
+  R3M_REQUIRE(R >= 1 && R <= SMALL_CONV_ROWS_MAX, "langrew_infer: R=%d rows (1 to %d)", R, SMALL_CONV_ROWS_MAX);
+  R3M_REQUIRE(D >= 32 && LD >= 32 && H >= 64, "langrew_infer: D=%d, lang_dim=%d (at least 32), hidden=%d (at least 64)", D, LD, H);
+  return check_dims(lang_dims_rows(1, 0, D, H, LD));
+}
+
+size_t langrew_infer_ws_bytes(int R, int D, int H, int LD) {
+  if (langrew_infer_check(R, D, H, LD)) return 0;
+  return lang_infer_ws(R, D, H, LD).total;
+}
+
+int langrew_infer(const float* e0, const float* eg, const float* le, const float* params, float* score, void* workspace, int R, int R0,
+                  int D, int H, int LD, hipStream_t s) {
+  if (int e = langrew_infer_check(R, D, H, LD)) return e;
+  R3M_REQUIRE(R0 == R || R0 == 1, "langrew_infer: R0=%d rows of e0 / le against R=%d rows (R0 must be R, or 1 to broadcast)", R0, R);
+  const LangDims d = lang_dims_rows(R, 0, D, H, LD);     // the parameter offsets
+  const LangInferWs w = lang_infer_ws(R, D, H, LD);
+  char* ws = static_cast<char*>(workspace);
+  float* X = reinterpret_cast<float*>(ws + w.X);
+  float* hb[2] = {reinterpret_cast<float*>(ws + w.Ha), reinterpret_cast<float*>(ws + w.Hb)};
+  hipLaunchKernelGGL(lang_concat_kernel, dim3(R), dim3(256), 0, s, e0, eg, le, X, D, LD, R0 == 1 && R > 1 ? 1 : 0);
+  if (int e = check_launch("lang_concat")) return e;
+  if (w.ctr_bytes && hipMemsetAsync(ws + w.ctr0, 0, w.ctr_bytes, s) != hipSuccess) {
+    set_last_error("langrew_infer: cannot reset the tickets");
+    return 1;
+  }
+  const float* in = X;
+  int K = d.K1;
+  for (int l = 0; l < 4; ++l) {
+    float* out = hb[l & 1];
+    const ConvGeom g = linear_geom(R, K, H);
+    if (w.take[l]) {
+      if (int e = launch_conv_small(in, params + d.w[l], out, nullptr, params + d.b[l], g, EPI_BIAS | EPI_RELU, 0,
+                                    reinterpret_cast<unsigned*>(ws + w.ctr[l]), reinterpret_cast<float*>(ws + w.slabs), s))
+        return e;
+    } else if (int e = conv_forward_launch(in, params + d.w[l], out, nullptr, params + d.b[l], g, EPI_BIAS | EPI_RELU, DT_F32, s))
+      return e;
+    in = out;
+    K = H;
+  }
+  hipLaunchKernelGGL((gemv_fwd_kernel<float>), dim3(ceil_div(R, 4)), dim3(256), 0, s, in, params + d.w[4], params + d.b[4], score, R, H);
+  return check_launch("gemv_fwd");
 }
 
 int langrew_call_backward(const float* dscore, const float* params, float* grads, float* de0, float* deg, float* dle, float* ws,

@@ -30,8 +30,9 @@ class LangEncoder(nn.Module):
     Features are computed ONCE per call; Trainer.update calls this once per step where the reference re-runs DistilBERT in each
     of its 15 get_reward calls on the same sentences (trainer.py:72-92)."""
 
-    def __init__(self, device, finetune=False, scratch=False, mask_padding=False, native=False):
+    def __init__(self, device, finetune=False, scratch=False, mask_padding=False, native=False, few_rows=False):
         super().__init__()
+        self.few_rows = bool(few_rows)  # native backend only: its Linears of few rows on the split-K kernel (HipDistilBert.features)
         self.native = bool(native)    # the locally found HuggingFace weights are converted to the HIP text model (r3m_amd/text.py)
         self.device = device
         self.modelname = "distilbert-base-uncased"
@@ -52,12 +53,15 @@ class LangEncoder(nn.Module):
         self._hf, self._pooled = (tokenizer, model), False
         return self
 
-    def use_native(self, tokenizer, model_or_state_dict, n_heads=None):
+    def use_native(self, tokenizer, model_or_state_dict, n_heads=None, few_rows=None):
         """Run the text model on the HIP path (r3m_amd/text.py, csrc/text.hip): encode() becomes one HipDistilBert.features call.
         model_or_state_dict: a transformers DistilBertModel, a HipDistilBert, or a state dict under HuggingFace's names (then n_heads
         is required: no tensor shape carries it). Like the `_hf` tuple the module stays OFF the module tree: state_dict(),
-        parameters() and the optimizer's owners are what they were."""
+        parameters() and the optimizer's owners are what they were. few_rows (None: leave the attribute as it is, default False):
+        encode() asks the native model for its few-row Linears."""
         from .text import HipDistilBert
+        if few_rows is not None:
+            self.few_rows = bool(few_rows)
         m = model_or_state_dict
         if isinstance(m, dict):
             if n_heads is None:
@@ -81,7 +85,7 @@ class LangEncoder(nn.Module):
             enc = tok(list(langs), return_tensors="pt", padding=True)
             if self._pooled:                         # HipDistilBert: the transformer and the pooling in one native call
                 self.encoder_calls += 1
-                return model.features(enc["input_ids"], enc["attention_mask"], mask_padding=self.mask_padding)
+                return model.features(enc["input_ids"], enc["attention_mask"], mask_padding=self.mask_padding, few_rows=self.few_rows)
             am = enc["attention_mask"].to(self.device)
             out = model(enc["input_ids"].to(self.device), attention_mask=am).last_hidden_state
             self.encoder_calls += 1

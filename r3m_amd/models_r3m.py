@@ -106,6 +106,13 @@ class R3M(nn.Module):
         from .inference import InferenceSession
         return InferenceSession(self.convnet, resize=list(obs_shape) != [3, 224, 224])
 
+    def reward_session(self, obs_shape=[3, 224, 224]):
+        """The language reward once per control step (inference.RewardSession): rs.reset(first_frames, sentences_or_features) caches
+        e0 and the sentence features, rs.step(frames) -> (reward [R], embedding [R, outdim]) runs the encoder session and the head's
+        forward-only pass on the few-row kernel. Needs a language head (langweight > 0)."""
+        from .inference import RewardSession
+        return RewardSession(self, obs_shape)
+
     def sim(self, tensor1, tensor2):
         if self.l2dist:
             return -torch.linalg.norm(tensor1 - tensor2, dim=-1)

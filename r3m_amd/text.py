@@ -3,7 +3,8 @@
 
     HipDistilBert.from_state_dict(sd, n_heads, device)      HuggingFace names, bare or with a `distilbert.` prefix
     HipDistilBert.from_hf(model, device)                    from a transformers.DistilBertModel
-    .features(input_ids, attention_mask, mask_padding=False) -> [B, dim]   pooled on the device
+    .features(input_ids, attention_mask, mask_padding=False, few_rows=False) -> [B, dim]   pooled on the device
+                                                            few_rows: the Linears of few B * T rows on the split-K kernel
     .__call__(input_ids, attention_mask=None).last_hidden_state            drops into LangEncoder.use_backend
 
 Inference only, fp32, no dropout; the tokenizer stays on the host."""
@@ -47,7 +48,7 @@ class HipDistilBert:
         self.device = params.device
         self.launches_per_call = 2 + 8 * self.n_layers
         self._dims_c = _dims6(self.dims)
-        self._ws = {}                     # (B, T) -> (workspace tensor, bytes)
+        self._ws = {}                     # (B, T, few_rows) -> (workspace tensor, bytes)
 
     # ---- construction ----
     @classmethod
@@ -103,27 +104,36 @@ class HipDistilBert:
         mask = _lib.upload_small(mask, self.device, torch.int32).contiguous()
         return ids, mask, B, T
 
-    def _forward(self, input_ids, attention_mask, pool, want_hidden):
+    def _forward(self, input_ids, attention_mask, pool, want_hidden, few_rows=False):
         L = _lib.lib()
         ids, mask, B, T = self._upload(input_ids, attention_mask)
-        if (B, T) not in self._ws:
-            nbytes = L.r3m_text_workspace_bytes(self._dims_c, B, T)
+        few_rows = bool(few_rows)
+        key = (B, T, few_rows)
+        if key not in self._ws:
+            nbytes = (L.r3m_text_small_workspace_bytes if few_rows else L.r3m_text_workspace_bytes)(self._dims_c, B, T)
             if nbytes == 0:
                 raise ValueError(f"HipDistilBert: {_lib.last_error()}")
-            self._ws[(B, T)] = (torch.empty(nbytes, dtype=torch.uint8, device=self.device), nbytes)
-        ws, nbytes = self._ws[(B, T)]
+            self._ws[key] = (torch.empty(nbytes, dtype=torch.uint8, device=self.device), nbytes)
+        ws, nbytes = self._ws[key]
+        run, what = (L.r3m_text_forward_small, "text_forward_small") if few_rows else (L.r3m_text_forward, "text_forward")
         feats = torch.empty((B, self.dim), dtype=torch.float32, device=self.device)
         hidden = torch.empty((B, T, self.dim), dtype=torch.float32, device=self.device) if want_hidden else None
         with _lib.on(self.params):
-            _lib.check(L.r3m_text_forward(ids.data_ptr(), mask.data_ptr(), self.params.data_ptr(), feats.data_ptr(), _lib.ptr(hidden),
-                                          ws.data_ptr(), nbytes, B, T, self._dims_c, int(pool), _lib.stream_ptr(self.device)),
-                       "text_forward")
+            _lib.check(run(ids.data_ptr(), mask.data_ptr(), self.params.data_ptr(), feats.data_ptr(), _lib.ptr(hidden), ws.data_ptr(), nbytes,
+                           B, T, self._dims_c, int(pool), _lib.stream_ptr(self.device)), what)
         return feats, hidden
 
-    def features(self, input_ids, attention_mask, mask_padding=False):
+    def features(self, input_ids, attention_mask, mask_padding=False, few_rows=False):
         """[B, dim] sentence features: the mean of the last hidden state over ALL positions (the reference, padding included), or
-        with mask_padding over the positions with attention_mask != 0."""
-        return self._forward(input_ids, attention_mask, 1 if mask_padding else 0, False)[0]
+        with mask_padding over the positions with attention_mask != 0. few_rows: r3m_text_forward_small, which runs every Linear that
+        the few-row plan takes at B * T rows on the split-K kernel of csrc/conv_small.hip (same arithmetic per product, another
+        summation order: results agree to fp32 rounding, not bit for bit)."""
+        return self._forward(input_ids, attention_mask, 1 if mask_padding else 0, False, few_rows)[0]
+
+    def hidden_and_pools(self, input_ids, attention_mask, mask_padding=False, few_rows=False):
+        """(last hidden state [B,T,dim], features [B,dim]) of ONE call (tests, parity reports)"""
+        feats, hidden = self._forward(input_ids, attention_mask, 1 if mask_padding else 0, True, few_rows)
+        return hidden, feats
 
     def __call__(self, input_ids, attention_mask=None):
         return SimpleNamespace(last_hidden_state=self._forward(input_ids, attention_mask, 0, True)[1])
