@@ -106,8 +106,28 @@ void r3m_profile_enable(int on);
 /* which kernel classes are bracketed while profiling is on: bit k = class k (0 conv fwd/dgrad 128-wide, 1 64-wide, 2 / 3 the weight
    gradients); default all. Each bracket costs the stream two event records. Returns the old mask. */
 unsigned r3m_profile_classes(unsigned mask);
+/* What the four classes contain (tests/test_gpu_profile.py pins it against tests/profile_model.py). Brackets sit in the dispatchers of the
+   gather GEMM, of the weight gradients and of the stem's forward / weight gradient, so:
+     - classes 0 / 1: one launch per convolution forward and per stride-1 input gradient, one per parity class of a strided input gradient
+       (FLOPs 2 M N taps K with the taps of that class, taps on padding included); the stem forward is class 1; a bf16 3x3 launch on the
+       kernel-row route is class 0 whatever its width. ALSO every Linear that runs as a 1x1 convolution: the hidden Linears of the reward
+       head (r3m_langrew_forward / _backward / _call_*) and of the DistilBERT forward (r3m_text_forward), with taps = 1 and M, N, K = rows,
+       outputs, inputs. A reader of bench.py's per-class lines finds them inside classes 0 / 1.
+     - classes 2 / 3: one launch per weight gradient (the stem's is class 3; the reward head's Linears' too); the split-K reduce behind it is
+       not bracketed.
+     - in NO class: launches of the few-row split-K kernel (r3m_conv2d_fwd_affine_small, r3m_linear_fwd_small; r3m_resnet_forward_prepared
+       counts only the convolutions the routing rule leaves or whose block does not run the fused sequence; likewise r3m_langrew_infer and
+       r3m_text_forward_small), the stem's input gradient (a backward with dx counts no launch more than one without), and every
+       BatchNorm, pooling, loss, optimizer, transpose and conversion kernel.
+   A launcher that returns an error counts nothing. The open bracket belongs to the calling thread: launches from several threads (a
+   backward on autograd's thread) are all counted. collect() sums per class since the last collect and resets; r3m_profile_enable(0)
+   drops what was recorded and not yet collected. */
 int r3m_profile_collect(double* ms, long long* launches, double* flops);
-int r3m_profile_collect_bytes(double* bytes);     /* algorithmic HBM bytes per class (operands + results once) of the launches of the last collect() */
+/* algorithmic HBM bytes per class of the launches of the last collect(): what each launch reads once plus what it writes once -- the input
+   pixels some (output row, tap) pair reads (padding and pixels no tap reaches are no traffic), the weights of its taps, the result, and what
+   its epilogue adds (statistics / partial rows, per-channel vectors, residuals, mask bits); a weight gradient: dY, the input pixels in range
+   and its split-K slabs */
+int r3m_profile_collect_bytes(double* bytes);
 int r3m_profile_dump_to(const char* host_path);   /* also write one CSV row per launch at collect(); NULL/"" stops */
 
 /* ---------------- encoder engine -----------------------------------------------------------------------------

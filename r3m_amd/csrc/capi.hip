@@ -71,6 +71,10 @@ static size_t g_prof_used = 0;                   // guarded by g_prof_mu
 static thread_local ProfEvent* t_prof_open = nullptr;
 
 void prof_begin(int kclass, double flops, int M, int N, int K, int taps, hipStream_t s) {
+  // A launcher that returned an error between begin and end left its bracket open. It stays unclosed (collect skips it); without
+  // this reset the prof_bytes / prof_end of the NEXT launch would close it instead when that launch opens none of its own (its class
+  // masked out, profiling switched off meanwhile) and count the failed launch with the other's bytes and a time across both.
+  t_prof_open = nullptr;
   if (!g_prof_on.load(std::memory_order_relaxed)) return;
   if (!((g_prof_classes.load(std::memory_order_relaxed) >> kclass) & 1u)) return;
   ProfEvent* e = nullptr;
@@ -104,6 +108,8 @@ void prof_end(hipStream_t s) {
   }
   t_prof_open = nullptr;
 }
+bool prof_open() { return t_prof_open != nullptr; }
+void prof_abandon() { t_prof_open = nullptr; }
 
 }  // namespace r3m
 

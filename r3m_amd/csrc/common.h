@@ -358,5 +358,7 @@ enum { KC_GEMM_WIDE = 0, KC_GEMM_NARROW = 1, KC_WGRAD_WIDE = 2, KC_WGRAD_NARROW 
 void prof_begin(int kclass, double flops, int M, int N, int K, int taps, hipStream_t s);   // start event (no-op when disabled)
 void prof_bytes(double bytes);                               // algorithmic HBM bytes of the launch just opened (roofline of the HBM-bound path)
 void prof_end(hipStream_t s);                                // records the stop event
+bool prof_open();                                            // this thread has a bracket open (the byte count is worth computing)
+void prof_abandon();                                         // error path between begin and end: the open bracket is dropped, nothing is counted
 
 }  // namespace r3m

@@ -38,6 +38,7 @@
 #include "common.h"
 #include "conv_dev.h"
 #include <utility>
+#include <vector>
 
 namespace r3m {
 
@@ -932,14 +933,40 @@ static int gg_use_glds() {
 
 // algorithmic HBM bytes of one gather-GEMM launch: the input tensor once, the weights once, the result once (+ the tensors
 // a read-modify-write epilogue adds: the old result / the residual gradient and its 1-bit mask)
+// The input counts the pixels some (GEMM row, tap) pair of the launch reads: padding is no traffic, nor are the pixels no tap reaches
+// (three quarters of the input of a 1x1 / stride-2 convolution, all of dY for a parity class without taps). Per-channel operands
+// (bias, eval-BatchNorm scale / shift, the BatchNorm-backward mean and mask coefficients) and the statistics rows are fp32.
+// Only evaluated while a bracket is open (prof_open).
+static double gather_gemm_pixels_read(const GatherGemmParams& p) {
+  if (p.simple_rows) return (double)p.M;
+  std::vector<char> row(p.Hi > 0 ? p.Hi : 0, 0), col(p.Wi > 0 ? p.Wi : 0, 0);
+  for (int t = 0; t < p.ntaps; ++t) {
+    for (int gy = 0; gy < p.Hg; ++gy) {
+      const int iy = gy * p.is + p.dy[t];
+      if (iy >= 0 && iy < p.Hi) row[iy] = 1;
+    }
+    for (int gx = 0; gx < p.Wg; ++gx) {
+      const int ix = gx * p.is + p.dx[t];
+      if (ix >= 0 && ix < p.Wi) col[ix] = 1;
+    }
+  }
+  long long rows = 0, cols = 0;      // the taps of a launch are a product set (kernel rows x kernel columns): so are the pixels read
+  for (char c : row) rows += c;
+  for (char c : col) cols += c;
+  return (double)p.N * (double)rows * (double)cols;
+}
 double gather_gemm_alg_bytes(const GatherGemmParams& p, int elem) {
-  const double in = p.simple_rows ? (double)p.M * p.Ci : (double)p.N * p.Hi * p.Wi * p.Ci;
+  const double in = gather_gemm_pixels_read(p) * p.Ci;
   const double out = (double)p.M * p.Nc;
   double b = elem * (in + out + (double)p.Nc * p.ntaps * p.Ci);
+  if (p.flags & EPI_STATS) b += 8.0 * gather_gemm_grid_m(p.M, p.Nc) * p.Nc;
+  if (p.flags & EPI_BIAS) b += 4.0 * p.Nc;
+  if (p.flags & EPI_AFFINE) b += 8.0 * p.Nc;
   if (p.flags & EPI_ACCUM) b += elem * out;
   if (p.flags & EPI_MASKED_ADD) b += elem * out + out / 8.0;
   if (p.flags & EPI_MASK_OUT) b += elem * out;
-  if (p.flags & EPI_BNRED) b += elem * out + (p.bn_bits ? out / 8.0 : 0.0) + 8.0 * bnred_partial_rows(p.M) * p.Nc;   // + y, mask, partials
+  if (p.flags & EPI_BNRED)      // + y, the mask (bits, or scale and shift to recompute it), the mean, the partial rows
+    b += elem * out + (p.bn_bits ? out / 8.0 : 8.0 * p.Nc) + 4.0 * p.Nc + 8.0 * bnred_partial_rows(p.M) * p.Nc;
   return b;
 }
 
@@ -1099,7 +1126,7 @@ int launch_gather_gemm(const GatherGemmParams& p_in, hipStream_t s) {
     }
   }
 #undef LAUNCH_GG
-  prof_bytes(gather_gemm_alg_bytes(p, 4));
+  if (prof_open()) prof_bytes(gather_gemm_alg_bytes(p, 4));
   prof_end(s);
   return check_launch(what);
 }

@@ -594,9 +594,9 @@ int launch_gather_gemm_bf16(const GatherGemmParams& p, hipStream_t s) {
     case GG16_ROUTE_PW: rc = launch_pw16(p, s); what = "pw16_gemm"; break;
     default: rc = wide ? gg16_launch_wide(p, s) : gg16_launch_narrow(p, s); what = "gather_gemm_bf16"; break;   // GG16_ROUTE_GATHER
   }
-  prof_bytes(gather_gemm_alg_bytes(p, 2));
+  if (rc) { prof_abandon(); return rc; }      // a launcher that returned an error: no launch is counted
+  if (prof_open()) prof_bytes(gather_gemm_alg_bytes(p, 2));
   prof_end(s);
-  if (rc) return rc;
   return check_launch(what);
 }
 

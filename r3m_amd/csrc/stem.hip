@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void stem_fwd_kernel(const float* __restrict__
 
 int launch_stem_fwd(const float* x_nchw, const float* w147, void* y, float* stats, int F, int dt, hipStream_t s) {
   const GatherGemmParams p = stem_fwd_params(y, stats, dt, F, 112, 112);
-  stem_prof_begin(KC_GEMM_NARROW, p.M, (double)F * 224 * 224 * 3 * 4, dt, s);
+  stem_prof_begin(KC_GEMM_NARROW, p.M, (double)F * 224 * 224 * 3 * 4, dt, s, stats);
   const int ntiles = F * 49;
   const int grid = ntiles < 512 ? ntiles : 512;   // persistent blocks (2 per CU): the 39 KB weight image is staged once per block
   if (dt == DT_BF16) {

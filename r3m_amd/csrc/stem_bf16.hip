@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256) void stem_fwd16_kernel(const bf16_t* __restric
 
 int launch_stem_fwd16(const void* xn16, const float* w147, void* y, float* stats, int F, hipStream_t s) {
   const GatherGemmParams p = stem_fwd_params(y, stats, DT_BF16, F, 112, 112);
-  stem_prof_begin(KC_GEMM_NARROW, p.M, (double)stem_xn16_bytes(F), DT_BF16, s);
+  stem_prof_begin(KC_GEMM_NARROW, p.M, (double)stem_xn16_bytes(F), DT_BF16, s, stats);
   const int ntiles = F * 49;
   const int grid = ntiles < 512 ? ntiles : 512;   // persistent blocks (2 per CU): the weight image is converted once per block
   static DynLdsOptIn optin_stats, optin_plain;

@@ -117,10 +117,13 @@ inline GatherGemmParams stem_fwd_params(void* y, float* stats, int dt, int F, in
   p.Hg = Ho; p.Wg = Wo; p.Ho = Ho; p.Wo = Wo;
   return p;
 }
-// profiling bracket of a stem GEMM over M output pixels (closed by prof_end): 2 M 64 147 flops, the image read + M x 64 elements
-inline void stem_prof_begin(int kclass, int M, double image_bytes, int dt, hipStream_t s) {
+// profiling bracket of a stem GEMM over M output pixels (closed by prof_end): 2 M 64 147 flops, the image read + M x 64 elements; the
+// forward (KC_GEMM_NARROW) also reads conv1's fp32 weights and, with `stats`, writes one statistics row per 256 output pixels
+inline void stem_prof_begin(int kclass, int M, double image_bytes, int dt, hipStream_t s, const float* stats = nullptr) {
   prof_begin(kclass, 2.0 * (double)M * 64.0 * 147.0, M, 64, 147, 1, s);
-  prof_bytes(image_bytes + (double)M * 64 * (dt == DT_BF16 ? 2 : 4));
+  double b = image_bytes + (double)M * 64 * (dt == DT_BF16 ? 2 : 4);
+  if (kclass == KC_GEMM_NARROW) b += 4.0 * 64 * 147 + (stats ? 8.0 * ceil_div(M, 256) * 64 : 0.0);
+  prof_bytes(b);
 }
 
 // ---- weight gradient on the fp32 MFMA: dW[co][kh*22 + j] partial of one block = sum over its output image rows of

@@ -296,7 +296,7 @@ int launch_stem_fwd_gen(const float* xn, const float* w147, void* y, float* stat
   const int ntiles = ceil_div(p.M, 256);
   const int grid = ntiles < 512 ? ntiles : 512;
   const int lds = stem_fwd_lds_bytes(g);
-  stem_prof_begin(KC_GEMM_NARROW, p.M, (double)F * H * W * 3 * (dt == DT_BF16 ? 2 : 4), dt, s);
+  stem_prof_begin(KC_GEMM_NARROW, p.M, (double)F * H * W * 3 * (dt == DT_BF16 ? 2 : 4), dt, s, stats);
 #define SG_FWD(E, IT, OT)                                                                                                     \
   do {                                                                                                                        \
     static DynLdsOptIn oi;                                                                                                    \

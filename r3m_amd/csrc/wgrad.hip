@@ -363,7 +363,22 @@ int launch_wgrad(const WgradParams& p0, const WgradPlan& r, hipStream_t s) {
     case WG16_ALL_TAPS:  what = "wgrad3x3_halo_bf16"; if (int e = launch_wgrad_bf16(p, r, s)) return e; break;
     default: R3M_REQUIRE(false, "wgrad: route %d", r.route);
   }
-  prof_bytes((double)esz * ((double)p.M * p.Co + (double)p.N * p.Hi * p.Wi * p.Ci) + 4.0 * (double)r.split * p.Co * T * p.Ci);
+  if (prof_open()) {   // dY, the input pixels some (output pixel, tap) pair reads (a 1x1 / stride-2 layer: a quarter), the split-K slabs
+    const auto read = [&](int n_in, int n_out, int k) {
+      int n = 0;
+      for (int i = 0; i < n_in; ++i) {
+        bool hit = false;
+        for (int kk = 0; kk < k && !hit; ++kk) {
+          const int o = i + p.pad - kk;
+          hit = o >= 0 && o % p.stride == 0 && o / p.stride < n_out;
+        }
+        n += hit;
+      }
+      return n;
+    };
+    const double x = (double)p.N * read(p.Hi, p.Ho, p.KH) * read(p.Wi, p.Wo, p.KW) * p.Ci;
+    prof_bytes((double)esz * ((double)p.M * p.Co + x) + 4.0 * (double)r.split * p.Co * T * p.Ci);
+  }
   prof_end(s);
   return check_launch(what);
 }
