@@ -536,6 +536,20 @@ int r3m_langrew_forward_dt(const float* alle, const float* feats, const int* per
                            size_t workspace_bytes, int B, int D, int hidden, int lang_dim, int dtype, r3m_stream_t stream);
 int r3m_langrew_backward_dt(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, void* workspace,
                             size_t workspace_bytes, int B, int D, int hidden, int lang_dim, int accumulate, int dtype, r3m_stream_t stream);
+/* The same pass for any number of cross-clip negatives N = the reference's model.num_negatives (r3m/trainer.py:66,86-92), 0 <= N <=
+ * R3M_MAX_NEGATIVES: 6 + 3N evaluations, (6 + 3N) B rows. perm / iperm are [3N][B] in the reference's draw order, row 3k + j the k-th
+ * draw of head j (may be NULL when N = 0); scores / dscore are [6 + 3N][B]: rows 0-2 the positives (e0,eg) (e0,es1) (e0,es2), rows 3-5
+ * the in-clip negatives (e0,e0) (e0,es0) (e0,es1), row q = 6 + 3k + j the k-th permuted negative of head j. Every call above is the
+ * N = 3 call of these. The cap of 16 is this library's (54 score rows), the reference has none; N outside 0..16, a row count
+ * (6 + 3N) B of 2^31 or more, or a workspace smaller than r3m_langrew_workspace_bytes_n reports return non-zero before any HIP call
+ * (workspace_bytes_n returns 0 for what it refuses, with the message set). */
+#define R3M_MAX_NEGATIVES 16
+size_t r3m_langrew_workspace_bytes_n(int B, int D, int hidden, int lang_dim, int N);
+int r3m_langrew_forward_n(const float* alle, const float* feats, const int* perm, const float* params, float* scores, void* workspace,
+                          size_t workspace_bytes, int B, int D, int hidden, int lang_dim, int N, int dtype, r3m_stream_t stream);
+int r3m_langrew_backward_n(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, void* workspace,
+                           size_t workspace_bytes, int B, int D, int hidden, int lang_dim, int N, int accumulate, int dtype,
+                           r3m_stream_t stream);
 /* ONE differentiable evaluation score[R] = G(e0[R,D], eg[R,D], le[R,lang_dim]) — the reference's own calling form
  * (R3M.get_reward r3m/models/models_r3m.py:78-81 -> LanguageReward.forward models_language.py:53-55, called 15x with autograd
  * by r3m/trainer.py:72-92). forward leaves the activations in `workspace` (r3m_langrew_call_workspace_bytes(R, ...));
@@ -618,7 +632,26 @@ int r3m_loss_tcn_lp(const float* alle, const int* perm, const int* iperm, float*
  * dscore [15][B] = d(full_loss)/d(score). Same workspace as r3m_loss_tcn_lp. */
 int r3m_loss_lang_infonce(const float* scores, const float* mask, float* dscore, void* workspace, size_t workspace_bytes, int B,
                           float langweight, r3m_stream_t stream);
-/* metrics[16]: 0 l2loss 1 l1loss 2 l0loss 3 tcnloss 4 aligned 5 rewloss 6-8 rewacc1-3 9 full_loss (trainer.py:55-57,111-117,147-152) */
+/* The objective for any number of cross-clip negatives N = model.num_negatives (trainer.py:66,86-92 and :124,135-139), 0 <= N <=
+ * R3M_MAX_NEGATIVES (16: this library's cap, the reference has none). The three calls above are the N = 3 calls of these.
+ *   TCN: 3 + 2N similarities per clip; perm / iperm [2N][B] int32 in the reference's draw order, row 2k the es0 permutation and row
+ *     2k + 1 the es2 permutation of negative k. The sums over negatives run k = 0..N-1 after the fixed terms. N = 0 with tcnweight > 0
+ *     is refused: the reference fails there (torch.stack of an empty list, trainer.py:140). N = 0 with tcnweight == 0 computes the
+ *     LP terms (perm / iperm are not read).
+ *   language InfoNCE: scores / dscore [6 + 3N][B], rows 0-2 positives, 3-5 in-clip negatives, q = 6 + 3k + j the k-th permuted negative
+ *     of head j; head j's negatives are summed in-clip first, then k = 0..N-1; rewacc_j compares the positive with the max of all
+ *     1 + N. N = 0 is the in-clip negative alone.
+ * The workspace grows with N (r3m_loss_workspace_bytes_n; 0 with the message set for a refused B or N); the per-clip partials lead it,
+ * so r3m_loss_finalize takes no N and accepts a workspace sized for any N. All refusals come before any HIP call. */
+size_t r3m_loss_workspace_bytes_n(int B, int N);
+int r3m_loss_tcn_lp_n(const float* alle, const int* perm, const int* iperm, float* dalle, void* workspace, size_t workspace_bytes,
+                      int B, int D, int N, int l2dist, float l2weight, float l1weight, float tcnweight, r3m_stream_t stream);
+int r3m_loss_lang_infonce_n(const float* scores, const float* mask, float* dscore, void* workspace, size_t workspace_bytes, int B, int N,
+                            float langweight, r3m_stream_t stream);
+/* metrics[16]: 0 l2loss 1 l1loss 2 l0loss 3 tcnloss 4 aligned 5 rewloss 6-8 rewacc1-3 9 full_loss (trainer.py:55-57,111-117,147-152).
+ * Takes the workspace that r3m_loss_tcn_lp[_n] (and r3m_loss_lang_infonce[_n]) filled, whatever N they ran with. It reads the per-clip
+ * partials that lead it, 48 B bytes, and refuses a workspace smaller than that; before the `_n` entry points existed it asked for the
+ * whole r3m_loss_workspace_bytes(B), which a workspace sized for fewer than 3 negatives does not have. */
 int r3m_loss_finalize(void* workspace, size_t workspace_bytes, int B, int have_lang, float* metrics, float l2weight,
                       float l1weight, float tcnweight, float langweight, r3m_stream_t stream);
 

@@ -144,6 +144,9 @@ SIGNATURES = {
     "r3m_langrew_backward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_langrew_forward_dt": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_langrew_backward_dt": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_langrew_workspace_bytes_n": (c_sz, [c_i] * 5),
+    "r3m_langrew_forward_n": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
+    "r3m_langrew_backward_n": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f]),
     "r3m_langrew_call_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "r3m_langrew_call_forward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_f]),
     "r3m_langrew_call_backward": (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_i, c_f]),
@@ -164,6 +167,9 @@ SIGNATURES = {
     "r3m_loss_workspace_bytes": (c_sz, [c_i]),
     "r3m_loss_tcn_lp": (c_i, [c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_fl, c_fl, c_fl, c_f]),
     "r3m_loss_lang_infonce": (c_i, [c_f, c_f, c_f, c_f, c_sz, c_i, c_fl, c_f]),
+    "r3m_loss_workspace_bytes_n": (c_sz, [c_i, c_i]),
+    "r3m_loss_tcn_lp_n": (c_i, [c_f, c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_i, c_i, c_fl, c_fl, c_fl, c_f]),
+    "r3m_loss_lang_infonce_n": (c_i, [c_f, c_f, c_f, c_f, c_sz, c_i, c_i, c_fl, c_f]),
     "r3m_loss_finalize": (c_i, [c_f, c_sz, c_i, c_i, c_f, c_fl, c_fl, c_fl, c_fl, c_f]),
     "r3m_adam_step": (c_i, [c_f, c_f, c_f, c_f, c_ll, c_d, c_d, c_d, c_d, c_ll, c_fl, c_f]),
     "r3m_sgd_step": (c_i, [c_f, c_f, c_f, c_ll, c_d, c_d, c_d, c_d, c_i, c_ll, c_fl, c_f]),

@@ -715,28 +715,50 @@ int r3m_debug_linear_small_plan(int M, int K, int N, int flags, int* out, int ca
 }
 
 long long r3m_langrew_num_params(int D, int hidden, int lang_dim) { return langrew_num_params(D, hidden, lang_dim); }
-size_t r3m_langrew_workspace_bytes(int B, int D, int hidden, int lang_dim) { return langrew_ws_floats(B, D, hidden, lang_dim) * 4; }
+// The batched head: every form is the `_n` call (N = num_negatives; the forms without it are N = 3). Argument checks first, no HIP call
+// before them.
+size_t r3m_langrew_workspace_bytes_n(int B, int D, int hidden, int lang_dim, int N) {
+  if (langrew_batch_refused("langrew_workspace_bytes", B, D, hidden, lang_dim, N)) return 0;
+  return langrew_ws_floats(B, D, hidden, lang_dim, N) * 4;
+}
+int r3m_langrew_forward_n(const float* alle, const float* feats, const int* perm, const float* params, float* scores, void* ws,
+                          size_t ws_bytes, int B, int D, int hidden, int lang_dim, int N, int dtype, r3m_stream_t stream) {
+  R3M_REQUIRE(alle && feats && (perm || N == 0) && params && scores && ws, "langrew_forward: null argument");
+  if (langrew_batch_refused("langrew_forward", B, D, hidden, lang_dim, N)) return 1;
+  const size_t need = langrew_ws_floats(B, D, hidden, lang_dim, N) * 4;
+  R3M_REQUIRE(ws_bytes >= need, "langrew_forward: workspace too small (%zu bytes; B=%d with %d negatives needs %zu, r3m_langrew_workspace_bytes_n)",
+              ws_bytes, B, N, need);
+  if (check_dt(dtype, "langrew_forward")) return 1;
+  return langrew_forward(alle, feats, perm, params, scores, static_cast<float*>(ws), B, D, hidden, lang_dim, N, dtype, S(stream));
+}
+int r3m_langrew_backward_n(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, void* ws,
+                           size_t ws_bytes, int B, int D, int hidden, int lang_dim, int N, int accumulate, int dtype,
+                           r3m_stream_t stream) {
+  R3M_REQUIRE(dscore && (iperm || N == 0) && params && grads && ws, "langrew_backward: null argument");
+  if (langrew_batch_refused("langrew_backward", B, D, hidden, lang_dim, N)) return 1;
+  const size_t need = langrew_ws_floats(B, D, hidden, lang_dim, N) * 4;
+  R3M_REQUIRE(ws_bytes >= need, "langrew_backward: workspace too small (%zu bytes; B=%d with %d negatives needs %zu, r3m_langrew_workspace_bytes_n)",
+              ws_bytes, B, N, need);
+  if (check_dt(dtype, "langrew_backward")) return 1;
+  return langrew_backward(dscore, iperm, params, grads, dalle, static_cast<float*>(ws), B, D, hidden, lang_dim, N, accumulate, dtype,
+                          S(stream));
+}
+size_t r3m_langrew_workspace_bytes(int B, int D, int hidden, int lang_dim) { return langrew_ws_floats(B, D, hidden, lang_dim, 3) * 4; }
 int r3m_langrew_forward_dt(const float* alle, const float* feats, const int* perm, const float* params, float* scores, void* ws,
                            size_t ws_bytes, int B, int D, int hidden, int lang_dim, int dtype, r3m_stream_t stream) {
-  R3M_REQUIRE(alle && feats && perm && params && scores && ws, "langrew_forward: null argument");
-  R3M_REQUIRE(ws_bytes >= r3m_langrew_workspace_bytes(B, D, hidden, lang_dim), "langrew_forward: workspace too small");
-  if (check_dt(dtype, "langrew_forward")) return 1;
-  return langrew_forward(alle, feats, perm, params, scores, static_cast<float*>(ws), B, D, hidden, lang_dim, dtype, S(stream));
+  return r3m_langrew_forward_n(alle, feats, perm, params, scores, ws, ws_bytes, B, D, hidden, lang_dim, 3, dtype, stream);
 }
 int r3m_langrew_backward_dt(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, void* ws,
                             size_t ws_bytes, int B, int D, int hidden, int lang_dim, int accumulate, int dtype, r3m_stream_t stream) {
-  R3M_REQUIRE(dscore && iperm && params && grads && ws, "langrew_backward: null argument");
-  R3M_REQUIRE(ws_bytes >= r3m_langrew_workspace_bytes(B, D, hidden, lang_dim), "langrew_backward: workspace too small");
-  if (check_dt(dtype, "langrew_backward")) return 1;
-  return langrew_backward(dscore, iperm, params, grads, dalle, static_cast<float*>(ws), B, D, hidden, lang_dim, accumulate, dtype, S(stream));
+  return r3m_langrew_backward_n(dscore, iperm, params, grads, dalle, ws, ws_bytes, B, D, hidden, lang_dim, 3, accumulate, dtype, stream);
 }
 int r3m_langrew_forward(const float* alle, const float* feats, const int* perm, const float* params, float* scores, void* ws,
                         size_t ws_bytes, int B, int D, int hidden, int lang_dim, r3m_stream_t stream) {
-  return r3m_langrew_forward_dt(alle, feats, perm, params, scores, ws, ws_bytes, B, D, hidden, lang_dim, DT_F32, stream);
+  return r3m_langrew_forward_n(alle, feats, perm, params, scores, ws, ws_bytes, B, D, hidden, lang_dim, 3, DT_F32, stream);
 }
 int r3m_langrew_backward(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, void* ws,
                          size_t ws_bytes, int B, int D, int hidden, int lang_dim, int accumulate, r3m_stream_t stream) {
-  return r3m_langrew_backward_dt(dscore, iperm, params, grads, dalle, ws, ws_bytes, B, D, hidden, lang_dim, accumulate, DT_F32, stream);
+  return r3m_langrew_backward_n(dscore, iperm, params, grads, dalle, ws, ws_bytes, B, D, hidden, lang_dim, 3, accumulate, DT_F32, stream);
 }
 
 size_t r3m_langrew_call_workspace_bytes(int R, int D, int hidden, int lang_dim) { return langrew_call_ws_floats(R, D, hidden, lang_dim) * 4; }
@@ -784,20 +806,44 @@ int r3m_resize_crop_backward(const float* dout, float* din, long long N, int C, 
   return launch_resize_crop_backward(dout, din, N, C, Hi, Wi, resized_h, resized_w, top, left, Ho, Wo, accumulate, S(stream));
 }
 
-size_t r3m_loss_workspace_bytes(int B) { return loss_workspace_floats(B) * 4; }
+// The objective: every form is the `_n` call (N = num_negatives; the forms without it are N = 3). Argument checks first, no HIP call
+// before them.
+size_t r3m_loss_workspace_bytes_n(int B, int N) {
+  if (loss_refused("loss_workspace_bytes", B, 1, N, 0.f)) return 0;
+  return loss_workspace_floats(B, N) * 4;
+}
+int r3m_loss_tcn_lp_n(const float* alle, const int* perm, const int* iperm, float* dalle, void* ws, size_t ws_bytes, int B, int D,
+                      int N, int l2dist, float l2w, float l1w, float tcnw, r3m_stream_t stream) {
+  if (loss_refused("loss_tcn_lp", B, D, N, tcnw)) return 1;
+  const size_t need = loss_workspace_floats(B, N) * 4;
+  R3M_REQUIRE(ws_bytes >= need, "loss_tcn_lp: workspace too small (%zu bytes; B=%d with %d negatives needs %zu, r3m_loss_workspace_bytes_n)",
+              ws_bytes, B, N, need);
+  return launch_tcn_lp_loss(alle, perm, iperm, dalle, static_cast<float*>(ws), B, D, N, l2dist, l2w, l1w, tcnw, S(stream));
+}
+int r3m_loss_lang_infonce_n(const float* scores, const float* mask, float* dscore, void* ws, size_t ws_bytes, int B, int N, float langw,
+                            r3m_stream_t stream) {
+  if (loss_refused("loss_lang_infonce", B, 1, N, 0.f)) return 1;
+  const size_t need = loss_workspace_floats(B, N) * 4;
+  R3M_REQUIRE(ws_bytes >= need, "loss_lang_infonce: workspace too small (%zu bytes; B=%d with %d negatives needs %zu, r3m_loss_workspace_bytes_n)",
+              ws_bytes, B, N, need);
+  return launch_lang_infonce(scores, mask, dscore, static_cast<float*>(ws), B, N, langw, S(stream));
+}
+size_t r3m_loss_workspace_bytes(int B) { return loss_workspace_floats(B, 3) * 4; }
 int r3m_loss_tcn_lp(const float* alle, const int* perm, const int* iperm, float* dalle, void* ws, size_t ws_bytes, int B, int D,
                     int l2dist, float l2w, float l1w, float tcnw, r3m_stream_t stream) {
-  R3M_REQUIRE(ws_bytes >= r3m_loss_workspace_bytes(B), "loss: workspace too small");
-  return launch_tcn_lp_loss(alle, perm, iperm, dalle, static_cast<float*>(ws), B, D, l2dist, l2w, l1w, tcnw, S(stream));
+  return r3m_loss_tcn_lp_n(alle, perm, iperm, dalle, ws, ws_bytes, B, D, 3, l2dist, l2w, l1w, tcnw, stream);
 }
 int r3m_loss_lang_infonce(const float* scores, const float* mask, float* dscore, void* ws, size_t ws_bytes, int B, float langw,
                           r3m_stream_t stream) {
-  R3M_REQUIRE(ws_bytes >= r3m_loss_workspace_bytes(B), "loss: workspace too small");
-  return launch_lang_infonce(scores, mask, dscore, static_cast<float*>(ws), B, langw, S(stream));
+  return r3m_loss_lang_infonce_n(scores, mask, dscore, ws, ws_bytes, B, 3, langw, stream);
 }
+// reads the per-clip partials only (clipm [B][8], clipl [B][4]): they lead the workspace whatever N the two calls above ran with, so this
+// call takes no N, asks for those 12 B floats only and so accepts any workspace that r3m_loss_workspace_bytes_n(B, N) sized
 int r3m_loss_finalize(void* ws, size_t ws_bytes, int B, int have_lang, float* metrics, float l2w, float l1w, float tcnw, float langw,
                       r3m_stream_t stream) {
-  R3M_REQUIRE(ws_bytes >= r3m_loss_workspace_bytes(B), "loss: workspace too small");
+  R3M_REQUIRE(B >= 1, "loss_finalize: B=%d", B);
+  R3M_REQUIRE(ws_bytes >= loss_finalize_floats(B) * 4, "loss_finalize: workspace too small (%zu bytes; B=%d needs %zu)", ws_bytes, B,
+              loss_finalize_floats(B) * 4);
   return launch_loss_finalize(static_cast<float*>(ws), B, have_lang, metrics, l2w, l1w, tcnw, langw, S(stream));
 }
 

@@ -303,10 +303,13 @@ int launch_feature_export(const void* z_nhwc, float* out_nchw, int N, int H, int
 int launch_feature_grad_add(const float* d_nchw, void* g_nhwc, int N, int H, int W, int C, int dt, hipStream_t s);
 
 // ---- losses (loss.hip) and optimizers (adam.hip) ----
-size_t loss_workspace_floats(int B);
-int launch_tcn_lp_loss(const float* alle, const int* perm, const int* iperm, float* dalle, float* ws, int B, int D, int l2dist,
+// N = the reference's num_negatives, 0..16; loss_refused: 0, or 1 with the message set (no HIP call); the launchers do not check again
+size_t loss_workspace_floats(int B, int N);
+size_t loss_finalize_floats(int B);                          // the leading part of the workspace that launch_loss_finalize reads
+int loss_refused(const char* what, int B, int D, int N, float tcnw);
+int launch_tcn_lp_loss(const float* alle, const int* perm, const int* iperm, float* dalle, float* ws, int B, int D, int N, int l2dist,
                        float l2w, float l1w, float tcnw, hipStream_t s);
-int launch_lang_infonce(const float* scores, const float* mask, float* dscore, float* ws, int B, float langw, hipStream_t s);
+int launch_lang_infonce(const float* scores, const float* mask, float* dscore, float* ws, int B, int N, float langw, hipStream_t s);
 int launch_loss_finalize(float* ws, int B, int have_lang, float* metrics, float l2w, float l1w, float tcnw, float langw,
                          hipStream_t s);
 // What one optimizer call steps: n disjoint, sorted [off, off + count) ranges of the flat buffers with a step count each (host arrays;
@@ -338,11 +341,14 @@ int launch_resize_crop_backward(const float* dout, float* din, long long N, int 
 
 // ---- language-reward head (lang.hip) ----
 long long langrew_num_params(int D, int H, int LD);
-size_t langrew_ws_floats(int B, int D, int H, int LD);
+// the batched step: (6 + 3N) B rows, N = num_negatives; langrew_batch_refused: 0, or 1 with the message set (no HIP call); the two
+// launchers below do not check again
+int langrew_batch_refused(const char* what, int B, int D, int H, int LD, int N);
+size_t langrew_ws_floats(int B, int D, int H, int LD, int N);
 int langrew_forward(const float* alle, const float* feats, const int* perm, const float* params, float* scores, float* ws, int B,
-                    int D, int H, int LD, int dt, hipStream_t s);
+                    int D, int H, int LD, int N, int dt, hipStream_t s);
 int langrew_backward(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, float* ws, int B, int D,
-                     int H, int LD, int accumulate, int dt, hipStream_t s);
+                     int H, int LD, int N, int accumulate, int dt, hipStream_t s);
 size_t langrew_call_ws_floats(int R, int D, int H, int LD);
 int langrew_call_forward(const float* e0, const float* eg, const float* le, const float* params, float* score, float* ws, int R,
                          int D, int H, int LD, hipStream_t s);

@@ -1,12 +1,12 @@
-// r3m_amd — language-reward head G(e_a, e_b, l) of R3M, batched: the reference evaluates LanguageReward 15 times per step
-// on [B, 2D+768] inputs (/root/reference/r3m/trainer.py:72-92 -> models_r3m.py:78-81 -> models_language.py:43-55); here
-// the 15 calls are ONE [15B, 2D+768] MLP pass (4 x Linear+ReLU on the MFMA gather-GEMM, final Linear(1024->1) as a GEMV),
+// r3m_amd — language-reward head G(e_a, e_b, l) of R3M, batched: the reference evaluates LanguageReward 6 + 3N times per step
+// (N = model.num_negatives, 3 by default: 15 times) on [B, 2D+768] inputs (/root/reference/r3m/trainer.py:72-92 -> models_r3m.py:78-81
+// -> models_language.py:43-55); here the calls are ONE [(6+3N)B, 2D+768] MLP pass (4 x Linear+ReLU on the MFMA gather-GEMM, final Linear(1024->1) as a GEMV),
 // forward and backward, with the permuted image pairs gathered on the fly and their gradients returned to alle through
 // the inverse permutations (gather form: no atomics, fixed summation order).
 //
 // Call order (row block q of the batched input; text features are NOT permuted, trainer.py:88-92):
 //   q0 (e0,eg) q1 (e0,es1) q2 (e0,es2) | q3 (e0,e0) q4 (e0,es0) q5 (e0,es1) | q6+3k+j: (e0[pi], other_j[pi]), pi = perm[3k+j],
-//   other_j = (eg, es1, es2)[j]
+//   other_j = (eg, es1, es2)[j], k = 0..N-1; perm / iperm are [3N][B]. 0 <= N <= LANG_MAX_NEG (N = 0: the six in-clip calls alone).
 // Parameter layout (flat, = state-dict order pred.{0,2,4,6,8}.{weight,bias}): W1[H][K1] b1[H] W2[H][H] b2 W3 b3 W4 b4 w5[H] b5[1]
 #include "engine.h"
 #include "conv_dev.h"
@@ -16,6 +16,9 @@ namespace r3m {
 
 // a Linear(K -> H) over R rows is the 1x1 convolution of R one-pixel images
 static ConvGeom linear_geom(int R, int K, int H) { return {R, 1, 1, K, H, 1, 1, 0}; }
+
+constexpr int LANG_MAX_NEG = 16;                       // = R3M_MAX_NEGATIVES (include/r3m_hip.h), the cap of csrc/loss.hip
+constexpr int LANG_MAX_CALLS = 6 + 3 * LANG_MAX_NEG;   // 54 row blocks
 
 __device__ __forceinline__ f32x4 ld4g(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
@@ -140,14 +143,14 @@ __global__ void sum_kernel(const float* __restrict__ v, float* __restrict__ out,
   }
 }
 
-// dalle[i,f,:] += sum over every row of dX that was gathered from alle[i,f,:]   (fixed order q = 0..14)
+// dalle[i,f,:] += sum over every row of dX that was gathered from alle[i,f,:]   (fixed order q = 0..Q-1, Q = 6 + 3N)
 template <class T>
 __global__ __launch_bounds__(256) void lang_scatter_kernel(const T* __restrict__ dX, const int* __restrict__ iperm,
-                                                            float* __restrict__ dalle, int B, int D, int LD) {
+                                                            float* __restrict__ dalle, int B, int D, int LD, int Q) {
   const int i = blockIdx.x, f = blockIdx.y;
   const long long K1 = 2LL * D + LD;
-  __shared__ int rows[15];
-  if (threadIdx.x < 15) {
+  __shared__ int rows[LANG_MAX_CALLS];
+  if (threadIdx.x < Q) {
     const int q = threadIdx.x;
     rows[q] = q < 6 ? i : iperm[(q - 6) * B + i];
   }
@@ -155,8 +158,8 @@ __global__ __launch_bounds__(256) void lang_scatter_kernel(const T* __restrict__
   float* out = dalle + ((long long)i * 5 + f) * D;
   for (int d = threadIdx.x * 4; d < D; d += 1024) {
     f32x4 g = ld4g(out + d);
-#pragma unroll
-    for (int q = 0; q < 15; ++q) {
+#pragma unroll 3
+    for (int q = 0; q < Q; ++q) {
       const T* x = dX + ((long long)q * B + rows[q]) * K1;
       if (f == 0) g += ld4t(x + d);                        // first image of every call is e0
       if (lang_bframe(q) == f) g += ld4t(x + D + d);       // second image
@@ -173,7 +176,7 @@ struct LangDims {
   long long X, Hh[4], dA, dB, Wt, wgp, cs, w16, total;
 };
 
-// R = rows of the MLP input: 15 B for the batched step (B clips), or the row count of ONE get_reward call (B = 0)
+// R = rows of the MLP input: (6 + 3N) B for the batched step (B clips), or the row count of ONE get_reward call (B = 0)
 static LangDims lang_dims_rows(int R, int B, int D, int H, int LD) {
   LangDims d;
   d.B = B; d.D = D; d.H = H; d.LD = LD; d.K1 = 2 * D + LD; d.R = R;
@@ -204,17 +207,27 @@ static LangDims lang_dims_rows(int R, int B, int D, int H, int LD) {
   return d;
 }
 
-static LangDims lang_dims(int B, int D, int H, int LD) { return lang_dims_rows(15 * B, B, D, H, LD); }
+static LangDims lang_dims(int B, int D, int H, int LD, int N) { return lang_dims_rows((6 + 3 * N) * B, B, D, H, LD); }
 
-long long langrew_num_params(int D, int H, int LD) { return lang_dims(1, D, H, LD).n_params; }
+long long langrew_num_params(int D, int H, int LD) { return lang_dims_rows(1, 0, D, H, LD).n_params; }
 size_t langrew_call_ws_floats(int R, int D, int H, int LD) { return (size_t)lang_dims_rows(R, 0, D, H, LD).total; }
-size_t langrew_ws_floats(int B, int D, int H, int LD) { return (size_t)lang_dims(B, D, H, LD).total; }
+size_t langrew_ws_floats(int B, int D, int H, int LD, int N) { return (size_t)lang_dims(B, D, H, LD, N).total; }
 
 static int check_dims(const LangDims& d, int dt = DT_F32) {
   R3M_REQUIRE(d.D % 32 == 0 && d.LD % 32 == 0 && d.H % 64 == 0, "langrew: D=%d, lang_dim=%d must be multiples of 32, hidden=%d of 64",
               d.D, d.LD, d.H);
   R3M_REQUIRE(dt == DT_F32 || dt == DT_BF16, "langrew: unknown dtype %d", dt);
   R3M_REQUIRE(dt == DT_F32 || d.LD % 64 == 0, "langrew(bf16): lang_dim=%d must be a multiple of 64", d.LD);
+  return 0;
+}
+
+// what the batched step refuses before it sizes anything: the number of negatives, and a row count (6 + 3N) B past a 32-bit int
+// (the GEMM launches then apply their own 32-bit index refusals to that row count)
+int langrew_batch_refused(const char* what, int B, int D, int H, int LD, int N) {
+  R3M_REQUIRE(N >= 0 && N <= LANG_MAX_NEG, "%s: num_negatives=%d is outside 0..16 (R3M_MAX_NEGATIVES)", what, N);
+  R3M_REQUIRE(B >= 1 && D >= 1 && H >= 1 && LD >= 1, "%s: B=%d D=%d hidden=%d lang_dim=%d", what, B, D, H, LD);
+  R3M_REQUIRE((long long)(6 + 3 * N) * B < (1LL << 31), "%s: (6 + 3 * %d) * B = %lld rows must stay below 2^31", what, N,
+              (long long)(6 + 3 * N) * B);
   return 0;
 }
 
@@ -283,8 +296,8 @@ static int mlp_forward(const LangDims& d, const float* params, float* scores, fl
 }
 
 int langrew_forward(const float* alle, const float* feats, const int* perm, const float* params, float* scores, float* ws, int B,
-                    int D, int H, int LD, int dt, hipStream_t s) {
-  const LangDims d = lang_dims(B, D, H, LD);
+                    int D, int H, int LD, int N, int dt, hipStream_t s) {
+  const LangDims d = lang_dims(B, D, H, LD, N);
   if (int e = check_dims(d, dt)) return e;
   if (dt == DT_BF16)
     hipLaunchKernelGGL((lang_gather_kernel<bf16_t>), dim3(d.R), dim3(256), 0, s, alle, feats, perm, as16(ws + d.X), B, D, LD);
@@ -318,7 +331,7 @@ static int mlp_backward(const LangDims& d, const float* dscore, const float* par
     hipLaunchKernelGGL((gemv_bwd_input_kernel<float>), dim3(ceil_div(n4, 256)), dim3(256), 0, s, dscore, H4, params + d.w[4], dA, n4, H / 4);
   if (int e = check_launch("lang_head_bwd")) return e;
   // hidden Linear layers 4..1:  dZ_l -> dW_l, db_l, dZ_{l-1} (ReLU mask of H_{l-1}: fused into the fp32 dgrad epilogue, a separate
-  // in-place pass for bf16). Ping-pong dA -> dB -> dA -> dB -> dA: the last product, dX [15B, K1], lands in dA (sized for K1).
+  // in-place pass for bf16). Ping-pong dA -> dB -> dA -> dB -> dA: the last product, dX [R, K1], lands in dA (sized for K1).
   float* dz = dA;
   float* nxt = dB;
   for (int l = 3; l >= 0; --l) {
@@ -348,16 +361,16 @@ static int mlp_backward(const LangDims& d, const float* dscore, const float* par
 }
 
 int langrew_backward(const float* dscore, const int* iperm, const float* params, float* grads, float* dalle, float* ws, int B, int D,
-                     int H, int LD, int accumulate, int dt, hipStream_t s) {
-  const LangDims d = lang_dims(B, D, H, LD);
+                     int H, int LD, int N, int accumulate, int dt, hipStream_t s) {
+  const LangDims d = lang_dims(B, D, H, LD, N);
   if (int e = check_dims(d, dt)) return e;
   float* dz = nullptr;
   if (int e = mlp_backward(d, dscore, params, grads, ws, accumulate, &dz, dt, s)) return e;
   if (dalle) {
     if (dt == DT_BF16)
-      hipLaunchKernelGGL((lang_scatter_kernel<bf16_t>), dim3(B, 5), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(dz), iperm, dalle, B, D, LD);
+      hipLaunchKernelGGL((lang_scatter_kernel<bf16_t>), dim3(B, 5), dim3(256), 0, s, reinterpret_cast<const bf16_t*>(dz), iperm, dalle, B, D, LD, 6 + 3 * N);
     else
-      hipLaunchKernelGGL((lang_scatter_kernel<float>), dim3(B, 5), dim3(256), 0, s, dz, iperm, dalle, B, D, LD);
+      hipLaunchKernelGGL((lang_scatter_kernel<float>), dim3(B, 5), dim3(256), 0, s, dz, iperm, dalle, B, D, LD, 6 + 3 * N);
     if (int e = check_launch("lang_scatter")) return e;
   }
   return 0;

@@ -149,15 +149,18 @@ class _BatchedRewardFn(torch.autograd.Function):
         alle = alle.contiguous()
         feats = feats.to(dtype=torch.float32).contiguous()
         perm = perm.to(device=alle.device, dtype=torch.int32).contiguous()
-        ws_bytes = L.r3m_langrew_workspace_bytes(B, D, module.hidden_dim, module.lang_dim)
+        N = perm.shape[0] // 3
+        ws_bytes = L.r3m_langrew_workspace_bytes_n(B, D, module.hidden_dim, module.lang_dim, N)
+        if not ws_bytes:
+            raise RuntimeError(f"r3m_hip langrew_workspace_bytes refused: {_lib.last_error()}")
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=alle.device)
-        scores = torch.empty((15, B), dtype=torch.float32, device=alle.device)
+        scores = torch.empty((6 + 3 * N, B), dtype=torch.float32, device=alle.device)
         with _lib.on(alle):
             dt = 1 if getattr(module, "precision", "fp32") == "bf16" else 0
-            _lib.check(L.r3m_langrew_forward_dt(alle.data_ptr(), feats.data_ptr(), perm.data_ptr(), module.flat_params().data_ptr(),
-                                                scores.data_ptr(), ws.data_ptr(), ws_bytes, B, D, module.hidden_dim, module.lang_dim,
-                                                dt, _lib.stream_ptr(alle.device)), "langrew_forward")
-        ctx.module, ctx.ws, ctx.ws_bytes, ctx.dims, ctx.dt = module, ws, ws_bytes, (B, D), dt
+            _lib.check(L.r3m_langrew_forward_n(alle.data_ptr(), feats.data_ptr(), perm.data_ptr(), module.flat_params().data_ptr(),
+                                               scores.data_ptr(), ws.data_ptr(), ws_bytes, B, D, module.hidden_dim, module.lang_dim,
+                                               N, dt, _lib.stream_ptr(alle.device)), "langrew_forward")
+        ctx.module, ctx.ws, ctx.ws_bytes, ctx.dims, ctx.dt = module, ws, ws_bytes, (B, D, N), dt
         ctx.save_for_backward(perm)
         return scores
 
@@ -166,16 +169,16 @@ class _BatchedRewardFn(torch.autograd.Function):
         L = _lib.lib()
         (perm,) = ctx.saved_tensors
         module = ctx.module
-        B, D = ctx.dims
+        B, D, N = ctx.dims
         iperm = inverse_permutations(perm).contiguous()
         dalle = torch.zeros((B, 5, D), dtype=torch.float32, device=dscores.device)
         g = module.flat_grads()
         accumulate = 0 if module._grad_fresh else 1
         dscores = dscores.contiguous()
         with _lib.on(dscores):
-            _lib.check(L.r3m_langrew_backward_dt(dscores.data_ptr(), iperm.data_ptr(), module.flat_params().data_ptr(),
-                                                 g.data_ptr(), dalle.data_ptr(), ctx.ws.data_ptr(), ctx.ws_bytes, B, D, module.hidden_dim,
-                                                 module.lang_dim, accumulate, ctx.dt, _lib.stream_ptr(dscores.device)), "langrew_backward")
+            _lib.check(L.r3m_langrew_backward_n(dscores.data_ptr(), iperm.data_ptr(), module.flat_params().data_ptr(),
+                                                g.data_ptr(), dalle.data_ptr(), ctx.ws.data_ptr(), ctx.ws_bytes, B, D, module.hidden_dim,
+                                                module.lang_dim, N, accumulate, ctx.dt, _lib.stream_ptr(dscores.device)), "langrew_backward")
         module._grad_fresh = False
         module._has_grads = True
         ctx.ws = None
@@ -326,9 +329,17 @@ class LanguageReward(nn.Module):
 
     # ---- compute ----
     def batched_scores(self, alle, feats, lang_perm):
-        """All 15 reward evaluations of Trainer.update in one pass. alle [B,5,D] (requires grad), feats [B,lang_dim] frozen,
-        lang_perm [9,B] = the reference's randperm draws (trainer.py:86-92). Returns scores [15,B] (rows: pos1-3, in-clip
-        negatives 1-3, then for each k the permuted negatives of heads 1-3)."""
+        """All 6 + 3N reward evaluations of Trainer.update in one pass (N = num_negatives, taken from lang_perm: 15 evaluations at the
+        reference's 3). alle [B,5,D] (requires grad), feats [B,lang_dim] frozen, lang_perm [3N,B] = the reference's randperm draws
+        (trainer.py:86-92), row 3k + j the k-th draw of head j; N = 0 is an empty [0,B] tensor. Returns scores [6+3N,B] (rows:
+        pos1-3, in-clip negatives 1-3, then row 6 + 3k + j the k-th permuted negative of head j)."""
+        from .ops import MAX_NEGATIVES
+        if lang_perm.dim() != 2 or lang_perm.shape[1] != alle.shape[0]:
+            raise ValueError(f"LanguageReward.batched_scores: lang_perm {tuple(lang_perm.shape)} must be [3 * num_negatives, B] with "
+                             f"B = {alle.shape[0]}")
+        if lang_perm.shape[0] % 3 != 0 or lang_perm.shape[0] // 3 > MAX_NEGATIVES:
+            raise ValueError(f"LanguageReward.batched_scores: lang_perm has {lang_perm.shape[0]} rows; it must hold 3 per negative "
+                             f"(heads a, b, c) for 0..{MAX_NEGATIVES} negatives")
         if not alle.is_cuda:
             raise RuntimeError("r3m_amd.LanguageReward runs on the HIP path only (no CPU fallback)")
         anchor = self.pred._modules["0"].weight

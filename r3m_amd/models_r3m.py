@@ -2,6 +2,7 @@
 (/root/reference/r3m/models/models_r3m.py:21-107), with every FLOP on the HIP path:
 
     R3M(device, lr, hidden_dim, size=34, l2weight=1.0, l1weight=1.0, langweight=1.0, tcnweight=0.0, l2dist=True, bs=16)
+      (+ keywords of this package; num_negatives=3 is the value the reference's constructor hard-wires, 0..16 here)
       .forward(obs, num_ims=1, obs_shape=[3,224,224]) -> [F, outdim]      obs in 0..255, NCHW        (models_r3m.py:84-100)
       .sim(t1, t2) -> [B]                              -||a-b||_2 or cosine                          (models_r3m.py:102-107)
       .get_reward(e0, es, sentences) -> (score[B], {})                                               (models_r3m.py:78-81)
@@ -34,7 +35,8 @@ class _NormalizeSpec(nn.Module):
 
 class R3M(nn.Module):
     def __init__(self, device, lr, hidden_dim, size=34, l2weight=1.0, l1weight=1.0, langweight=1.0, tcnweight=0.0,
-                 l2dist=True, bs=16, precision="fp32", max_live_forwards=1, weight_decay=0.0, grad_clip=0.0, native_text=False):
+                 l2dist=True, bs=16, precision="fp32", max_live_forwards=1, weight_decay=0.0, grad_clip=0.0, native_text=False,
+                 num_negatives=3):
         super().__init__()
         self.device = device
         self.use_tb = False
@@ -44,7 +46,10 @@ class R3M(nn.Module):
         self.l2dist = l2dist         # -L2 distance (True) or cosine similarity (False)
         self.langweight = langweight
         self.size = size
-        self.num_negatives = 3
+        # cross-clip negatives of both InfoNCE losses (models_r3m.py:34 sets 3; trainer.py:66,124 read the attribute every step, so it
+        # stays a plain writable attribute and Trainer.update checks it again)
+        from .ops import check_num_negatives
+        self.num_negatives = check_num_negatives(num_negatives, tcnweight, "R3M")
 
         self.cs = nn.CosineSimilarity(1)
         self.bce = nn.BCELoss(reduction="none")

@@ -4,9 +4,12 @@
   * the 5B frames go through the HIP encoder engine in one call (trainer.py:39-41);
   * LP norms + TCN InfoNCE + language InfoNCE are the fused loss kernels of csrc/loss.hip, forward and backward together
     (trainer.py:52-59, 64-118, 122-150) — the permutations are still drawn with torch.randperm on the CPU generator in the
-    reference's order (language: (a,b,c) x 3 at :86-92, then TCN: (es0, es2) x 3 at :136-137), uploaded once;
-  * the 15 reward-head evaluations are one batched [15B, 2D+768] GEMM chain (models_language.LanguageReward.batched);
-    the frozen sentence features are computed once per step instead of 15 times (trainer.py:72-92 -> models_r3m.py:78-81);
+    reference's order (language: (a,b,c) x N at :86-92, then TCN: (es0, es2) x N at :136-137), uploaded once. N is
+    model.module.num_negatives, read once per step as the reference reads it (:66, :124), 3 unless the user changed it; the HIP
+    objective takes 0..16 (0 only without the time-contrastive loss) and anything else raises ValueError before the encoder runs;
+  * the 6 + 3N reward-head evaluations (15 at N = 3) are one batched [(6+3N)B, 2D+768] GEMM chain
+    (models_language.LanguageReward.batched_scores); the frozen sentence features are computed once per step instead of once per
+    evaluation (trainer.py:72-92 -> models_r3m.py:78-81);
   * with a data-parallel wrapper built with global_negatives=True the rank's [B,5,D] embeddings (and sentence features / mask)
     are all-gathered first and everything below runs on the global batch, as the reference's DataParallel step does on GPU 0
     (trainer.py:41: `alles` is the gathered output); permutations are drawn by every rank (same RNG consumption) and rank 0's
@@ -39,6 +42,8 @@ class Trainer:
         b_im, b_lang = batch
         t2 = time.time()
         core = model.module
+        # users set the attribute after construction, as on the reference: checked here again, before anything runs
+        num_neg = ops.check_num_negatives(core.num_negatives, core.tcnweight, "Trainer.update")
 
         bs = b_im.shape[0]
         b_im_r = b_im.reshape(bs * 5, 3, 224, 224)
@@ -54,10 +59,11 @@ class Trainer:
         scores = mask = None
         lang_perm = None
         if core.langweight > 0:
-            lang_perm = torch.stack([torch.randperm(bs) for _ in range(3 * core.num_negatives)])  # (a,b,c) x num_neg
+            lang_perm = torch.stack([torch.randperm(bs) for _ in range(3 * num_neg)]) if num_neg else \
+                torch.empty((0, bs), dtype=torch.int64)                                           # (a,b,c) x num_neg
         tcn_perm = None
         if core.tcnweight > 0:
-            tcn_perm = torch.stack([torch.randperm(bs) for _ in range(2 * core.num_negatives)]).to(torch.int32)
+            tcn_perm = torch.stack([torch.randperm(bs) for _ in range(2 * num_neg)]).to(torch.int32)
             tcn_perm = _lib.upload_small(tcn_perm, alle.device)      # pinned staging: a pageable copy would stall the host here
             if gneg:
                 tcn_perm = model.share(tcn_perm)
@@ -81,7 +87,7 @@ class Trainer:
         t5 = time.time()
 
         full_loss, m = ops.r3m_loss(alle, tcn_perm, core.l2weight, core.l1weight, core.tcnweight, l2dist=core.l2dist,
-                                    scores=scores, mask=mask, langweight=core.langweight)
+                                    scores=scores, mask=mask, langweight=core.langweight, num_negatives=num_neg)
         t6 = time.time()
         # The metrics are final once the objective's forward has run: their device->host copy is queued HERE, in front of the
         # backward pass, and the host waits for that copy only — it returns while the GPU still works through backward + Adam and
