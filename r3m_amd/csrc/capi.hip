@@ -388,40 +388,6 @@ int r3m_conv2d_fwd_affine_dt(const void* x, const void* w, void* out, const floa
               "(128, 128|16 or 128|2|16 on a fusing route): the engine runs conv + bn_act_fwd here", flags);
   return conv_forward_launch_affine(FP(x), FP(w), FPM(out), scale, shift, g, flags, dtype, S(stream));
 }
-size_t r3m_conv2d_small_workspace_bytes(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int split) {
-  const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
-  const int fl = EPI_AFFINE | EPI_RELU;
-  if (!small_conv_plan(g, fl, split).grid) return 0;
-  return small_conv_ctr_bytes(g, fl, split) + small_conv_slab_bytes(g, fl, split);
-}
-int r3m_conv2d_fwd_affine_small(const float* x, const float* w, float* out, const float* scale, const float* shift, int N, int Hi, int Wi,
-                                int Ci, int Co, int k, int stride, int pad, int flags, int split, void* workspace, size_t workspace_bytes,
-                                r3m_stream_t stream) {
-  R3M_REQUIRE(x && w && out && scale && shift, "conv2d_fwd_affine_small: null argument");
-  R3M_REQUIRE(!small_linear_flags(flags), "conv2d_fwd_affine_small: epilogue flags %d are a Linear store (r3m_linear_fwd_small); this entry "
-              "takes 128, 128|16 or 128|2|16", flags);
-  const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
-  const SmallConvPlan r = small_conv_plan(g, flags, split);
-  if (!r.grid || split < 0 || split > small_conv_max_split(g))      // a shape, flag set or split the kernel does not take: the launcher says why
-    return launch_conv_small(x, w, out, scale, shift, g, flags, split, nullptr, nullptr, S(stream));
-  const size_t ctr = small_conv_ctr_bytes(g, flags, split), need = ctr + small_conv_slab_bytes(g, flags, split);
-  R3M_REQUIRE(workspace && workspace_bytes >= need, "conv2d_fwd_affine_small: the workspace has %zu bytes, this launch needs %zu "
-              "(r3m_conv2d_small_workspace_bytes)", workspace ? workspace_bytes : (size_t)0, need);
-  if (r.S > 1 && hipMemsetAsync(workspace, 0, ctr, S(stream)) != hipSuccess) {
-    set_last_error("conv2d_fwd_affine_small: cannot reset the tickets");
-    return 1;
-  }
-  return launch_conv_small(x, w, out, scale, shift, g, flags, split, static_cast<unsigned*>(workspace),
-                           reinterpret_cast<float*>(static_cast<char*>(workspace) + ctr), S(stream));
-}
-int r3m_debug_conv_small_plan(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int* out, int cap) {
-  if (!out || cap < 10) { set_last_error("debug_conv_small_plan: the output buffer needs 10 ints"); return -1; }
-  const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
-  const SmallConvPlan r = small_conv_plan(g, flags, 0);
-  const int v[10] = {r.take, r.bm, r.bn, r.S, r.grid, r.cps, r.tiles_m, r.tiles_n, r.nch, r.grid ? small_conv_max_split(g) : 0};
-  for (int i = 0; i < 10; ++i) out[i] = v[i];
-  return 10;
-}
 int r3m_resnet_inference_prepare(r3m_resnet_t h, const float* params, const float* buffers, void* arena, r3m_stream_t stream) {
   R3M_REQUIRE(h && params && buffers && arena, "resnet_inference_prepare: null argument");
   return plan_inference_prepare(*PLAN(h), params, buffers, static_cast<float*>(arena), S(stream));
@@ -669,50 +635,7 @@ int r3m_avgpool_bwd(const float* dh, float* dx, int N, int HW, int C, r3m_stream
 int r3m_linear_fwd(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int relu, r3m_stream_t stream) {
   return conv_forward_launch(x, w, y, nullptr, bias, {M, 1, 1, K, N, 1, 1, 0}, (bias ? EPI_BIAS : 0) | (relu ? EPI_RELU : 0), DT_F32, S(stream));
 }
-// few rows: the split-K kernel of conv_small.hip on the 1 x 1 geometry, Linear stores
-static const char* linear_small_refuses(int M, int K, int N, int flags) {
-  if (!small_linear_flags(flags)) return "flags must be 8 (bias), 8|16 (+ ReLU) or 8|256 (+ GELU); the convolution stores belong to r3m_conv2d_fwd_affine_small";
-  if (M < 1) return "M must be at least 1";
-  if (K < 32 || (K & 31)) return "K must be a multiple of 32";
-  if (N < 64 || (N & 63)) return "N must be a multiple of 64";
-  return small_conv_refuses({M, 1, 1, K, N, 1, 1, 0}, flags);
-}
-size_t r3m_linear_small_workspace_bytes(int M, int K, int N, int split) {
-  const ConvGeom g{M, 1, 1, K, N, 1, 1, 0};
-  const int fl = EPI_BIAS;
-  if (linear_small_refuses(M, K, N, fl) || !small_conv_plan(g, fl, split).grid) return 0;
-  return small_conv_ctr_bytes(g, fl, split) + small_conv_slab_bytes(g, fl, split);
-}
-int r3m_linear_fwd_small(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int flags, int split,
-                         void* workspace, size_t workspace_bytes, r3m_stream_t stream) {
-  R3M_REQUIRE(x && w && bias && y, "linear_fwd_small: null argument");
-  if (const char* why = linear_small_refuses(M, K, N, flags)) {
-    set_last_error("linear_fwd_small: %s (M=%d K=%d N=%d flags=%d)", why, M, K, N, flags);
-    return 1;
-  }
-  const ConvGeom g{M, 1, 1, K, N, 1, 1, 0};
-  R3M_REQUIRE(split >= 0 && split <= small_conv_max_split(g), "linear_fwd_small: split=%d outside 0..%d", split, small_conv_max_split(g));
-  const size_t ctr = small_conv_ctr_bytes(g, flags, split), need = ctr + small_conv_slab_bytes(g, flags, split);
-  const SmallConvPlan r = small_conv_plan(g, flags, split);
-  R3M_REQUIRE(r.S == 1 || workspace, "linear_fwd_small: %d slices need a workspace (r3m_linear_small_workspace_bytes)", r.S);
-  R3M_REQUIRE(!workspace || workspace_bytes >= need, "linear_fwd_small: the workspace has %zu bytes, this launch needs %zu "
-              "(r3m_linear_small_workspace_bytes)", workspace_bytes, need);
-  if (r.S > 1 && hipMemsetAsync(workspace, 0, ctr, S(stream)) != hipSuccess) {
-    set_last_error("linear_fwd_small: cannot reset the tickets");
-    return 1;
-  }
-  return launch_conv_small(x, w, y, nullptr, bias, g, flags, split, static_cast<unsigned*>(workspace),
-                           workspace ? reinterpret_cast<float*>(static_cast<char*>(workspace) + ctr) : nullptr, S(stream));
-}
-int r3m_debug_linear_small_plan(int M, int K, int N, int flags, int* out, int cap) {
-  if (!out || cap < 10) { set_last_error("debug_linear_small_plan: the output buffer needs 10 ints"); return -1; }
-  for (int i = 0; i < 10; ++i) out[i] = 0;
-  if (const char* why = linear_small_refuses(M, K, N, flags)) {
-    set_last_error("debug_linear_small_plan: %s (M=%d K=%d N=%d flags=%d)", why, M, K, N, flags);
-    return 10;
-  }
-  return r3m_debug_conv_small_plan(M, 1, 1, K, N, 1, 1, 0, flags, out, cap);
-}
+// (r3m_linear_fwd_small, the same product over few rows, is with its kernel in conv_small.hip)
 
 long long r3m_langrew_num_params(int D, int hidden, int lang_dim) { return langrew_num_params(D, hidden, lang_dim); }
 // The batched head: every form is the `_n` call (N = num_negatives; the forms without it are N = 3). Argument checks first, no HIP call

@@ -16,13 +16,17 @@
 //     the S slabs IN SLICE ORDER (its own included, read back like the others), applies scale / shift, the residual and the ReLU and
 //     stores. No block waits for another one: no spinning, no grid barrier, no floating-point atomics — the same operands give the same
 //     bits on every launch whichever block arrives last. S = 1 stores from the accumulators and touches neither counter nor slab.
-// The counters are zeroed by a hipMemsetAsync ahead of the launch (the C entry does it per launch, the engine once per forward).
+// Tickets and slabs live in the caller's workspace, laid out by ONE type for every caller: SmallLaunchSet (declared in engine.h with
+// the layout rule, defined below) lists a call's launches, gives each its own ticket block, zeroes all of them with one
+// hipMemsetAsync ahead of the first launch and shares one slab area between them. The encoder's prepared forward (engine.hip), the
+// reward head (lang.hip), the text model (text.hip) and the single-launch C entries at the end of this file all go through it.
 //
 // A Linear over few rows is the same launch: the 1 x 1 geometry (M, 1, 1, K, N, 1, 1, 0) makes the main loop y[M, N] = x[M, K] w[N, K]^T.
 // Only the store differs, so the store is a template parameter (SmallStore): the convolution instantiations keep the affine store
 // above, the Linear ones store acc + bias[col] with an optional ReLU (EPI_BIAS [| EPI_RELU]: the reward head) or through the exact GELU
 // (EPI_BIAS | EPI_GELU: the text model's lin1). Main loop, slabs, tickets and the slice-order sum are one body for all of them.
 #include "engine.h"
+#include "../../include/r3m_hip.h"
 #include <algorithm>
 #include <cstring>
 
@@ -226,13 +230,6 @@ SmallConvPlan small_conv_plan(const ConvGeom& c, int flags, int split) {
   return r;
 }
 
-static size_t small_ctr_bytes(const SmallConvPlan& r) { return ((size_t)r.tiles_m * r.tiles_n * 4 + 255) / 256 * 256; }
-size_t small_conv_ctr_bytes(const ConvGeom& c, int flags, int split) { return small_ctr_bytes(small_conv_plan(c, flags, split)); }
-size_t small_conv_slab_bytes(const ConvGeom& c, int flags, int split) {
-  const SmallConvPlan r = small_conv_plan(c, flags, split);
-  return (size_t)r.S * r.tiles_m * r.bm * c.Co * 4;
-}
-
 template <int ST>
 static void launch_small_tile(const SmallConvParams& p, const SmallConvPlan& r, hipStream_t s) {
   switch (r.bm) {
@@ -264,4 +261,126 @@ int launch_conv_small(const float* x, const float* w, float* out, const float* s
   return check_launch("conv_small");
 }
 
+// ---- the workspace of one call (engine.h states the layout) ----
+int SmallLaunchSet::add(const ConvGeom& g, int flags, int split, SmallRoute route) {
+  if (n == CAP) return -1;
+  Entry& t = e[n];
+  t = Entry{g, flags, split, false, 0, 0, ctr_bytes};
+  if (route != SMALL_NEVER) {
+    const SmallConvPlan r = small_conv_plan(g, flags, split);
+    t.run = route == SMALL_FORCED ? r.grid != 0 : r.take != 0;
+    if (t.run) {
+      t.S = r.S;
+      t.ctr = ((size_t)r.tiles_m * r.tiles_n * 4 + 255) / 256 * 256;          // one ticket per tile, padded to 256 bytes
+      ctr_bytes += t.ctr;
+      slab_bytes = std::max(slab_bytes, (size_t)r.S * r.tiles_m * r.bm * g.Co * 4);   // S slabs of tiles_m * bm rows x Co
+    }
+  }
+  return n++;
+}
+
+int SmallLaunchSet::reset(void* base, hipStream_t s) const {
+  return ticket_bytes() && hipMemsetAsync(base, 0, ticket_bytes(), s) != hipSuccess;
+}
+
+int SmallLaunchSet::launch(int i, int rep, void* base, const float* x, const float* w, float* out, const float* scale, const float* shift,
+                           hipStream_t s, int flags) const {
+  const Entry& t = e[i];
+  char* b = static_cast<char*>(base);
+  return launch_conv_small(x, w, out, scale, shift, t.g, flags < 0 ? t.flags : flags, t.split,
+                           b ? reinterpret_cast<unsigned*>(b + rep * ctr_bytes + t.ctr_off) : nullptr,
+                           b ? reinterpret_cast<float*>(b + ticket_bytes()) : nullptr, s);
+}
+
+int SmallLaunchSet::linear(int i, int rep, void* base, const float* x, const float* w, const float* bias, float* y, hipStream_t s) const {
+  const Entry& t = e[i];
+  if (t.run) return launch(i, rep, base, x, w, y, nullptr, bias, s);
+  if (!(t.flags & EPI_GELU)) return conv_forward_launch(x, w, y, nullptr, bias, t.g, t.flags, DT_F32, s);
+  TRY(conv_forward_launch(x, w, y, nullptr, nullptr, t.g, 0, DT_F32, s));
+  return launch_bias_gelu(y, bias, t.g.N, t.g.Co, s);
+}
+
+// What the single-launch C entries share: a one-entry set on the caller's workspace — size, check the workspace, reset, launch.
+// A shape, flag set or split the kernel does not take goes to the launcher, which says why. sizer: the entry's *_workspace_bytes,
+// for the messages; ws_optional: a launch of one slice runs without a workspace.
+static int small_entry(const char* what, const char* sizer, bool ws_optional, const float* x, const float* w, float* out,
+                       const float* scale, const float* shift, const ConvGeom& g, int flags, int split, void* ws, size_t ws_bytes,
+                       hipStream_t s) {
+  SmallLaunchSet set;
+  set.add(g, flags, split, SMALL_FORCED);
+  if (!set.runs(0) || split < 0 || split > small_conv_max_split(g)) return launch_conv_small(x, w, out, scale, shift, g, flags, split, nullptr, nullptr, s);
+  const int S = set.e[0].S;
+  if (ws_optional) R3M_REQUIRE(S == 1 || ws, "%s: %d slices need a workspace (%s)", what, S, sizer);
+  R3M_REQUIRE(ws ? ws_bytes >= set.bytes() : ws_optional, "%s: the workspace has %zu bytes, this launch needs %zu (%s)", what,
+              ws ? ws_bytes : (size_t)0, set.bytes(), sizer);
+  R3M_REQUIRE(S == 1 || !set.reset(ws, s), "%s: cannot reset the tickets", what);   // one slice touches no ticket
+  return set.launch(0, 0, ws, x, w, out, scale, shift, s);
+}
+static size_t small_entry_bytes(const ConvGeom& g, int flags, int split) {
+  SmallLaunchSet set;
+  set.add(g, flags, split, SMALL_FORCED);
+  return set.bytes();
+}
+
+static const char* linear_small_refuses(int M, int K, int N, int flags) {
+  if (!small_linear_flags(flags)) return "flags must be 8 (bias), 8|16 (+ ReLU) or 8|256 (+ GELU); the convolution stores belong to r3m_conv2d_fwd_affine_small";
+  if (M < 1) return "M must be at least 1";
+  if (K < 32 || (K & 31)) return "K must be a multiple of 32";
+  if (N < 64 || (N & 63)) return "N must be a multiple of 64";
+  return small_conv_refuses({M, 1, 1, K, N, 1, 1, 0}, flags);
+}
+
 }  // namespace r3m
+
+using namespace r3m;
+static inline hipStream_t S(r3m_stream_t s) { return static_cast<hipStream_t>(s); }
+
+extern "C" {
+
+size_t r3m_conv2d_small_workspace_bytes(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int split) {
+  return small_entry_bytes({N, Hi, Wi, Ci, Co, k, stride, pad}, EPI_AFFINE | EPI_RELU, split);
+}
+int r3m_conv2d_fwd_affine_small(const float* x, const float* w, float* out, const float* scale, const float* shift, int N, int Hi, int Wi,
+                                int Ci, int Co, int k, int stride, int pad, int flags, int split, void* workspace, size_t workspace_bytes,
+                                r3m_stream_t stream) {
+  R3M_REQUIRE(x && w && out && scale && shift, "conv2d_fwd_affine_small: null argument");
+  R3M_REQUIRE(!small_linear_flags(flags), "conv2d_fwd_affine_small: epilogue flags %d are a Linear store (r3m_linear_fwd_small); this entry "
+              "takes 128, 128|16 or 128|2|16", flags);
+  return small_entry("conv2d_fwd_affine_small", "r3m_conv2d_small_workspace_bytes", false, x, w, out, scale, shift,
+                     {N, Hi, Wi, Ci, Co, k, stride, pad}, flags, split, workspace, workspace_bytes, S(stream));
+}
+int r3m_debug_conv_small_plan(int N, int Hi, int Wi, int Ci, int Co, int k, int stride, int pad, int flags, int* out, int cap) {
+  if (!out || cap < 10) { set_last_error("debug_conv_small_plan: the output buffer needs 10 ints"); return -1; }
+  const ConvGeom g{N, Hi, Wi, Ci, Co, k, stride, pad};
+  const SmallConvPlan r = small_conv_plan(g, flags, 0);
+  const int v[10] = {r.take, r.bm, r.bn, r.S, r.grid, r.cps, r.tiles_m, r.tiles_n, r.nch, r.grid ? small_conv_max_split(g) : 0};
+  for (int i = 0; i < 10; ++i) out[i] = v[i];
+  return 10;
+}
+
+// a Linear over few rows: the 1 x 1 geometry, Linear stores
+size_t r3m_linear_small_workspace_bytes(int M, int K, int N, int split) {
+  if (linear_small_refuses(M, K, N, EPI_BIAS)) return 0;
+  return small_entry_bytes({M, 1, 1, K, N, 1, 1, 0}, EPI_BIAS, split);
+}
+int r3m_linear_fwd_small(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int flags, int split,
+                         void* workspace, size_t workspace_bytes, r3m_stream_t stream) {
+  R3M_REQUIRE(x && w && bias && y, "linear_fwd_small: null argument");
+  if (const char* why = linear_small_refuses(M, K, N, flags)) {
+    set_last_error("linear_fwd_small: %s (M=%d K=%d N=%d flags=%d)", why, M, K, N, flags);
+    return 1;
+  }
+  return small_entry("linear_fwd_small", "r3m_linear_small_workspace_bytes", true, x, w, y, nullptr, bias, {M, 1, 1, K, N, 1, 1, 0}, flags,
+                     split, workspace, workspace_bytes, S(stream));
+}
+int r3m_debug_linear_small_plan(int M, int K, int N, int flags, int* out, int cap) {
+  if (!out || cap < 10) { set_last_error("debug_linear_small_plan: the output buffer needs 10 ints"); return -1; }
+  for (int i = 0; i < 10; ++i) out[i] = 0;
+  if (const char* why = linear_small_refuses(M, K, N, flags)) {
+    set_last_error("debug_linear_small_plan: %s (M=%d K=%d N=%d flags=%d)", why, M, K, N, flags);
+    return 10;
+  }
+  return r3m_debug_conv_small_plan(M, 1, 1, K, N, 1, 1, 0, flags, out, cap);
+}
+
+}  // extern "C"

@@ -77,11 +77,43 @@ SmallConvPlan small_conv_plan(const ConvGeom& c, int flags, int split);
 int small_conv_max_split(const ConvGeom& c);
 bool small_linear_flags(int flags);                                      // one of the three Linear flag sets
 const char* small_conv_refuses(const ConvGeom& c, int flags);            // null, or why the kernel does not take the launch at all
-size_t small_conv_ctr_bytes(const ConvGeom& c, int flags, int split);    // one ticket per tile, padded to 256 bytes
-size_t small_conv_slab_bytes(const ConvGeom& c, int flags, int split);   // S slabs of tiles_m * bm rows x Co
 // ctr: the launch's zeroed tickets, slabs: its slab area (both may be null when the plan has one slice)
 int launch_conv_small(const float* x, const float* w, float* out, const float* scale, const float* shift, const ConvGeom& c, int flags,
                       int split, unsigned* ctr, float* slabs, hipStream_t s);
+
+int launch_bias_gelu(float* x, const float* bias, long long rows, int C, hipStream_t s);   // text.hip: x = gelu(x + bias[col]) in place
+
+// The split-K workspace of ONE call (a forward of the encoder, of the reward head, of the text model, or a single launch): the ordered
+// list of the call's launches, run `reps` times over (the text model's four Linears, once per layer). The rule, stated here once:
+//   [ticket blocks in launch order: repetition 0's entries, repetition 1's, ...][one slab area]
+// a ticket block (one ticket per tile, padded to 256 bytes) belongs to exactly one launch, reset() zeroes all of them with ONE memset
+// ahead of the first launch, and the slab area is shared, sized for the largest launch: the launches are ordered on the stream.
+// An entry the set does not run on the kernel has no ticket block and leaves the slab size alone; its caller runs the ordinary kernel.
+// Plain data of fixed capacity: building one on the stack per call allocates nothing.
+// SmallRoute says which entries run on the kernel: those the routing rule takes (small_conv_plan(...).take), every one the kernel accepts at all (the
+// single-launch C entries), or none (the caller's ordinary path through the same code)
+enum SmallRoute { SMALL_BY_RULE = 0, SMALL_FORCED = 1, SMALL_NEVER = 2 };
+struct SmallLaunchSet {
+  static constexpr int CAP = 56;                      // a ResNet-50 has 53 convolutions (BnEvalTable has the same room)
+  struct Entry { ConvGeom g; int flags, split; bool run; int S; size_t ctr, ctr_off; };   // run: on the kernel, in S slices, with ctr ticket bytes
+  Entry e[CAP];
+  int n = 0, reps = 1;
+  size_t ctr_bytes = 0, slab_bytes = 0;               // tickets of one repetition; the slab area
+  // appends a launch and returns its index; past CAP entries it returns -1 and the launch is not run here
+  int add(const ConvGeom& g, int flags, int split = 0, SmallRoute route = SMALL_BY_RULE);
+  bool runs(int i) const { return i >= 0 && i < n && e[i].run; }
+  size_t ticket_bytes() const { return ctr_bytes * reps; }
+  size_t bytes() const { return ticket_bytes() + slab_bytes; }
+  // the single memset (none when no entry has tickets); non-zero when it fails, the caller names the call in its error
+  int reset(void* base, hipStream_t s) const;
+  // entry i of repetition rep on the kernel, with its own ticket block and the shared slab area; flags >= 0: another store of the
+  // same family than the entry was planned with (the plan does not depend on which)
+  int launch(int i, int rep, void* base, const float* x, const float* w, float* out, const float* scale, const float* shift,
+             hipStream_t s, int flags = -1) const;
+  // y = store(x w^T + bias) of Linear entry i: launch() when the set runs it, else the ordinary launches — conv_forward_launch with
+  // the entry's flags, and for EPI_BIAS | EPI_GELU the plain GEMM followed by launch_bias_gelu
+  int linear(int i, int rep, void* base, const float* x, const float* w, const float* bias, float* y, hipStream_t s) const;
+};
 
 // ---- the plan ----
 struct Plan;

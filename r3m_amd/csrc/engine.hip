@@ -141,10 +141,8 @@ struct Plan {
   long long wt_elems = 0;
   // options (plan_set_*)
   int fuse_bnred = 1;       // BatchNorm-backward partials from the producing dgrad's epilogue (EPI_BNRED); 0: stand-alone reduce pass
-  // the small-M kernel (conv_small.hip) in a prepared forward: per convolution its ticket block inside the caller's workspace (-1: the
-  // routing rule leaves the launch where it is), all ticket blocks first (one memset per call), one slab area behind them for all
-  std::vector<long long> small_ctr_off;
-  long long small_ctr_bytes = 0, small_slab_bytes = 0;
+  // the small-M kernel (conv_small.hip) in a prepared forward: entry i is convolution i, on the caller's workspace (fp32 plans; empty otherwise)
+  SmallLaunchSet small;
   std::vector<unsigned char> trainable;   // plan_set_trainable: one byte per tensor, empty = all trainable (read by the next stage 0)
   int bn_pair = R3M_BN_PAIR_DEFAULT;   // the two tail BatchNorms of a downsample block share their backward passes (bn_backward_pair); 0: separate passes
   RunState run;
@@ -407,16 +405,8 @@ Plan* plan_create(int size, int F, int dtype, int H, int W) {
     if (emax > 0) P.E_off = take(emax);
   }
   P.arena_floats = off;
-  P.small_ctr_off.assign(P.convs.size(), -1);
-  if (dtype == DT_F32)
-    for (size_t i = 1; i < P.convs.size(); ++i) {
-      const ConvGeom g = P.convs[i].geom(F);
-      const int fl = EPI_AFFINE | EPI_RELU;   // the plan does not depend on which of the three stores the launch makes
-      if (!small_conv_plan(g, fl, 0).take) continue;
-      P.small_ctr_off[i] = P.small_ctr_bytes;
-      P.small_ctr_bytes += (long long)small_conv_ctr_bytes(g, fl, 0);
-      P.small_slab_bytes = std::max(P.small_slab_bytes, (long long)small_conv_slab_bytes(g, fl, 0));
-    }
+  if (dtype == DT_F32)   // the plan does not depend on which of the three stores the launch makes; the stem (entry 0) is never a launch of the set
+    for (size_t i = 0; i < P.convs.size(); ++i) P.small.add(P.convs[i].geom(F), EPI_AFFINE | EPI_RELU, 0, i ? SMALL_BY_RULE : SMALL_NEVER);
   return Pp;
 }
 
@@ -694,9 +684,8 @@ static bool block_fusable(Ctx& c, const BlockSpec& B) {
 }
 static int conv_bn_fused(Ctx& c, const ConvSpec& L, const float* X, float* out, int flags) {
   TRY(bn_forward_coeffs(c, L));
-  if (const long long co = c.P.small_ctr_off[&L - c.P.convs.data()]; c.small_ws && co >= 0)
-    return launch_conv_small(X, c.params + L.w_off, out, c.coef(L).scale, c.coef(L).shift, L.geom(c.P.F), flags, 0,
-                             reinterpret_cast<unsigned*>(c.small_ws + co), reinterpret_cast<float*>(c.small_ws + c.P.small_ctr_bytes), c.s);
+  if (const int i = (int)(&L - c.P.convs.data()); c.small_ws && c.P.small.runs(i))
+    return c.P.small.launch(i, 0, c.small_ws, X, c.params + L.w_off, out, c.coef(L).scale, c.coef(L).shift, c.s, flags);
   TileCounters tc(c, TileCounters::FORWARD, L);
   return conv_forward_launch_affine(X, fwd_weights(c, L), out, c.coef(L).scale, c.coef(L).shift, L.geom(c.P.F), flags, c.dt, c.s);
 }
@@ -784,20 +773,17 @@ int plan_inference_prepare(Plan& P, const float* params, const float* bufs, floa
   P.run.prepared = arena;
   return 0;
 }
-long long plan_inference_workspace_bytes(Plan* P) { return P->small_ctr_bytes + P->small_slab_bytes; }
+long long plan_inference_workspace_bytes(Plan* P) { return (long long)P->small.bytes(); }
 int plan_forward_prepared(Plan& P, const float* x_nchw, const float* params, float* arena, void* workspace, float* h_out, float* const* feats,
                           int flags, hipStream_t s) {
   R3M_REQUIRE(P.run.prepared && P.run.prepared == arena, "resnet_forward_prepared: this arena is not prepared for the plan (call "
               "r3m_resnet_inference_prepare first; any other forward of the plan invalidates the preparation)");
-  const bool small = !(flags & 1) && P.small_ctr_bytes > 0;
+  const bool small = !(flags & 1) && P.small.ticket_bytes() > 0;
   R3M_REQUIRE(!small || workspace, "resnet_forward_prepared: the plan needs a workspace of r3m_resnet_inference_workspace_bytes");
   Ctx c{P, P.run, params, nullptr, nullptr, arena, s, 0, 0, P.dtype};
   c.prepared = true;
   c.small_ws = small ? static_cast<char*>(workspace) : nullptr;
-  if (small && hipMemsetAsync(workspace, 0, (size_t)P.small_ctr_bytes, s) != hipSuccess) {
-    set_last_error("resnet_forward_prepared: cannot reset the split-K tickets");
-    return 1;
-  }
+  R3M_REQUIRE(!small || !P.small.reset(workspace, s), "resnet_forward_prepared: cannot reset the split-K tickets");
   return forward_sequence(c, x_nchw, nullptr, h_out, true, true, feats);
 }
 

@@ -414,13 +414,12 @@ int langrew_call_forward(const float* e0, const float* eg, const float* le, cons
 }
 
 // ---- the same evaluation WITHOUT a backward (a reward per control step: one frame or a handful per call). Nothing is kept for a
-// gradient: the input rows, two hidden buffers that the four Linears ping-pong between, and the split-K workspace of the few-row
-// kernel (conv_small.hip): a ticket block per Linear the rule takes, zeroed by ONE memset, and ONE slab area sized for the largest
-// launch (the launches are ordered on the stream). A Linear the rule leaves runs the conv_forward_launch of mlp_forward. The routing
-// is small_conv_plan(...).take of each layer's geometry: a pure function of (R, D, H, LD). Offsets in bytes, multiples of 256.
+// gradient: the input rows, two hidden buffers that the four Linears ping-pong between, and behind them the split-K workspace of the
+// few-row kernel, a SmallLaunchSet (engine.h has the layout) of the four Linears. One the routing rule leaves runs the
+// conv_forward_launch of mlp_forward; the rule is a pure function of (R, D, H, LD). Offsets in bytes, multiples of 256.
 struct LangInferWs {
-  size_t X, Ha, Hb, ctr0, ctr_bytes, ctr[4], slabs, total;
-  bool take[4];
+  size_t X, Ha, Hb, small, total;
+  SmallLaunchSet set;
 };
 static LangInferWs lang_infer_ws(int R, int D, int H, int LD) {
   LangInferWs w;
@@ -430,19 +429,8 @@ static LangInferWs lang_infer_ws(int R, int D, int H, int LD) {
   w.X = take((size_t)R * K1 * 4);
   w.Ha = take((size_t)R * H * 4);
   w.Hb = take((size_t)R * H * 4);
-  w.ctr0 = o;
-  size_t slab = 0;
-  for (int l = 0; l < 4; ++l) {
-    const ConvGeom g = linear_geom(R, l == 0 ? (int)K1 : H, H);
-    const int fl = EPI_BIAS | EPI_RELU;
-    w.take[l] = small_conv_plan(g, fl, 0).take != 0;
-    w.ctr[l] = o;
-    if (!w.take[l]) continue;
-    take(small_conv_ctr_bytes(g, fl, 0));
-    slab = std::max(slab, small_conv_slab_bytes(g, fl, 0));
-  }
-  w.ctr_bytes = o - w.ctr0;
-  w.slabs = take(slab);
+  for (int l = 0; l < 4; ++l) w.set.add(linear_geom(R, l == 0 ? (int)K1 : H, H), EPI_BIAS | EPI_RELU);
+  w.small = take(w.set.bytes());
   w.total = o;
   return w;
 }
@@ -469,23 +457,11 @@ int langrew_infer(const float* e0, const float* eg, const float* le, const float
   float* hb[2] = {reinterpret_cast<float*>(ws + w.Ha), reinterpret_cast<float*>(ws + w.Hb)};
   hipLaunchKernelGGL(lang_concat_kernel, dim3(R), dim3(256), 0, s, e0, eg, le, X, D, LD, R0 == 1 && R > 1 ? 1 : 0);
   if (int e = check_launch("lang_concat")) return e;
-  if (w.ctr_bytes && hipMemsetAsync(ws + w.ctr0, 0, w.ctr_bytes, s) != hipSuccess) {
-    set_last_error("langrew_infer: cannot reset the tickets");
-    return 1;
-  }
+  R3M_REQUIRE(!w.set.reset(ws + w.small, s), "langrew_infer: cannot reset the tickets");
   const float* in = X;
-  int K = d.K1;
   for (int l = 0; l < 4; ++l) {
-    float* out = hb[l & 1];
-    const ConvGeom g = linear_geom(R, K, H);
-    if (w.take[l]) {
-      if (int e = launch_conv_small(in, params + d.w[l], out, nullptr, params + d.b[l], g, EPI_BIAS | EPI_RELU, 0,
-                                    reinterpret_cast<unsigned*>(ws + w.ctr[l]), reinterpret_cast<float*>(ws + w.slabs), s))
-        return e;
-    } else if (int e = conv_forward_launch(in, params + d.w[l], out, nullptr, params + d.b[l], g, EPI_BIAS | EPI_RELU, DT_F32, s))
-      return e;
-    in = out;
-    K = H;
+    if (int e = w.set.linear(l, 0, ws + w.small, in, params + d.w[l], params + d.b[l], hb[l & 1], s)) return e;
+    in = hb[l & 1];
   }
   hipLaunchKernelGGL((gemv_fwd_kernel<float>), dim3(ceil_div(R, 4)), dim3(256), 0, s, in, params + d.w[4], params + d.b[4], score, R, H);
   return check_launch("gemv_fwd");

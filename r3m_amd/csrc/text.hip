@@ -202,7 +202,7 @@ static int launch_text_embed(const int* ids, const float* word, const float* pos
   return check_launch("text_embed");
 }
 
-static int launch_bias_gelu(float* x, const float* bias, long long rows, int C, hipStream_t s) {
+int launch_bias_gelu(float* x, const float* bias, long long rows, int C, hipStream_t s) {
   R3M_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && rows * C / 4 < (1LL << 31) * 256, "bias_gelu: rows=%lld, C=%d (C must be a positive multiple of 4)",
               rows, C);
   const long long n4 = rows * C / 4;
@@ -350,44 +350,32 @@ static int text_check_shape(const TextDims& d, int B, int T, const char* what) {
   return attention_check(B, T, d.n_heads, d.dim / d.n_heads, what);
 }
 
-// few_rows (r3m_text_forward_small): behind the base workspace, a ticket block per Linear the few-row kernel (conv_small.hip) takes at
-// R rows — four per layer, every launch its own, all zeroed by ONE memset per call — and ONE slab area sized for the largest launch.
-// The four Linear shapes are the same in every layer, so is the routing: small_conv_plan(...).take, a pure function of (R, dims).
+// The four Linears of a layer as a SmallLaunchSet (engine.h has the workspace layout), repeated once per layer: the shapes are the same
+// in every layer, so is the routing, a pure function of (R, dims). few_rows (r3m_text_forward_small): the rule decides, and the
+// set's workspace lies behind the base workspace, from small_off on. Otherwise every entry is the ordinary launch and the set needs no bytes.
 enum { TL_QKV = 0, TL_OUT = 1, TL_LIN1 = 2, TL_LIN2 = 3 };
-struct TextSmallWs {
-  bool take[4];
-  size_t ctr_each[4];        // ticket bytes of one launch of Linear i (0: not taken)
-  size_t ctr0, ctr_bytes, slabs, total;   // bytes from the workspace's start
+struct TextSmall {
+  SmallLaunchSet set;
+  size_t small_off, total;   // bytes from the workspace's start
 };
-static ConvGeom text_small_geom(const TextDims& d, int R, int i) {
-  const int D = d.dim, F = d.ffn;
-  return text_linear_geom(R, i == TL_LIN2 ? F : D, i == TL_QKV ? 3 * D : i == TL_OUT ? D : i == TL_LIN1 ? F : D);
-}
-static int text_small_flags(int i) { return i == TL_LIN1 ? (EPI_BIAS | EPI_GELU) : EPI_BIAS; }
-static TextSmallWs text_small_ws(const TextDims& d, long long rows) {
-  TextSmallWs w;
-  size_t o = ((size_t)text_ws(d, rows).total * 4 + 255) / 256 * 256;
-  w.ctr0 = o;
-  size_t per_layer = 0, slab = 0;
-  for (int i = 0; i < 4; ++i) {
-    const ConvGeom g = text_small_geom(d, (int)rows, i);
-    const int fl = text_small_flags(i);
-    w.take[i] = rows <= SMALL_CONV_ROWS_MAX && small_conv_plan(g, fl, 0).take != 0;
-    w.ctr_each[i] = w.take[i] ? small_conv_ctr_bytes(g, fl, 0) : 0;
-    per_layer += w.ctr_each[i];
-    if (w.take[i]) slab = std::max(slab, small_conv_slab_bytes(g, fl, 0));
-  }
-  w.ctr_bytes = per_layer * d.n_layers;
-  o += w.ctr_bytes;
-  w.slabs = o;
-  w.total = o + (slab + 255) / 256 * 256;
+static TextSmall text_small(const TextDims& d, long long rows, bool few_rows) {
+  TextSmall w;
+  const int R = (int)rows, D = d.dim, F = d.ffn;
+  const SmallRoute route = few_rows ? SMALL_BY_RULE : SMALL_NEVER;
+  w.set.reps = d.n_layers;
+  w.set.add(text_linear_geom(R, D, 3 * D), EPI_BIAS, 0, route);              // TL_QKV
+  w.set.add(text_linear_geom(R, D, D), EPI_BIAS, 0, route);                  // TL_OUT
+  w.set.add(text_linear_geom(R, D, F), EPI_BIAS | EPI_GELU, 0, route);       // TL_LIN1: bias + GELU in the store
+  w.set.add(text_linear_geom(R, F, D), EPI_BIAS, 0, route);                  // TL_LIN2
+  w.small_off = ((size_t)text_ws(d, rows).total * 4 + 255) / 256 * 256;
+  w.total = w.small_off + (w.set.bytes() + 255) / 256 * 256;
   return w;
 }
 
 // few_rows == false: the launches of r3m_text_forward, exactly
 static int text_forward(const int* ids, const int* mask, const float* P, float* feats, float* hidden, float* ws, int B, int T,
                         const TextDims& d, int pool, bool few_rows, hipStream_t s) {
-  const int D = d.dim, F = d.ffn, R = B * T, hd = D / d.n_heads;
+  const int D = d.dim, R = B * T, hd = D / d.n_heads;
   const float eps = 1e-12f;
   const TextWs w = text_ws(d, R);
   float* x = ws + w.x;
@@ -396,46 +384,18 @@ static int text_forward(const int* ids, const int* mask, const float* P, float* 
   float* ctx = ws + w.ctx;
   float* big = ws + w.big;
   const long long V = d.vocab, MP = d.max_pos;
-  TextSmallWs sw;
-  memset(&sw, 0, sizeof sw);
-  char* wsb = reinterpret_cast<char*>(ws);
-  size_t ctr_next = 0;
-  if (few_rows) {
-    sw = text_small_ws(d, R);
-    ctr_next = sw.ctr0;
-    if (sw.ctr_bytes && hipMemsetAsync(wsb + sw.ctr0, 0, sw.ctr_bytes, s) != hipSuccess) {
-      set_last_error("text_forward_small: cannot reset the tickets");
-      return 1;
-    }
-  }
-  // Linear i of a layer on the few-row kernel where the plan takes it; returns -1 where it does not (the caller runs today's launches)
-  auto small = [&](int i, const float* in, const float* wt, const float* bias, float* out) -> int {
-    if (!sw.take[i]) return -1;
-    unsigned* ctr = reinterpret_cast<unsigned*>(wsb + ctr_next);
-    ctr_next += sw.ctr_each[i];
-    return launch_conv_small(in, wt, out, nullptr, bias, text_small_geom(d, R, i), text_small_flags(i), 0, ctr,
-                             reinterpret_cast<float*>(wsb + sw.slabs), s);
-  };
+  const TextSmall sw = text_small(d, R, few_rows);
+  char* sws = reinterpret_cast<char*>(ws) + sw.small_off;
+  R3M_REQUIRE(!sw.set.reset(sws, s), "text_forward_small: cannot reset the tickets");
   TRY(launch_text_embed(ids, P, P + V * D, P + (V + MP) * D, P + (V + MP + 1) * D, x, B, T, D, d.vocab, eps, s));
   for (int l = 0; l < d.n_layers; ++l) {
     const TextLayer t = text_layer(d, l);
-    int e = small(TL_QKV, x, P + t.wqkv, P + t.bqkv, big);
-    if (e < 0) e = conv_forward_launch(x, P + t.wqkv, big, nullptr, P + t.bqkv, text_linear_geom(R, D, 3 * D), EPI_BIAS, DT_F32, s);
-    TRY(e);
+    TRY(sw.set.linear(TL_QKV, l, sws, x, P + t.wqkv, P + t.bqkv, big, s));
     TRY(launch_attention(big, mask, ctx, B, T, d.n_heads, hd, s));
-    e = small(TL_OUT, ctx, P + t.wo, P + t.bo, tmp);
-    if (e < 0) e = conv_forward_launch(ctx, P + t.wo, tmp, nullptr, P + t.bo, text_linear_geom(R, D, D), EPI_BIAS, DT_F32, s);
-    TRY(e);
+    TRY(sw.set.linear(TL_OUT, l, sws, ctx, P + t.wo, P + t.bo, tmp, s));
     TRY(launch_layernorm(tmp, x, P + t.ln1g, P + t.ln1b, sa, R, D, eps, s));
-    e = small(TL_LIN1, sa, P + t.w1, P + t.b1, big);       // bias + GELU in the store
-    if (e < 0) {
-      TRY(conv_forward_launch(sa, P + t.w1, big, nullptr, nullptr, text_linear_geom(R, D, F), 0, DT_F32, s));
-      e = launch_bias_gelu(big, P + t.b1, R, F, s);
-    }
-    TRY(e);
-    e = small(TL_LIN2, big, P + t.w2, P + t.b2, tmp);
-    if (e < 0) e = conv_forward_launch(big, P + t.w2, tmp, nullptr, P + t.b2, text_linear_geom(R, F, D), EPI_BIAS, DT_F32, s);
-    TRY(e);
+    TRY(sw.set.linear(TL_LIN1, l, sws, sa, P + t.w1, P + t.b1, big, s));
+    TRY(sw.set.linear(TL_LIN2, l, sws, big, P + t.w2, P + t.b2, tmp, s));
     float* y = (l == d.n_layers - 1 && hidden) ? hidden : x;     // the last hidden state goes straight to the caller's buffer
     TRY(launch_layernorm(tmp, sa, P + t.ln2g, P + t.ln2b, y, R, D, eps, s));
     x = y;
@@ -479,7 +439,7 @@ static int text_forward_entry(const char* what, bool few_rows, const int* ids, c
   TRY(text_dims(dims, &d, what));
   TRY(text_check_shape(d, B, T, what));
   R3M_REQUIRE(pool == 0 || pool == 1, "%s: pool=%d (0: mean over all positions, 1: mean over mask != 0)", what, pool);
-  const size_t need = few_rows ? text_small_ws(d, (long long)B * T).total : (size_t)text_ws(d, (long long)B * T).total * 4;
+  const size_t need = few_rows ? text_small(d, (long long)B * T, true).total : (size_t)text_ws(d, (long long)B * T).total * 4;
   R3M_REQUIRE(ws_bytes >= need, "%s: workspace too small (%zu bytes, need %zu)", what, ws_bytes, need);
   R3M_REQUIRE((reinterpret_cast<uintptr_t>(params) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(feats) & 15) == 0 && (reinterpret_cast<uintptr_t>(hidden) & 15) == 0,
@@ -493,7 +453,7 @@ int r3m_text_forward(const int* ids, const int* mask, const float* params, float
 size_t r3m_text_small_workspace_bytes(const int* dims, int B, int T) {
   TextDims d;
   if (text_dims(dims, &d, "text_small_workspace_bytes") || text_check_shape(d, B, T, "text_small_workspace_bytes")) return 0;
-  return text_small_ws(d, (long long)B * T).total;
+  return text_small(d, (long long)B * T, true).total;
 }
 int r3m_text_forward_small(const int* ids, const int* mask, const float* params, float* feats, float* hidden, void* ws, size_t ws_bytes,
                            int B, int T, const int* dims, int pool, r3m_stream_t stream) {
